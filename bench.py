@@ -429,6 +429,35 @@ def lazy_part(ncl, ng, am, feats, dev, full_states, full_arcs, gnet):
             "identical_to_composed_first": "%d/%d" % (same, len(feats))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+REF_STATS = ("tot_active_emit_hyps", "tot_active_end_hyps", "tot_active_models", "tot_proc_emit_hyps", "tot_proc_end_hyps")
+
+
+def dump_outputs(path, hyps):
+    """--dump-outputs: what a caller of the timed path receives for its last step, one .npy per field, utterance order.
+    Words of all utterances back to back (chain order, newest first, as the records hold them), word_offsets[u] .. [u + 1]
+    the utterance's; n_words = -1 where no token survived.  Integers are written as float64 (exact for int32).  The
+    reference's five statistics ride along where the records carry them (one rank: Hyp.stats; gathered records do not)."""
+    get = (lambda h, k: h[k]) if hyps and isinstance(hyps[0], dict) else getattr
+    n = np.array([get(h, "n") for h in hyps], np.float64)
+    words = [max(0, int(x)) for x in n]
+    offs = np.zeros(len(hyps) + 1, np.float64)
+    offs[1:] = np.cumsum(words)
+    cat = lambda k, dt: (np.concatenate([np.asarray(get(h, k), dt)[:w] for h, w in zip(hyps, words)]) if hyps else np.zeros(0, dt))
+    out = {"n_words": n, "word_offsets": offs,
+           "label": cat("label", np.float64), "time": cat("time", np.float64),
+           "score": cat("score", np.float32), "ac": cat("ac", np.float32), "lm": cat("lm", np.float32),
+           "totals": np.array([[get(h, "tot_score"), get(h, "tot_ac"), get(h, "tot_lm")] for h in hyps], np.float32).reshape(-1, 3)}
+    if hyps and not isinstance(hyps[0], dict):
+        out["ref_stats"] = np.array([[h.stats[k] for k in REF_STATS] for h in hyps], np.float64).reshape(-1, len(REF_STATS))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:                       # (1-best records are a few hundred bytes per utterance: never near this)
+        raise SystemExit("bench.py --dump-outputs: %d bytes of records exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside torchrun: start the N ranks ourselves."""
     with socket.socket() as s:
@@ -472,6 +501,8 @@ def main():
                     help="exact (default): the reference's roundings, log-likelihoods bit-identical to the CPU oracle; fast: fused multiply-add "
                          "distance + fp32 logAdd on the hardware's exp / log (jd_dec_set_scoring: labels and times identical, scores within 1e-4)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the 1-best records of the last timed step (utterance order) as DIR/<name>.npy")
     args = ap.parse_args()
 
     share_gpu = os.environ.get("JD_BENCH_SHARE_GPU") == "1"      # development: all ranks on GPU 0, gloo
@@ -772,6 +803,8 @@ def main():
         frames_total = float(frames_local); frames_timed_total = float(frames_timed)
         n_gathered = len(hyps)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, allh if world > 1 else hyps)
     if rank != 0:
         if world > 1:
             dist.barrier(**bar_kw)                      # rank 0 finishes its CPU baseline first

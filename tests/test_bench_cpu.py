@@ -58,3 +58,27 @@ def test_reference_cpu_constants_come_from_the_committed_file():
     assert r["B1_WFSTDecoderLite_fps"] == f["WFSTDecoderLite"]["frames_per_s"] and r["B2_WFSTDecoderLiteThreading_fps"] == f["WFSTDecoderLiteThreading"]["frames_per_s"]
     assert r["B1_identical_to_oracle"] == "64/64" and r["B2_identical_to_oracle"] == "64/64"
     assert all(len(v) < 128 for v in r.values() if isinstance(v, str)), r      # (the driver's record cuts longer strings)
+
+
+def test_dump_outputs_writes_the_records_of_a_step(tmp_path):
+    """--dump-outputs: one float32 / float64 array per field, the words of all utterances back to back behind word_offsets,
+    -1 words where nothing survived; records from one rank (Hyp) and gathered records (dicts) give the same arrays"""
+    from juicer_amd.capi import Hyp
+    st = {k: i + 10 for i, k in enumerate(bench.REF_STATS)}
+    st["tot_recs_read"] = 99
+    hyps = [Hyp(n=2, label=np.array([5, 3], np.int32), time=np.array([40, 12], np.int32), score=np.array([-9.5, -4.25], np.float32),
+                ac=np.array([-8.0, -4.0], np.float32), lm=np.array([-1.5, -0.25], np.float32), tot_score=-9.5, tot_ac=-8.0, tot_lm=-1.5, stats=st),
+            Hyp(n=-1, label=np.zeros(0, np.int32), time=np.zeros(0, np.int32), score=np.zeros(0, np.float32), ac=np.zeros(0, np.float32),
+                lm=np.zeros(0, np.float32), tot_score=0.0, tot_ac=0.0, tot_lm=0.0, stats=st)]
+    bench.dump_outputs(str(tmp_path / "one"), hyps)
+    got = {f[:-4]: np.load(str(tmp_path / "one" / f)) for f in os.listdir(str(tmp_path / "one"))}
+    assert set(got) == {"n_words", "word_offsets", "label", "time", "score", "ac", "lm", "totals", "ref_stats"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["n_words"].tolist() == [2, -1] and got["word_offsets"].tolist() == [0, 2, 2]
+    assert got["label"].tolist() == [5, 3] and got["time"].tolist() == [40, 12] and got["score"].tolist() == [-9.5, -4.25]
+    assert got["totals"].shape == (2, 3) and got["ref_stats"].tolist() == [[10, 11, 12, 13, 14]] * 2
+    gathered = [dict(n=h.n, n_frames=50, label=h.label, time=h.time, score=h.score, ac=h.ac, lm=h.lm, tot_score=h.tot_score,
+                     tot_ac=h.tot_ac, tot_lm=h.tot_lm) for h in hyps]
+    bench.dump_outputs(str(tmp_path / "all"), gathered)
+    for f in os.listdir(str(tmp_path / "all")):
+        assert np.array_equal(np.load(str(tmp_path / "all" / f)), got[f[:-4]]), f
