@@ -598,6 +598,12 @@ int jd_am_score_frames(const jd_am *a, int32_t device, const float *frames,
  * the kernels' own expf for x[0..n), evaluated on HIP device `device`, or by its host twin
  * (same source) when device == -1.  tests/test_expf.py compares both with the host libm. */
 int jd_debug_expf(int32_t device, const float *x, int64_t n, float *out);
+/* ... and of the rest of logAdd.  jd_debug_log1pe: log(1.0 + (double)expf(d[i])) in double for d[i] in [-19, 0]; variant 0 =
+ * the kernels' replica of the host libm's log, 1 = the table value they round first.  jd_debug_log_add: logAdd(x[i], y[i]);
+ * variant 0 = the generic kernel's, 1 = jd_gmm_kernel39's pairwise step (elements 2j and 2j + 1 are one pair), 2 = the
+ * JD_SCORE_FAST kernel's (device only).  tests/test_logadd.py compares them with the host libm and the CPU oracle. */
+int jd_debug_log1pe(int32_t device, int32_t variant, const float *d, int64_t n, double *out);
+int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const float *y, int64_t n, float *out);
 
 const char *jd_last_error(void);
 const char *jd_version(void);

@@ -96,7 +96,7 @@ EXPORTS = [
     "jd_dec_prefetch_scores", "jd_streams_push", "jd_dec_info",
     "jd_broker_create", "jd_broker_destroy", "jd_broker_open", "jd_broker_close", "jd_broker_init", "jd_broker_push",
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
-    "jd_dec_set_scoring", "jd_am_score_frames_mode",
+    "jd_dec_set_scoring", "jd_am_score_frames_mode", "jd_debug_log1pe", "jd_debug_log_add",
 ]
 
 _lib = None
@@ -301,6 +301,27 @@ class Models:
         return cls(h)
 
     @classmethod
+    def from_flat(cls, det, mean, ivar, n_mix):
+        """Models from the prepared arrays as they are (jd_am_create_flat): det [G, M], mean / ivar [G, M, D] (inverse
+        variances), n_mix [G]; one 3-state HMM on tied state 0 as the topology.  Scoring a frame equal to a component's mean
+        gives its det exactly."""
+        det, mean, ivar, nm = _f32(det), _f32(mean), _f32(ivar), _i32(n_mix)
+        G, M, D = mean.shape
+        assert det.shape == (G, M) and ivar.shape == mean.shape and nm.shape == (G,)
+        hn, hg, ht, tn = _i32([3]), _i32([-1, 0, -1]), _i32([0]), _i32([3])
+        tee = _f32([LOG_ZERO])
+        trP = np.full((1, 3, 3), LOG_ZERO, np.float32)
+        trP[0, 0, 1] = 0.0
+        trP[0, 1, 1] = trP[0, 1, 2] = np.log(np.float32(0.5))
+        se = np.array([[[0, 0], [0, 2], [1, 2]]], np.int16)
+        h = C.c_void_p()
+        _check(lib().jd_am_create_flat(C.byref(h), C.c_int32(D), C.c_int32(G), C.c_int32(M), _p(nm, C.c_int32), _p(det, C.c_float),
+                                       _p(mean, C.c_float), _p(ivar, C.c_float), C.c_int32(1), C.c_int32(3), _p(hn, C.c_int32),
+                                       _p(hg, C.c_int32), _p(ht, C.c_int32), _p(tee, C.c_float), C.c_int32(1), _p(tn, C.c_int32),
+                                       _p(trP, C.c_float), _p(se, C.c_int16)))
+        return cls(h)
+
+    @classmethod
     def from_mmf_file(cls, path):
         L = lib()
         h = C.c_void_p()
@@ -386,6 +407,32 @@ class Models:
         if getattr(self, "h", None) and _lib is not None:
             _lib.jd_am_destroy(self.h)
             self.h = None
+
+
+# jd_debug_log_add's variants: the generic kernel's logAdd, jd_gmm_kernel39's pairwise step, jd_gmm_fast39's (device only)
+LOGADD_GENERIC, LOGADD_PAIR, LOGADD_FAST = 0, 1, 2
+# jd_debug_log1pe's: the replica of the libm's log(1 + e), the table value
+LOG1PE_LIBM, LOG1PE_TABLE = 0, 1
+
+
+def debug_log_add(x, y, variant: int, device: int = -1):
+    """logAdd(x[i], y[i]) as the kernels compute it (device -1: the host twin compiled from the same source)."""
+    x, y = _f32(x), _f32(y)
+    assert x.shape == y.shape and x.ndim == 1
+    out = np.empty_like(x)
+    _check(lib().jd_debug_log_add(C.c_int32(device), C.c_int32(variant), _p(x, C.c_float), _p(y, C.c_float),
+                                  C.c_int64(x.shape[0]), _p(out, C.c_float)))
+    return out
+
+
+def debug_log1pe(d, variant: int, device: int = -1):
+    """log(1.0 + (double)expf(d[i])) in double, d[i] in [-19, 0], as the kernels compute it."""
+    d = _f32(d)
+    assert d.ndim == 1
+    out = np.empty(d.shape[0], np.float64)
+    _check(lib().jd_debug_log1pe(C.c_int32(device), C.c_int32(variant), _p(d, C.c_float), C.c_int64(d.shape[0]),
+                                 _p(out, C.c_double)))
+    return out
 
 
 class Decoder:

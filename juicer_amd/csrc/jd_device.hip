@@ -1764,6 +1764,109 @@ extern "C" int jd_debug_expf(int32_t device, const float *x, int64_t n, float *o
     return JD_OK;
 }
 
+// Test hooks for logAdd (HTKFlatModels.cpp:266-293), jd_debug_expf's companions; device == -1 runs the host twins compiled
+// from the same source.  jd_debug_log1pe: out[i] = log(1.0 + (double)expf(d[i])) in double, d[i] in [-19, 0] - variant 0
+// jd_log_libm_impl (the libm's value), 1 jd_log1pe_table (the table value the gate rounds).  jd_debug_log_add: out[i] =
+// logAdd(x[i], y[i]) - variant 0 jd_log_add (the generic kernel's), 1 jd_log_add2x2 (jd_gmm_kernel39's: elements 2j and 2j + 1
+// are one call's pair), 2 jd_log_add_fast (jd_gmm_fast39's; device only).
+__global__ void jd_debug_log1pe_kernel(const float *d, long long n, int variant, const JdLogTab *tab, double *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double e = (double)jd_expf(d[i]);
+    out[i] = variant ? jd_log1pe_table(e, tab) : jd_log_libm_impl(1.0 + e, jd_log_tab);
+}
+__global__ void jd_debug_log_add_kernel(const float *x, const float *y, long long n, int variant, const JdLogTab *tab, float *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (variant == 1) {
+        const long long j = 2 * i;
+        if (j >= n) return;
+        float a0 = x[j], a1 = (j + 1 < n) ? x[j + 1] : a0;
+        const float c0 = y[j], c1 = (j + 1 < n) ? y[j + 1] : c0;
+        jd_log_add2x2(a0, a1, c0, c1, tab, jd_exp2f_tab);                 // NaN: jd_gmm_kernel39 scores the cell again
+        out[j] = (a0 != a0) ? jd_log_add(x[j], c0, tab) : a0;
+        if (j + 1 < n) out[j + 1] = (a1 != a1) ? jd_log_add(x[j + 1], c1, tab) : a1;
+        return;
+    }
+    if (i < n) out[i] = variant ? jd_log_add_fast(x[i], y[i]) : jd_log_add(x[i], y[i], tab);
+}
+static int debug_upload_logtab(JdLogTab **d_tab)
+{
+    JdLogTab t[129];
+    jd_fill_logtab(t);
+    HIPCHK(hipMalloc(d_tab, sizeof t));
+    HIPCHK(hipMemcpy(*d_tab, t, sizeof t, hipMemcpyHostToDevice));
+    return JD_OK;
+}
+extern "C" int jd_debug_log1pe(int32_t device, int32_t variant, const float *d, int64_t n, double *out)
+{
+    if (!d || !out || n < 0 || (variant != 0 && variant != 1)) return jd_fail(JD_EINVAL, "jd_debug_log1pe: bad argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (!(d[i] >= -19.0f && d[i] <= 0.0f)) return jd_fail(JD_EINVAL, "jd_debug_log1pe: d[%lld] outside [-19, 0]", (long long)i);
+    if (device == -1) {
+        JdLogTab t[129];
+        jd_fill_logtab(t);
+        for (int64_t i = 0; i < n; ++i) {
+            const double e = (double)jd_expf_impl(d[i], jd_exp2f_tab_host);
+            out[i] = variant ? jd_log1pe_table(e, t) : jd_log_libm_impl(1.0 + e, jd_log_tab_host);
+        }
+        return JD_OK;
+    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    float *dd = nullptr;
+    double *dy = nullptr;
+    JdLogTab *dt = nullptr;
+    rc = debug_upload_logtab(&dt);
+    if (rc) return rc;
+    HIPCHK(hipMalloc(&dd, std::max<size_t>((size_t)n, 1) * sizeof(float)));
+    HIPCHK(hipMalloc(&dy, std::max<size_t>((size_t)n, 1) * sizeof(double)));
+    HIPCHK(hipMemcpy(dd, d, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (n) hipLaunchKernelGGL(jd_debug_log1pe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dd, (long long)n, (int)variant, dt, dy);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    (void)hipFree(dd); (void)hipFree(dy); (void)hipFree(dt);
+    return JD_OK;
+}
+extern "C" int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const float *y, int64_t n, float *out)
+{
+    if (!x || !y || !out || n < 0 || variant < 0 || variant > 2) return jd_fail(JD_EINVAL, "jd_debug_log_add: bad argument");
+    if (device == -1) {
+        if (variant == 2) return jd_fail(JD_EINVAL, "jd_debug_log_add: jd_log_add_fast has no host twin (device only)");
+        JdLogTab t[129];
+        jd_fill_logtab(t);
+        if (variant == 0)
+            for (int64_t i = 0; i < n; ++i) out[i] = jd_log_add_impl(x[i], y[i], t, jd_exp2f_tab_host, jd_log_tab_host);
+        else
+            for (int64_t j = 0; j < n; j += 2) {
+                float a0 = x[j], a1 = (j + 1 < n) ? x[j + 1] : a0;
+                const float c0 = y[j], c1 = (j + 1 < n) ? y[j + 1] : c0;
+                jd_log_add2x2(a0, a1, c0, c1, t, jd_exp2f_tab_host);
+                out[j] = (a0 != a0) ? jd_log_add_impl(x[j], c0, t, jd_exp2f_tab_host, jd_log_tab_host) : a0;
+                if (j + 1 < n) out[j + 1] = (a1 != a1) ? jd_log_add_impl(x[j + 1], c1, t, jd_exp2f_tab_host, jd_log_tab_host) : a1;
+            }
+        return JD_OK;
+    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    float *dx = nullptr, *dy = nullptr, *dz = nullptr;
+    JdLogTab *dt = nullptr;
+    rc = debug_upload_logtab(&dt);
+    if (rc) return rc;
+    const size_t bytes = std::max<size_t>((size_t)n, 1) * sizeof(float);
+    HIPCHK(hipMalloc(&dx, bytes));
+    HIPCHK(hipMalloc(&dy, bytes));
+    HIPCHK(hipMalloc(&dz, bytes));
+    HIPCHK(hipMemcpy(dx, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dy, y, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (n) hipLaunchKernelGGL(jd_debug_log_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dy, (long long)n, (int)variant, dt, dz);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dz, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dz); (void)hipFree(dt);
+    return JD_OK;
+}
+
 // Diagnostics: what part of a likelihood table does the search read?  (SURVEY.md 8d's Ug: the reference scores a tied
 // state only when a token that passed the emit threshold asks for it, WFSTDecoderLite.cpp:409-411; here every state of
 // every frame is scored.)  enable != 0: the slab's bitmap is cleared and every cell phase A adds to a token is marked from

@@ -1,7 +1,7 @@
 // jd_gmm.h - the companion scoring kernels of juicer_amd (included by jd_device.hip; gfx950 only):
 // HTKFlatModels::calcGMMOutput + logAdd (src/HTKFlatModels.cpp:226-293) for every tied state of every frame of a
 // likelihood table - jd_gmm_kernel39 (D = 39: two frames per lane, packed fp32, the reference's roundings) and the
-// generic jd_gmm_kernel - with the bit-exact replica of glibc's expf they need.
+// generic jd_gmm_kernel - with the bit-exact replicas of glibc's expf and log they need.
 #pragma once
 
 // glibc 2.35 expf (sysdeps/ieee754/flt-32/e_expf.c, ARM optimized-routines
@@ -47,13 +47,183 @@ __host__ __device__ __forceinline__ float jd_expf_impl(float x, const unsigned l
 }
 __device__ __forceinline__ float jd_expf(float x) { return jd_expf_impl(x, jd_exp2f_tab); }
 
-// HTKFlatModels::logAdd, HTKFlatModels.cpp:266-293
-__device__ __forceinline__ float jd_log_add(float x, float y)
+// glibc 2.35 log (sysdeps/ieee754/dbl-64/e_log.c, ARM optimized-routines algorithm) as the x86-64 libm runs it: the
+// FMA build its ifunc selects, with the contractions GCC makes under -mfma written out as fma() here (this library builds
+// with -ffp-contract=off).  __log_data: 128 (invc, logc) pairs, then ln2hi / ln2lo and the polynomials below.  Only
+// what logAdd hands it is supported: y = 1 + e, e in (0, 1] - positive, normal, finite (no special cases).  Equal to
+// the host libm for every float d in [-18.42, 0] (tests/test_logadd.py, through jd_debug_log1pe).
+#define JD_LOG_TAB                                                                                          \
+    0x3ff734f0c3e0de9fULL, 0xbfd7cc7f79e69000ULL, 0x3ff713786a2ce91fULL, 0xbfd76feec20d0000ULL,   \
+    0x3ff6f26008fab5a0ULL, 0xbfd713e31351e000ULL, 0x3ff6d1a61f138c7dULL, 0xbfd6b85b38287800ULL,   \
+    0x3ff6b1490bc5b4d1ULL, 0xbfd65d5590807800ULL, 0x3ff69147332f0cbaULL, 0xbfd602d076180000ULL,   \
+    0x3ff6719f18224223ULL, 0xbfd5a8ca86909000ULL, 0x3ff6524f99a51ed9ULL, 0xbfd54f4356035000ULL,   \
+    0x3ff63356aa8f24c4ULL, 0xbfd4f637c36b4000ULL, 0x3ff614b36b9ddc14ULL, 0xbfd49da7fda85000ULL,   \
+    0x3ff5f66452c65c4cULL, 0xbfd445923989a800ULL, 0x3ff5d867b5912c4fULL, 0xbfd3edf439b0b800ULL,   \
+    0x3ff5babccb5b90deULL, 0xbfd396ce448f7000ULL, 0x3ff59d61f2d91a78ULL, 0xbfd3401e17bda000ULL,   \
+    0x3ff5805612465687ULL, 0xbfd2e9e2ef468000ULL, 0x3ff56397cee76bd3ULL, 0xbfd2941b3830e000ULL,   \
+    0x3ff54725e2a77f93ULL, 0xbfd23ec58cda8800ULL, 0x3ff52aff42064583ULL, 0xbfd1e9e129279000ULL,   \
+    0x3ff50f22dbb2bddfULL, 0xbfd1956d2b48f800ULL, 0x3ff4f38f4734ded7ULL, 0xbfd141679ab9f800ULL,   \
+    0x3ff4d843cfde2840ULL, 0xbfd0edd094ef9800ULL, 0x3ff4bd3ec078a3c8ULL, 0xbfd09aa518db1000ULL,   \
+    0x3ff4a27fc3e0258aULL, 0xbfd047e65263b800ULL, 0x3ff4880524d48434ULL, 0xbfcfeb224586f000ULL,   \
+    0x3ff46dce1b192d0bULL, 0xbfcf474a7517b000ULL, 0x3ff453d9d3391854ULL, 0xbfcea4443d103000ULL,   \
+    0x3ff43a2744b4845aULL, 0xbfce020d44e9b000ULL, 0x3ff420b54115f8fbULL, 0xbfcd60a22977f000ULL,   \
+    0x3ff40782da3ef4b1ULL, 0xbfccc00104959000ULL, 0x3ff3ee8f5d57fe8fULL, 0xbfcc202956891000ULL,   \
+    0x3ff3d5d9a00b4ce9ULL, 0xbfcb81178d811000ULL, 0x3ff3bd60c010c12bULL, 0xbfcae2c9ccd3d000ULL,   \
+    0x3ff3a5242b75dab8ULL, 0xbfca45402e129000ULL, 0x3ff38d22cd9fd002ULL, 0xbfc9a877681df000ULL,   \
+    0x3ff3755bc5847a1cULL, 0xbfc90c6d69483000ULL, 0x3ff35dce49ad36e2ULL, 0xbfc87120a645c000ULL,   \
+    0x3ff34679984dd440ULL, 0xbfc7d68fb4143000ULL, 0x3ff32f5cceffcb24ULL, 0xbfc73cb83c627000ULL,   \
+    0x3ff3187775a10d49ULL, 0xbfc6a39a9b376000ULL, 0x3ff301c8373e3990ULL, 0xbfc60b3154b7a000ULL,   \
+    0x3ff2eb4ebb95f841ULL, 0xbfc5737d76243000ULL, 0x3ff2d50a0219a9d1ULL, 0xbfc4dc7b8fc23000ULL,   \
+    0x3ff2bef9a8b7fd2aULL, 0xbfc4462c51d20000ULL, 0x3ff2a91c7a0c1babULL, 0xbfc3b08abc830000ULL,   \
+    0x3ff293726014b530ULL, 0xbfc31b996b490000ULL, 0x3ff27dfa5757a1f5ULL, 0xbfc2875490a44000ULL,   \
+    0x3ff268b39b1d3bbfULL, 0xbfc1f3b9f879a000ULL, 0x3ff2539d838ff5bdULL, 0xbfc160c8252ca000ULL,   \
+    0x3ff23eb7aac9083bULL, 0xbfc0ce7f57f72000ULL, 0x3ff22a012ba940b6ULL, 0xbfc03cdc49fea000ULL,   \
+    0x3ff2157996cc4132ULL, 0xbfbf57bdbc4b8000ULL, 0x3ff201201dd2fc9bULL, 0xbfbe370896404000ULL,   \
+    0x3ff1ecf4494d480bULL, 0xbfbd17983ef94000ULL, 0x3ff1d8f5528f6569ULL, 0xbfbbf9674ed8a000ULL,   \
+    0x3ff1c52311577e7cULL, 0xbfbadc79202f6000ULL, 0x3ff1b17c74cb26e9ULL, 0xbfb9c0c3e7288000ULL,   \
+    0x3ff19e010c2c1ab6ULL, 0xbfb8a646b372c000ULL, 0x3ff18ab07bb670bdULL, 0xbfb78d01b3ac0000ULL,   \
+    0x3ff1778a25efbcb6ULL, 0xbfb674f145380000ULL, 0x3ff1648d354c31daULL, 0xbfb55e0e6d878000ULL,   \
+    0x3ff151b990275fddULL, 0xbfb4485cdea1e000ULL, 0x3ff13f0ea432d24cULL, 0xbfb333d94d6aa000ULL,   \
+    0x3ff12c8b7210f9daULL, 0xbfb22079f8c56000ULL, 0x3ff11a3028ecb531ULL, 0xbfb10e4698622000ULL,   \
+    0x3ff107fbda8434afULL, 0xbfaffa6c6ad20000ULL, 0x3ff0f5ee0f4e6bb3ULL, 0xbfadda8d4a774000ULL,   \
+    0x3ff0e4065d2a9fceULL, 0xbfabbcece4850000ULL, 0x3ff0d244632ca521ULL, 0xbfa9a1894012c000ULL,   \
+    0x3ff0c0a77ce2981aULL, 0xbfa788583302c000ULL, 0x3ff0af2f83c636d1ULL, 0xbfa5715e67d68000ULL,   \
+    0x3ff09ddb98a01339ULL, 0xbfa35c8a49658000ULL, 0x3ff08cabaf52e7dfULL, 0xbfa149e364154000ULL,   \
+    0x3ff07b9f2f4e28fbULL, 0xbf9e72c082eb8000ULL, 0x3ff06ab58c358f19ULL, 0xbf9a55f152528000ULL,   \
+    0x3ff059eea5ecf92cULL, 0xbf963d62cf818000ULL, 0x3ff04949cdd12c90ULL, 0xbf9228fb8caa0000ULL,   \
+    0x3ff038c6c6f0ada9ULL, 0xbf8c317b20f90000ULL, 0x3ff02865137932a9ULL, 0xbf8419355daa0000ULL,   \
+    0x3ff0182427ea7348ULL, 0xbf781203c2ec0000ULL, 0x3ff008040614b195ULL, 0xbf60040979240000ULL,   \
+    0x3fefe01ff726fa1aULL, 0x3f6feff384900000ULL, 0x3fefa11cc261ea74ULL, 0x3f87dc41353d0000ULL,   \
+    0x3fef6310b081992eULL, 0x3f93cea3c4c28000ULL, 0x3fef25f63ceeadcdULL, 0x3f9b9fc114890000ULL,   \
+    0x3feee9c8039113e7ULL, 0x3fa1b0d8ce110000ULL, 0x3feeae8078cbb1abULL, 0x3fa58a5bd001c000ULL,   \
+    0x3fee741aa29d0c9bULL, 0x3fa95c8340d88000ULL, 0x3fee3a91830a99b5ULL, 0x3fad276aef578000ULL,   \
+    0x3fee01e009609a56ULL, 0x3fb07598e598c000ULL, 0x3fedca01e577bb98ULL, 0x3fb253f5e30d2000ULL,   \
+    0x3fed92f20b7c9103ULL, 0x3fb42edd8b380000ULL, 0x3fed5cac66fb5cceULL, 0x3fb606598757c000ULL,   \
+    0x3fed272caa5ede9dULL, 0x3fb7da76356a0000ULL, 0x3fecf26e3e6b2ccdULL, 0x3fb9ab434e1c6000ULL,   \
+    0x3fecbe6da2a77902ULL, 0x3fbb78c7bb0d6000ULL, 0x3fec8b266d37086dULL, 0x3fbd431332e72000ULL,   \
+    0x3fec5894bd5d5804ULL, 0x3fbf0a3171de6000ULL, 0x3fec26b533bb9f8cULL, 0x3fc067152b914000ULL,   \
+    0x3febf583eeece73fULL, 0x3fc147858292b000ULL, 0x3febc4fd75db96c1ULL, 0x3fc2266ecdca3000ULL,   \
+    0x3feb951e0c864a28ULL, 0x3fc303d7a6c55000ULL, 0x3feb65e2c5ef3e2cULL, 0x3fc3dfc33c331000ULL,   \
+    0x3feb374867c9888bULL, 0x3fc4ba366b7a8000ULL, 0x3feb094b211d304aULL, 0x3fc5933928d1f000ULL,   \
+    0x3feadbe885f2ef7eULL, 0x3fc66acd2418f000ULL, 0x3feaaf1d31603da2ULL, 0x3fc740f8ec669000ULL,   \
+    0x3fea82e63fd358a7ULL, 0x3fc815c0f51af000ULL, 0x3fea5740ef09738bULL, 0x3fc8e92954f68000ULL,   \
+    0x3fea2c2a90ab4b27ULL, 0x3fc9bb3602f84000ULL, 0x3fea01a01393f2d1ULL, 0x3fca8bed1c2c0000ULL,   \
+    0x3fe9d79f24db3c1bULL, 0x3fcb5b515c01d000ULL, 0x3fe9ae2505c7b190ULL, 0x3fcc2967ccbcc000ULL,   \
+    0x3fe9852ef297ce2fULL, 0x3fccf635d5486000ULL, 0x3fe95cbaeea44b75ULL, 0x3fcdc1bd3446c000ULL,   \
+    0x3fe934c69de74838ULL, 0x3fce8c01b8cfe000ULL, 0x3fe90d4f2f6752e6ULL, 0x3fcf5509c0179000ULL,   \
+    0x3fe8e6528effd79dULL, 0x3fd00e6c121fb800ULL, 0x3fe8bfce9fcc007cULL, 0x3fd071b80e93d000ULL,   \
+    0x3fe899c0dabec30eULL, 0x3fd0d46b9e867000ULL, 0x3fe87427aa2317fbULL, 0x3fd13687334bd000ULL,   \
+    0x3fe84f00acb39a08ULL, 0x3fd1980d67234800ULL, 0x3fe82a49e8653e55ULL, 0x3fd1f8ffe0cc8000ULL,   \
+    0x3fe8060195f40260ULL, 0x3fd2595fd7636800ULL, 0x3fe7e22563e0a329ULL, 0x3fd2b9300914a800ULL,   \
+    0x3fe7beb377dcb5adULL, 0x3fd3187210436000ULL, 0x3fe79baa679725c2ULL, 0x3fd377266dec1800ULL,   \
+    0x3fe77907f2170657ULL, 0x3fd3d54ffbaf3000ULL, 0x3fe756cadbd6130cULL, 0x3fd432eee32fe000ULL
+__device__ __constant__ unsigned long long jd_log_tab[256] = {JD_LOG_TAB};
+static const unsigned long long jd_log_tab_host[256] = {JD_LOG_TAB};     // jd_debug_log1pe / jd_debug_log_add (device = -1)
+
+__host__ __device__ __forceinline__ double jd_u2d(unsigned long long u) { double d; memcpy(&d, &u, sizeof d); return d; }
+__host__ __device__ __forceinline__ unsigned long long jd_d2u(double d) { unsigned long long u; memcpy(&u, &d, sizeof u); return u; }
+
+__host__ __device__ inline double jd_log_libm_impl(double x, const unsigned long long *tab)
 {
-    if (x < y) { float t = x; x = y; y = t; }
-    float diff = y - x;
-    if (diff < -18.42) return x;
-    return (float)((double)x + log(1.0 + (double)jd_expf(diff)));
+    const unsigned long long ix = jd_d2u(x);
+    if (ix - 0x3fee000000000000ULL < 0x3ff1090000000000ULL - 0x3fee000000000000ULL) {   // [1 - 2^-4, 1 + 0x1.09p-4): poly1
+        if (ix == 0x3ff0000000000000ULL) return 0.0;
+        const double r = x - 1.0, r2 = r * r, r3 = r * r2;
+        double p = __builtin_fma(r, -0x1.ffffffffffdcbp-3, 0x1.5555555555577p-2);
+        p = __builtin_fma(r2, 0x1.999999995dd0cp-3, p);
+        double q = __builtin_fma(r, 0x1.24924a344de30p-3, -0x1.55555556745a7p-3);
+        q = __builtin_fma(r2, -0x1.fffffa4423d65p-4, q);
+        double s = __builtin_fma(r, -0x1.999eb43b068ffp-4, 0x1.c7184282ad6cap-4);
+        s = __builtin_fma(r2, 0x1.78182f7afd085p-4, s);
+        s = __builtin_fma(r3, -0x1.5521375d145cdp-4, s);
+        s = __builtin_fma(s, r3, q);
+        s = __builtin_fma(s, r3, p);
+        const double rhi = __builtin_fma(-r, 0x1p27, __builtin_fma(r, 0x1p27, r));     // r + w - w, w = r 2^27
+        const double rlo = r - rhi;
+        const double rr = rhi * rhi;
+        const double hi = __builtin_fma(rr, -0.5, r);
+        double lo = __builtin_fma(rr, -0.5, r - hi);
+        lo = __builtin_fma(rlo * -0.5, r + rhi, lo);
+        return hi + __builtin_fma(s, r3, lo);
+    }
+    // x = 2^k z, z in [0x1.6p-1, 0x1.6p+0); log x = k ln2 + log c + log1p(z / c - 1) for the c of z's subinterval
+    const unsigned long long tmp = ix - 0x3fe6000000000000ULL;
+    const int i = (int)((tmp >> 45) & 127);
+    const double kd = (double)((long long)tmp >> 52);
+    const double z = jd_u2d(ix - (tmp & (0xfffULL << 52)));
+    const double invc = jd_u2d(tab[2 * i]), logc = jd_u2d(tab[2 * i + 1]);
+    const double r = __builtin_fma(z, invc, -1.0);
+    const double w = __builtin_fma(kd, 0x1.62e42fefa3800p-1, logc);                   // ln2hi
+    const double hi = w + r;
+    const double lo = __builtin_fma(kd, 0x1.ef35793c76730p-45, (w - hi) + r);         // ln2lo
+    const double r2 = r * r;
+    const double p = __builtin_fma(__builtin_fma(r, -0x1.55575e506c89fp-3, 0x1.999b324f10111p-3), r2,
+                                   __builtin_fma(r, -0x1.fffffffeb4590p-3, 0x1.555555551305bp-2));
+    return __builtin_fma(r * r2, p, __builtin_fma(r2, -0x1.0000000000001p-1, lo)) + hi;
+}
+
+// The fast value of log(1 + e), e in (0, 1], in double: a 129-entry table (c = 1 + k/128, invc = fl(1/c), logc = -log(invc),
+// jd_fill_logtab) and log(y) = logc + log1p(y invc - 1) by a degree-7 polynomial.  Within 2 doubles of the libm's value for
+// every float d in [-18.42, 0] (tests/test_logadd.py) but not equal to it: 39 M of those d differ by 1 or 2 ulp, and under
+// cancellation (a logAdd result near 0) such a difference reaches the float.  jd_log_add_gate decides when it can.
+struct JdLogTab { double invc, logc; };
+static inline void jd_fill_logtab(JdLogTab *t)
+{
+    for (int k = 0; k <= 128; ++k) {
+        const double c = 1.0 + k / 128.0;
+        t[k].invc = (k == 0) ? 1.0 : 1.0 / c;
+        t[k].logc = (k == 0) ? 0.0 : (double)(-logl((long double)t[k].invc));   // the identity holds for the ROUNDED invc
+    }
+}
+__host__ __device__ __forceinline__ double jd_log1pe_table(double e, const JdLogTab *tab)
+{
+    const JdLogTab t = tab[(int)(e * 128.0 + 0.5)];
+    const double r = __builtin_fma(1.0 + e, t.invc, -1.0);
+    double q = 1.0 / 7.0;
+    q = __builtin_fma(q, r, -1.0 / 6.0);
+    q = __builtin_fma(q, r, 1.0 / 5.0);
+    q = __builtin_fma(q, r, -1.0 / 4.0);
+    q = __builtin_fma(q, r, 1.0 / 3.0);
+    q = __builtin_fma(q, r, -1.0 / 2.0);
+    q = __builtin_fma(q, r, 1.0);
+    return t.logc + q * r;
+}
+
+// HTKFlatModels::logAdd (HTKFlatModels.cpp:266-293): a < c ? swap; d = y - x; d < -18.42 ? x : (float)(x + log(1.0 + expf(d))),
+// log in double, as the host libm computes it.  Split in two so that jd_log_add2x2 can run two of them side by side:
+//   gate    the table value m; rounding is monotone, so when x + (m - 2 ulp) and x + (m + 2 ulp) round to the same float the
+//           libm's value, which lies between them, rounds to it too.  Returns whether they do not (the result is open).
+//   settle  the cut and NaN (a NaN operand makes d NaN: expf and log propagate it in the reference).
+// An open result takes jd_log_libm_impl (rare: the float result must lie within ~2 double ulps of a rounding boundary).
+__host__ __device__ __forceinline__ bool jd_log_add_gate(float a, float c, const JdLogTab *tab, const unsigned long long *etab,
+                                                         float &x, float &d, double &y, float &n)
+{
+    const bool s = a < c;
+    x = s ? c : a;
+    d = (s ? a : c) - x;
+    // (the clamp keeps the table index in range for the steps whose result is discarded)
+    const double e = (double)jd_expf_impl(fmaxf(d, -19.0f), etab);
+    y = 1.0 + e;
+    const unsigned long long m = jd_d2u(jd_log1pe_table(e, tab));                  // > 0
+    n = (float)((double)x + jd_u2d(m - 2));
+    return d >= -18.42 && n != (float)((double)x + jd_u2d(m + 2));
+}
+__host__ __device__ __forceinline__ float jd_log_add_settle(float x, float d, float n)
+{
+    return d < -18.42 ? x : (d != d ? d : n);                                       // HTKFlatModels.cpp:276 (double compare)
+}
+__host__ __device__ __forceinline__ float jd_log_add_impl(float a, float c, const JdLogTab *tab, const unsigned long long *etab,
+                                                          const unsigned long long *ltab)
+{
+    float x, d, n;
+    double y;
+    if (jd_log_add_gate(a, c, tab, etab, x, d, y, n)) n = (float)((double)x + jd_log_libm_impl(y, ltab));
+    return jd_log_add_settle(x, d, n);
+}
+// the generic kernel's (tab: the table of jd_fill_logtab in device memory)
+__device__ __forceinline__ float jd_log_add(float a, float c, const JdLogTab *tab)
+{
+    return jd_log_add_impl(a, c, tab, jd_exp2f_tab, jd_log_tab);
 }
 
 // ------------------------------------------------------------------- GMM kernel
@@ -66,7 +236,8 @@ __global__ __launch_bounds__(256) void jd_gmm_kernel(const float *__restrict__ f
                                                      const float *__restrict__ par,
                                                      const float *__restrict__ det,
                                                      const int *__restrict__ n_mix, int G, int M, int D,
-                                                     float *__restrict__ ll, int skip_unused)
+                                                     float *__restrict__ ll, int skip_unused,
+                                                     const JdLogTab *__restrict__ logtab)
 {
     constexpr int DP = (DT > 0) ? (DT | 1) : 0;      // odd row stride: conflict-free per-lane rows
     extern __shared__ __align__(16) char smem[];
@@ -130,7 +301,7 @@ __global__ __launch_bounds__(256) void jd_gmm_kernel(const float *__restrict__ f
                     }
                 }
                 float comp = (float)(-0.5 * (double)sum + (double)dg[m]);   // :254
-                acc = jd_log_add(acc, comp);
+                acc = jd_log_add(acc, comp, logtab);
             }
         }
         so[lane * (GMM_GT + 1) + gl] = acc;
@@ -154,38 +325,47 @@ __global__ __launch_bounds__(256) void jd_gmm_kernel(const float *__restrict__ f
 // v_pk_mul_f32: two IEEE fp32 operations, no contraction - the same roundings as the reference's
 // scalar code, HTKFlatModels.cpp:249-250) with the tied state's (mean, ivar) pairs arriving
 // through the scalar cache.  logAdd (HTKFlatModels.cpp:266-293) evaluates log(1.0 + e), e in
-// (0, 1], in double with a 128-interval table (c = 1 + k/128; log y = -log(invc) + log1p(y invc - 1),
-// degree-7 polynomial: < 1 ulp in double, like the libm the reference links).
+// (0, 1], in double as the libm the reference links does: a table value, and where its last bits could
+// move the float result the replica of glibc's log (jd_log_add_gate / jd_log_libm_impl above).
 #define GMM_ROWS2 128
 typedef float jd_f2 __attribute__((ext_vector_type(2)));
-struct JdLogTab { double invc, logc; };
-
-// One logAdd step for the two frames of a lane, straight-line (no branch: some lane of a wave always
-// takes the long path) and written pairwise so that the two dependent chains interleave.  etab is
-// the LDS copy of jd_exp2f_tab, tab the LDS copy of the log table.
-__device__ __forceinline__ void jd_log_add2x2(float &a0, float &a1, float c0, float c1, const JdLogTab *tab,
-                                              const unsigned long long *etab)
+// One logAdd step for the two frames of a lane, straight-line (no branch: some lane of a wave always takes the long path) and
+// written pairwise so that the two dependent chains interleave.  etab is the LDS copy of jd_exp2f_tab, tab the LDS copy of
+// the log table.  A result the table value leaves open (jd_log_add_gate) is NOT settled here: it becomes NaN, which every
+// later step of the chain passes on, and jd_gmm_kernel39 scores a cell that ends NaN again with jd_log_add_impl once the
+// tile's chains are done (its replica of the libm's log needs registers the distance loop holds).
+__host__ __device__ __forceinline__ void jd_log_add2x2(float &a0, float &a1, float c0, float c1, const JdLogTab *tab,
+                                                       const unsigned long long *etab)
 {
-    const bool s0 = a0 < c0, s1 = a1 < c1;
-    const float x0 = s0 ? c0 : a0, y0 = s0 ? a0 : c0;
-    const float x1 = s1 ? c1 : a1, y1 = s1 ? a1 : c1;
-    const float d0 = y0 - x0, d1 = y1 - x1;
-    const bool keep0 = d0 < -18.42, keep1 = d1 < -18.42;               // HTKFlatModels.cpp:276 (double compare)
-    // (the clamp keeps the table index in range for the lanes whose result is discarded)
-    const double e0 = (double)jd_expf_impl(fmaxf(d0, -19.0f), etab), e1 = (double)jd_expf_impl(fmaxf(d1, -19.0f), etab);
-    const double yy0 = 1.0 + e0, yy1 = 1.0 + e1;
-    const JdLogTab t0 = tab[(int)(e0 * 128.0 + 0.5)], t1 = tab[(int)(e1 * 128.0 + 0.5)];
-    const double r0 = __builtin_fma(yy0, t0.invc, -1.0), r1 = __builtin_fma(yy1, t1.invc, -1.0);
-    double q0 = 1.0 / 7.0, q1 = 1.0 / 7.0;
-    q0 = __builtin_fma(q0, r0, -1.0 / 6.0); q1 = __builtin_fma(q1, r1, -1.0 / 6.0);
-    q0 = __builtin_fma(q0, r0, 1.0 / 5.0);  q1 = __builtin_fma(q1, r1, 1.0 / 5.0);
-    q0 = __builtin_fma(q0, r0, -1.0 / 4.0); q1 = __builtin_fma(q1, r1, -1.0 / 4.0);
-    q0 = __builtin_fma(q0, r0, 1.0 / 3.0);  q1 = __builtin_fma(q1, r1, 1.0 / 3.0);
-    q0 = __builtin_fma(q0, r0, -1.0 / 2.0); q1 = __builtin_fma(q1, r1, -1.0 / 2.0);
-    q0 = __builtin_fma(q0, r0, 1.0);        q1 = __builtin_fma(q1, r1, 1.0);
-    const float n0 = (float)((double)x0 + (t0.logc + q0 * r0)), n1 = (float)((double)x1 + (t1.logc + q1 * r1));
-    a0 = keep0 ? x0 : n0;
-    a1 = keep1 ? x1 : n1;
+    float x0, x1, d0, d1, n0, n1;
+    double y0, y1;
+    const bool o0 = jd_log_add_gate(a0, c0, tab, etab, x0, d0, y0, n0);
+    const bool o1 = jd_log_add_gate(a1, c1, tab, etab, x1, d1, y1, n1);
+    a0 = o0 ? __builtin_nanf("") : jd_log_add_settle(x0, d0, n0);
+    a1 = o1 ? __builtin_nanf("") : jd_log_add_settle(x1, d1, n1);
+}
+
+// The cell (row r, tied state g) of jd_gmm_kernel39 again, one frame per lane with the exact logAdd throughout: the distance
+// in the kernel's order and roundings (scalar IEEE operations equal the packed ones), features from memory (the tile's LDS
+// copy is the output tile by then).
+__device__ __noinline__ float jd_gmm_cell39(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows, int r,
+                                            const float *__restrict__ pg, const float *__restrict__ dg, int nm,
+                                            const JdLogTab *tab, const unsigned long long *etab)
+{
+    const int src = (r < n_rows) ? row_src[r] : -1;
+    float acc = LZ;
+    for (int m = 0; m < nm; ++m) {
+        const float *pm = pg + (size_t)m * 39 * 2;
+        float sum = 0.0f;
+        for (int j = 0; j < 39; ++j) {
+            const float u = ((src >= 0) ? feats[(size_t)src * 39 + j] : 0.0f) - pm[2 * j];
+            const float z = u * u * pm[2 * j + 1];
+            sum = (j == 0) ? z : sum + z;
+        }
+        const float c = (float)(-0.5 * (double)sum + (double)dg[m]);
+        acc = (m == 0) ? (c <= LZ ? LZ : c) : jd_log_add_impl(acc, c, tab, etab, jd_log_tab);
+    }
+    return acc;
 }
 
 template <int GT>
@@ -230,6 +410,8 @@ __global__ __launch_bounds__(256, 4) void jd_gmm_kernel39(const float *__restric
         for (int j = 0; j < DT; ++j) { x[j].x = sx[lane * DP + j]; x[j].y = sx[(lane + 64) * DP + j]; }
         __syncthreads();                              // sx is re-used as the output tile
         constexpr int GPW = GT / 4;               // tied states per wave
+        static_assert(GPW <= 16, "one bit per (state, frame) of a lane in open_cells");
+        unsigned open_cells = 0;                  // bit gi: frame 0's cell of state gi is NaN (an open step, or NaN), bit 16 + gi: frame 1's
         for (int gi = 0; gi < GPW; ++gi) {
             const int gl = wid * GPW + gi;            // wave-uniform
             const int g = g0 + gl;
@@ -256,14 +438,23 @@ __global__ __launch_bounds__(256, 4) void jd_gmm_kernel39(const float *__restric
                     }
                     const double dm = (double)dg[m];
                     const float c0 = (float)(-0.5 * (double)sum.x + dm), c1 = (float)(-0.5 * (double)sum.y + dm);   // :254
-                    // logAdd(LOG_ZERO, c) is c for every c > LOG_ZERO and LOG_ZERO else (the difference is below -18.42,
-                    // or the sum rounds back): the first mixture needs no exponential and no logarithm
-                    if (m == 0) { acc0 = LZ < c0 ? c0 : LZ; acc1 = LZ < c1 ? c1 : LZ; }
+                    // logAdd(LOG_ZERO, c) is c for every c > LOG_ZERO, NaN for a NaN c and LOG_ZERO else (the difference is below
+                    // -18.42, or the sum rounds back): the first mixture needs no exponential and no logarithm
+                    if (m == 0) { acc0 = c0 <= LZ ? LZ : c0; acc1 = c1 <= LZ ? LZ : c1; }
                     else jd_log_add2x2(acc0, acc1, c0, c1, stab, setab);
                 }
             }
             so[lane * (GT + 1) + gl] = acc0;
             so[(lane + 64) * (GT + 1) + gl] = acc1;
+            open_cells |= (acc0 != acc0 ? 1u << gi : 0u) | (acc1 != acc1 ? 1u << (16 + gi) : 0u);
+        }
+        // the NaN cells again with the exact logAdd (their lanes' own entries of the output tile): the chains that met an open step
+        // get their value, the NaN ones (a NaN feature or parameter) stay NaN
+        for (unsigned o = open_cells; o; o &= o - 1) {
+            const int b = __builtin_ctz(o), gl = wid * GPW + (b & 15), fr = b >> 4;
+            const int g = g0 + gl;
+            so[(lane + 64 * fr) * (GT + 1) + gl] = jd_gmm_cell39(feats, row_src, n_rows, r0 + lane + 64 * fr, par + (size_t)g * M * DT * 2,
+                                                                det + (size_t)g * M, n_mix[g], stab, setab);
         }
         __syncthreads();
         for (int e = tid; e < GMM_ROWS2 * GT; e += 256) {

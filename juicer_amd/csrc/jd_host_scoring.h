@@ -38,14 +38,9 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
     HIPCHK(hipMemcpy(b.par, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b.det, a->det.data(), gm * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b.n_mix, a->n_mix.data(), (size_t)a->n_gmm * sizeof(int), hipMemcpyHostToDevice));
-    {   // table of jd_log_add2: c_k = 1 + k/128, invc = fl(1/c_k), logc = -log(invc) (so that the identity
-        // log y = logc + log1p(y invc - 1) holds for the ROUNDED invc)
+    {   // the table of jd_log1pe_table (both exact kernels)
         std::vector<JdLogTab> t(129);
-        for (int k = 0; k <= 128; ++k) {
-            const double c = 1.0 + k / 128.0;
-            t[(size_t)k].invc = (k == 0) ? 1.0 : 1.0 / c;
-            t[(size_t)k].logc = (k == 0) ? 0.0 : (double)(-logl((long double)t[(size_t)k].invc));
-        }
+        jd_fill_logtab(t.data());
         HIPCHK(hipMalloc(&b.logtab, t.size() * sizeof(JdLogTab)));
         HIPCHK(hipMemcpy(b.logtab, t.data(), t.size() * sizeof(JdLogTab), hipMemcpyHostToDevice));
     }
@@ -131,7 +126,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
         const int dp = a->D | 1;
         const size_t sm = (size_t)(GMM_ROWS * dp + GMM_ROWS * (GMM_GT + 1)) * sizeof(float);
         hipLaunchKernelGGL(jd_gmm_kernel<0>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
-                           b.n_mix, a->n_gmm, a->max_mix, a->D, d_ll, skip_unused);
+                           b.n_mix, a->n_gmm, a->max_mix, a->D, d_ll, skip_unused, b.logtab);
     }
     HIPCHK(hipGetLastError());
     return JD_OK;

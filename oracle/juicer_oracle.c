@@ -299,6 +299,49 @@ int jo_am_create_htk(jo_am **out, int32_t D, int32_t n_gmm, int32_t max_mix,
 }
 
 /* HTKModels::Load(phonesListFName, priorsFName, statesPerModel), HTKModels.cpp:74-218 (hybrid ANN / HMM) */
+/* Models from the prepared arrays (fDets, fMeans, fVars = inverse variances) as they are, the counterpart of jd_am_create_flat:
+ * lets a test choose every component value exactly (frame = mean gives det).  The topology arguments, transition
+ * probabilities included, as jo_am_create_htk's. */
+int jo_am_create_flat(jo_am **out, int32_t D, int32_t n_gmm, int32_t max_mix, const int32_t *n_mix,
+                      const float *det, const float *mean, const float *ivar,
+                      int32_t n_hmm, int32_t max_n, const int32_t *hmm_nstates,
+                      const int32_t *hmm_gmm, const int32_t *hmm_tm,
+                      int32_t n_tm, const int32_t *tm_nstates, const float *transp)
+{
+    if (!out || !n_mix || !det || !mean || !ivar) return fail(-1, "jo_am_create_flat: bad argument");
+    if (D <= 0 || n_gmm <= 0 || max_mix <= 0) return fail(-1, "jo_am_create_flat: bad sizes");
+    const size_t gm = (size_t)n_gmm * max_mix;
+    /* the topology through jo_am_create_htk (one unit-weight, unit-variance mixture per state), then the Gaussians replaced */
+    int32_t *nm1 = (int32_t *)malloc(sizeof(int32_t) * n_gmm);
+    float *w1 = (float *)malloc(sizeof(float) * n_gmm), *m1 = (float *)calloc((size_t)n_gmm * D, sizeof(float));
+    float *v1 = (float *)malloc(sizeof(float) * (size_t)n_gmm * D);
+    for (int32_t g = 0; g < n_gmm; ++g) { nm1[g] = 1; w1[g] = 1.0f; }
+    for (size_t k = 0; k < (size_t)n_gmm * D; ++k) v1[k] = 1.0f;
+    jo_am *a = NULL;
+    int rc = jo_am_create_htk(&a, D, n_gmm, 1, nm1, w1, m1, v1, n_hmm, max_n, hmm_nstates, hmm_gmm, hmm_tm, n_tm, tm_nstates, transp);
+    free(nm1); free(w1); free(m1); free(v1);
+    if (rc) return rc;
+    a->max_mix = max_mix;
+    a->det = (float *)realloc(a->det, sizeof(float) * gm);
+    a->mean = (float *)realloc(a->mean, sizeof(float) * gm * D);
+    a->ivar = (float *)realloc(a->ivar, sizeof(float) * gm * D);
+    for (int32_t g = 0; g < n_gmm; ++g) {
+        if (n_mix[g] < 1 || n_mix[g] > max_mix) { jo_am_destroy(a); return fail(-1, "n_mix[%d] out of range", g); }
+        a->n_mix[g] = n_mix[g];
+        for (int32_t m = 0; m < max_mix; ++m) {
+            const size_t gi = (size_t)g * max_mix + m;
+            const int pad = m >= n_mix[g];
+            a->det[gi] = pad ? LZ : det[gi];
+            for (int32_t k = 0; k < D; ++k) {
+                a->mean[gi * D + k] = pad ? 0.0f : mean[gi * D + k];
+                a->ivar[gi * D + k] = pad ? 0.0f : ivar[gi * D + k];
+            }
+        }
+    }
+    *out = a;
+    return 0;
+}
+
 int jo_am_create_hybrid(jo_am **out, int32_t n_phones, const float *priors, int32_t states_per_model)
 {
     if (!out || !priors || n_phones <= 0) return fail(-1, "jo_am_create_hybrid: bad argument");
@@ -1256,5 +1299,20 @@ int jo_expf_array(const float *x, int64_t n, float *out)
 {
     if (!x || !out || n < 0) return -1;
     for (int64_t i = 0; i < n; ++i) out[i] = expf(x[i]);
+    return 0;
+}
+
+/* HTKFlatModels::logAdd elementwise, and its double log(1.0 + (double)expf(d)) (:266-293) - what the kernels' logAdd is held to */
+int jo_log_add_array(const float *x, const float *y, int64_t n, float *out)
+{
+    if (!x || !y || !out || n < 0) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = log_add(x[i], y[i]);
+    return 0;
+}
+
+int jo_log1pe_array(const float *d, int64_t n, double *out)
+{
+    if (!d || !out || n < 0) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = log(1.0 + (double)expf(d[i]));
     return 0;
 }

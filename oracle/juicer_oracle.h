@@ -65,6 +65,13 @@ int jo_am_create_htk(jo_am **out, int32_t D, int32_t n_gmm, int32_t max_mix,
                      int32_t n_hmm, int32_t max_n, const int32_t *hmm_nstates,
                      const int32_t *hmm_gmm, const int32_t *hmm_tm,
                      int32_t n_tm, const int32_t *tm_nstates, const float *transp);
+/* from the prepared arrays (det, mean, inverse variances [n_gmm][max_mix]([D])), the counterpart of jd_am_create_flat;
+ * topology and transp (probabilities) as jo_am_create_htk's */
+int jo_am_create_flat(jo_am **out, int32_t D, int32_t n_gmm, int32_t max_mix, const int32_t *n_mix,
+                      const float *det, const float *mean, const float *ivar,
+                      int32_t n_hmm, int32_t max_n, const int32_t *hmm_nstates,
+                      const int32_t *hmm_gmm, const int32_t *hmm_tm,
+                      int32_t n_tm, const int32_t *tm_nstates, const float *transp);
 int jo_am_get_flat(const jo_am *a, float *det, float *mean, float *ivar);
 int jo_am_get_trans(const jo_am *a, float *trP, int16_t *se, float *tee);
 /* HTKFlatModels::calcGMMOutput for every tied state of every frame, no cache */
@@ -115,6 +122,9 @@ int jo_dec_set_tie_mode(jo_dec *d, int mode);
 
 /* host libm expf, elementwise */
 int jo_expf_array(const float *x, int64_t n, float *out);
+/* HTKFlatModels::logAdd elementwise, and the double log(1.0 + (double)expf(d)) inside it */
+int jo_log_add_array(const float *x, const float *y, int64_t n, float *out);
+int jo_log1pe_array(const float *d, int64_t n, double *out);
 
 const char *jo_last_error(void);
 

@@ -162,6 +162,26 @@ class OracleAM:
         _check(lib().jo_am_create_hybrid(C.byref(self.h), C.c_int32(P), _p(pr, C.c_float), C.c_int32(states_per_model)))
         return self
 
+    @classmethod
+    def from_flat(cls, det, mean, ivar, n_mix):
+        """the prepared arrays as they are (jo_am_create_flat), one 3-state HMM on tied state 0: capi.Models.from_flat's twin"""
+        self = cls.__new__(cls)
+        det, mean, ivar, nm = _f32(det), _f32(mean), _f32(ivar), _i32(n_mix)
+        G, M, D = mean.shape
+        assert det.shape == (G, M) and ivar.shape == mean.shape and nm.shape == (G,)
+        self.h = C.c_void_p()
+        self.D, self.n_gmm, self.max_mix = D, G, M
+        self.n_hmm, self.max_n, self.n_tm = 1, 3, 1
+        hn, hg, ht, tn = _i32([3]), _i32([-1, 0, -1]), _i32([0]), _i32([3])
+        tp = np.zeros((1, 3, 3), np.float32)
+        tp[0, 0, 1] = 1.0
+        tp[0, 1, 1] = tp[0, 1, 2] = 0.5
+        _check(lib().jo_am_create_flat(C.byref(self.h), C.c_int32(D), C.c_int32(G), C.c_int32(M), _p(nm, C.c_int32),
+                                       _p(det, C.c_float), _p(mean, C.c_float), _p(ivar, C.c_float), C.c_int32(1), C.c_int32(3),
+                                       _p(hn, C.c_int32), _p(hg, C.c_int32), _p(ht, C.c_int32), C.c_int32(1), _p(tn, C.c_int32),
+                                       _p(tp, C.c_float)))
+        return self
+
     def flat(self):
         det = np.zeros((self.n_gmm, self.max_mix), np.float32)
         mean = np.zeros((self.n_gmm, self.max_mix, self.D), np.float32)
@@ -186,6 +206,22 @@ class OracleAM:
         if getattr(self, "h", None) and _lib is not None:
             _lib.jo_am_destroy(self.h)
             self.h = None
+
+
+def log_add_array(x, y):
+    """HTKFlatModels::logAdd (:266-293) elementwise, on the host libm"""
+    x, y = _f32(x), _f32(y)
+    out = np.empty_like(x)
+    _check(lib().jo_log_add_array(_p(x, C.c_float), _p(y, C.c_float), C.c_int64(x.shape[0]), _p(out, C.c_float)))
+    return out
+
+
+def log1pe_array(d):
+    """log(1.0 + (double)expf(d)) in double, on the host libm: the value inside logAdd"""
+    d = _f32(d)
+    out = np.empty(d.shape[0], np.float64)
+    _check(lib().jo_log1pe_array(_p(d, C.c_float), C.c_int64(d.shape[0]), _p(out, C.c_double)))
+    return out
 
 
 class OracleDecoder:
