@@ -547,6 +547,42 @@ int jd_dec_set_pipeline(jd_dec *d, int32_t mode, int32_t depth, int32_t slots);
 int jd_dec_set_scoring(jd_dec *d, int32_t mode);
 int jd_am_score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, float *out);
 
+/* Model-level output (IDecoder::modelLevelOutput; basicCore's WFSTDecoder::extendModelEndState): besides the words, which HMM
+ * (model) the best path passed and in which frames.
+ *   JD_OUTPUT_WORDS                      the default: jd_hyp, the 1-best word chain
+ *   JD_OUTPUT_WORDS | JD_OUTPUT_MODELS   the same jd_hyp - bit for bit what word output gives, the search is the same - and a
+ *                                        jd_model_hyp beside it (jd_dec_model_result)
+ * A jd_model_hyp entry per arc with an in-label (a model) the best path traversed, tee models included (zero frames), and per
+ * epsilon-input arc with a word label (model 0); newest first, like jd_hyp:
+ *   model  in-label = HMM index + 1 (0: a word label on an epsilon-input arc)
+ *   label  word id + 1 when the same arc carries a word label, else 0
+ *   time   the frame the token left the model (a word's end frame in jd_hyp); a segment starts at the next entry's time
+ *          (frame 0 for the oldest)
+ *   score / ac / lm  the token's there; entry 0 and the totals with the final state's weight, as in jd_hyp.
+ * The search kernels write a Path record for every model the best paths pass: more records, more collections on heavy graphs.
+ * Set between utterances: refused (JD_ESTATE) while a stream has frames pushed since its jd_stream_init and no jd_stream_finish
+ * yet.  The result arrays of model-level output are allocated when it is first switched on.  Not with partial traces (jd_dec_set_partial_interval > 0; jd_stream_partial with trace_now works and
+ * gives words), not under a broker (jd_broker_create refuses such a decoder; set it before creating one), and jd_multi_* decode
+ * words only.  jd_dec_model_result: result i of the decoder's last jd_stream_finish (i = the stream) or jd_decode_batch /
+ * jd_decode_batch_device (i = the utterance); valid until the next decode, finish or jd_dec_set_output_level.  n = -1: no result
+ * (as in jd_hyp); n is capped by the result capacity (8192 entries), a longer chain fails the decode with JD_ENOMEM.
+ */
+#define JD_OUTPUT_WORDS  1
+#define JD_OUTPUT_MODELS 2
+typedef struct jd_model_hyp {
+    int32_t  n;
+    const int32_t *model;
+    const int32_t *label;
+    const int32_t *time;
+    const float   *score;
+    const float   *ac;
+    const float   *lm;
+    float tot_score, tot_ac, tot_lm;
+} jd_model_hyp;
+int jd_dec_set_output_level(jd_dec *d, int32_t level);
+int jd_dec_get_output_level(const jd_dec *d, int32_t *level);
+int jd_dec_model_result(jd_dec *d, int32_t i, jd_model_hyp *out);
+
 /* What JD_FLOW_RESIDENT has done so far (cumulative over the decoder's life; a bench reads it on either side of its
  * timed region: frames_searched is what the slots really advanced in between, whatever was announced or handed back). */
 typedef struct jd_pipe_stats {

@@ -56,6 +56,14 @@ class Timing(C.Structure):
 
 FLOW_SERIAL, FLOW_TWO_IN_FLIGHT, FLOW_RESIDENT = 0, 1, 3      # jd_dec_set_pipeline
 SCORE_EXACT, SCORE_FAST = 0, 1                                # jd_dec_set_scoring
+OUTPUT_WORDS, OUTPUT_MODELS = 1, 2                            # jd_dec_set_output_level
+
+
+class CModelHyp(C.Structure):
+    _fields_ = [("n", C.c_int32),
+                ("model", C.POINTER(C.c_int32)), ("label", C.POINTER(C.c_int32)), ("time", C.POINTER(C.c_int32)),
+                ("score", C.POINTER(C.c_float)), ("ac", C.POINTER(C.c_float)), ("lm", C.POINTER(C.c_float)),
+                ("tot_score", C.c_float), ("tot_ac", C.c_float), ("tot_lm", C.c_float)]
 
 
 class PipeStats(C.Structure):
@@ -79,6 +87,24 @@ class Hyp:
     tot_ac: float
     tot_lm: float
     stats: dict
+    models: Optional["ModelHyp"] = None      # model-level output (Decoder.set_output_level(OUTPUT_WORDS | OUTPUT_MODELS))
+
+
+@dataclass
+class ModelHyp:
+    """Model-level result (jd_model_hyp), newest first: model = HMM index + 1 (0: a word label on an epsilon-input arc),
+    label = word id + 1 of the same arc (0: none), time = the frame the token left the model; a segment starts at the
+    next entry's time (frame 0 for the oldest)."""
+    n: int
+    model: np.ndarray
+    label: np.ndarray
+    time: np.ndarray
+    score: np.ndarray
+    ac: np.ndarray
+    lm: np.ndarray
+    tot_score: float
+    tot_ac: float
+    tot_lm: float
 
 
 # every symbol include/juicer_amd.h declares
@@ -97,6 +123,7 @@ EXPORTS = [
     "jd_broker_create", "jd_broker_destroy", "jd_broker_open", "jd_broker_close", "jd_broker_init", "jd_broker_push",
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
     "jd_dec_set_scoring", "jd_am_score_frames_mode", "jd_debug_log1pe", "jd_debug_log_add",
+    "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
 ]
 
 _lib = None
@@ -151,6 +178,16 @@ def _hyp_from_c(h: CHyp) -> Hyp:
     return Hyp(n=int(h.n), label=arr(h.label, np.int32), time=arr(h.time, np.int32),
                score=arr(h.score, np.float32), ac=arr(h.ac, np.float32), lm=arr(h.lm, np.float32),
                tot_score=float(h.tot_score), tot_ac=float(h.tot_ac), tot_lm=float(h.tot_lm), stats=st)
+
+
+def _model_hyp_from_c(h: CModelHyp) -> ModelHyp:
+    k = max(int(h.n), 0)
+
+    def arr(ptr, dt):
+        return np.frombuffer(C.string_at(ptr, 4 * k), dtype=dt).copy() if k else np.zeros(0, dtype=dt)
+    return ModelHyp(n=int(h.n), model=arr(h.model, np.int32), label=arr(h.label, np.int32), time=arr(h.time, np.int32),
+                    score=arr(h.score, np.float32), ac=arr(h.ac, np.float32), lm=arr(h.lm, np.float32),
+                    tot_score=float(h.tot_score), tot_ac=float(h.tot_ac), tot_lm=float(h.tot_lm))
 
 
 class Network:
@@ -462,7 +499,29 @@ class Decoder:
     def stream_finish(self, s: int = 0) -> Hyp:
         h = CHyp()
         _check(lib().jd_stream_finish(self.h, C.c_int32(s), C.byref(h)))
-        return _hyp_from_c(h)
+        return self._with_models(_hyp_from_c(h), s, self.output_level() & OUTPUT_MODELS)
+
+    # -- model-level output (jd_dec_set_output_level)
+    def set_output_level(self, level: int):
+        """OUTPUT_WORDS (default) or OUTPUT_WORDS | OUTPUT_MODELS: every result then has .models (a ModelHyp) beside the
+        words, which stay what word output gives.  Between decodes."""
+        _check(lib().jd_dec_set_output_level(self.h, C.c_int32(level)))
+
+    def output_level(self) -> int:
+        v = C.c_int32(0)
+        _check(lib().jd_dec_get_output_level(self.h, C.byref(v)))
+        return v.value
+
+    def model_result(self, i: int) -> ModelHyp:
+        """Result i of the last stream_finish (i = the stream) or decode_batch / decode_batch_device (i = the utterance)."""
+        h = CModelHyp()
+        _check(lib().jd_dec_model_result(self.h, C.c_int32(i), C.byref(h)))
+        return _model_hyp_from_c(h)
+
+    def _with_models(self, hyp: Hyp, i: int, models: int) -> Hyp:
+        if models:
+            hyp.models = self.model_result(i)
+        return hyp
 
     def streams_push(self, streams, frames):
         """jd_stream_push for several streams at once: one scoring launch + one search launch (jd_streams_push)."""
@@ -537,7 +596,8 @@ class Decoder:
         hyps = (CHyp * n)()
         rc = lib().jd_decode_batch(self.h, C.c_int32(n), ptrs, _p(nfr, C.c_int32), hyps)
         _check(rc)
-        return [_hyp_from_c(hyps[i]) for i in range(n)]
+        m = self.output_level() & OUTPUT_MODELS
+        return [self._with_models(_hyp_from_c(hyps[i]), i, m) for i in range(n)]
 
     def decode_batch_device(self, d_feats_ptr: int, offs, hip_stream: int = 0, raw: bool = False):
         """Features already in HBM: d_feats_ptr = device address of [total_frames, D] floats."""
@@ -549,7 +609,8 @@ class Decoder:
         _check(rc)
         if raw:
             return hyps
-        return [_hyp_from_c(hyps[i]) for i in range(n)]
+        m = self.output_level() & OUTPUT_MODELS
+        return [self._with_models(_hyp_from_c(hyps[i]), i, m) for i in range(n)]
 
     def prefetch_scores(self, d_feats_ptr: int, offs, hip_stream: int = 0):
         """Announce the batch the NEXT decode_batch_device call will decode (same arguments): its likelihood table is

@@ -445,6 +445,10 @@ extern "C" int jd_broker_create(jd_broker **out, jd_dec *dec, int32_t n_clients)
     int rc = jd_dec_info(dec, &ms, &D);
     if (rc) return rc;
     if (n_clients > ms) return jd_fail(JD_EINVAL, "jd_broker_create: %d clients on a decoder of %d streams", n_clients, ms);
+    int32_t level = 0;
+    rc = jd_dec_get_output_level(dec, &level);
+    if (rc) return rc;
+    if (level & JD_OUTPUT_MODELS) return jd_fail(JD_EINVAL, "jd_broker_create: a broker serves word output only (the decoder's output level has JD_OUTPUT_MODELS)");
     jd_broker *b = new jd_broker();
     b->dec = dec; b->D = D; b->n_clients = n_clients;
     b->clients.resize((size_t)n_clients);

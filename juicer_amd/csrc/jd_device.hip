@@ -57,7 +57,7 @@
 #define HIST_MAX_BINS 2048
 
 struct __align__(16) Tok { float score, ac, lm; int path; };
-struct __align__(16) PathRec { int prev, frame, label, pad0; float score, ac, lm, pad1; };
+struct __align__(16) PathRec { int prev, frame, label, model; float score, ac, lm, pad1; };   // model: in-label, model-level output only (else 0)
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -194,6 +194,11 @@ extern "C" int jd_release_cached_memory(int32_t device)
 struct HostResult {
     std::vector<int32_t> label, time;
     std::vector<float> score, ac, lm;
+    // model-level output (jd_dec_set_output_level): the whole record chain, newest first (jd_dec_model_result)
+    int32_t m_n = -1;
+    std::vector<int32_t> m_model, m_label, m_time;
+    std::vector<float> m_score, m_ac, m_lm;
+    float m_tot[3] = {0.0f, 0.0f, 0.0f};
 };
 
 // How one wave of utterances is laid out in likelihood tables (plan_wave): frames per chunk, the rows of every chunk
@@ -245,6 +250,8 @@ struct jd_dec {
     int64_t slots_hint = 0;               // jd_dec_set_max_alloc_models
     int res_cap = 8192;
     int *d_res = nullptr;                 // result arena, see ensure_arenas
+    int *d_res_model = nullptr;           // ... the records' models beside it, [stream][res_cap] (model-level output)
+    bool models = false;                  // model-level output (jd_dec_set_output_level): the search kernels' MDL flavour
     int n_cus = 256;
     // search launches: one 512-thread workgroup per CU, a cluster of them per stream
     int max_cw = MAXCW;                   // upper bound of workgroups per stream cluster (JD_CW overrides)
@@ -301,6 +308,7 @@ struct jd_dec {
     // streaming API state
     std::vector<int> stream_T;                 // frames pushed so far
     std::vector<int> stream_started;
+    std::vector<int> stream_open;            // frames pushed since the stream's init, not finished yet (jd_dec_set_output_level)
     // PARTIAL_DECODING (WFSTDecoderLite.h:199-205), streaming API
     int partial_interval = 0;                  // partialTraceInterval
     std::vector<int> last_collect, last_trace; // lastPathCollectFrame, lastPartialTraceFrame
@@ -708,6 +716,7 @@ extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, f
     *d->h_resident = 0;
     d->stream_T.assign((size_t)max_streams, 0);
     d->stream_started.assign((size_t)max_streams, 0);
+    d->stream_open.assign((size_t)max_streams, 0);
     d->lazy_in.assign((size_t)max_streams, 0);
     d->stream_dirty.assign((size_t)max_streams, 0);
     d->last_collect.assign((size_t)max_streams, -1);
@@ -716,6 +725,7 @@ extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, f
     d->partial_label.resize((size_t)max_streams);
     d->partial_time.resize((size_t)max_streams);
     d->results.resize((size_t)max_streams);
+    if (const char *e = jd_dev_env("JD_RES_CAP")) { const int v = atoi(e); if (v >= 16 && v <= (1 << 20)) d->res_cap = v; }   // (tests)
 #undef TRY
     *out = d;
     return JD_OK;
@@ -854,6 +864,10 @@ static int ensure_arenas_try(jd_dec *d, double mem_fraction)
     d->h_streams.assign((size_t)B, StreamDev());
     rc = dmalloc(d, &d->d_res, (size_t)B * 5 * d->res_cap);
     if (rc) return rc;
+    if (d->models) {                                                   // (model-level output only; else jd_dec_set_output_level)
+        rc = dmalloc(d, &d->d_res_model, (size_t)B * d->res_cap);
+        if (rc) return rc;
+    }
     size_t stream_bytes = 0;                                           // (the same for every stream: known after the first sizing pass)
     for (int s = 0; s < B; ++s) {
         StreamDev &S = d->h_streams[(size_t)s];
@@ -940,7 +954,7 @@ static int ensure_arenas(jd_dec *d)
         d->slab = ArenaSlab();
         if (d->h_status) { (void)hipHostFree(d->h_status); d->h_status = nullptr; }
         if (d->d_ll_slab) { (void)hipFree(d->d_ll_slab); d->d_ll_slab = nullptr; d->ll_cap = 0; for (int i = 0; i < 3; ++i) d->d_ll[i] = nullptr; }
-        d->d_res = nullptr; d->d_streams = nullptr; d->d_T = nullptr; d->d_ctl = nullptr; d->d_status = nullptr;
+        d->d_res = nullptr; d->d_res_model = nullptr; d->d_streams = nullptr; d->d_T = nullptr; d->d_ctl = nullptr; d->d_status = nullptr;
         (void)hipGetLastError();
         if (rc != JD_ENOMEM || attempt == 3 || (u_slots > 0 && u_items > 0 && u_paths > 0)) return rc;
         d->cap_slots = u_slots; d->cap_items = u_items; d->cap_paths = u_paths; d->cap_new = 0;
@@ -1009,8 +1023,12 @@ static int report_stream_error(jd_dec *d, int s_i, int error, int frame, int lst
                    "jd_dec_set_capacity", s_i, frame, what, cap, error == JDE_PATHS ? 1 : std::max(lst_nw, 1));
 }
 
+// the model array of the finish kernels: model-level output only
+static int *res_model_of(jd_dec *d) { return d->models ? d->d_res_model : nullptr; }
+
+// resm_v: the virtual slots' model arrays (model-level output; with resn_v)
 static int fetch_results_from(jd_dec *d, const StreamCtl *ctl_v, const int *resn_v, const int *res_v, const int *slot_of, int s0, int n,
-                              jd_hyp *out, int out0, const int *out_idx)
+                              jd_hyp *out, int out0, const int *out_idx, const int *resm_v = nullptr)
 {
     std::vector<StreamDev> hs((size_t)n);
     std::vector<StreamCtl> hc((size_t)n);
@@ -1031,6 +1049,13 @@ static int fetch_results_from(jd_dec *d, const StreamCtl *ctl_v, const int *resn
     if (kmax > 0)                                                      // rows = (stream, array), first kmax words of each
         HIPCHK(hipMemcpy2D(hres.data(), (size_t)kmax * 4, res_base + (size_t)s0 * 5 * d->res_cap, (size_t)d->res_cap * 4,
                            (size_t)kmax * 4, (size_t)n * 5, hipMemcpyDeviceToHost));
+    const int *resm_base = resn_v ? resm_v : d->d_res_model;
+    std::vector<int> hmod;
+    if (d->models && kmax > 0) {
+        hmod.resize((size_t)n * kmax);
+        HIPCHK(hipMemcpy2D(hmod.data(), (size_t)kmax * 4, resm_base + (size_t)s0 * d->res_cap, (size_t)d->res_cap * 4,
+                           (size_t)kmax * 4, (size_t)n, hipMemcpyDeviceToHost));
+    }
     for (int i = 0; i < n; ++i) {
         const StreamDev &S = hs[(size_t)i];
         const StreamCtl &K = hc[(size_t)i];
@@ -1056,9 +1081,37 @@ static int fetch_results_from(jd_dec *d, const StreamCtl *ctl_v, const int *resn
         H.stats.ties = 0;
         int k = S.res_n;
         if (k > d->res_cap) {
-            if (first_err == JD_OK) first_err = jd_fail(JD_ENOMEM, "stream %d: hypothesis has %d words (> %d)", s_i, k, d->res_cap);
+            if (first_err == JD_OK)
+                first_err = d->models ? jd_fail(JD_ENOMEM, "stream %d: the model-level result has %d entries (> %d, the result capacity)", s_i, k, d->res_cap)
+                                      : jd_fail(JD_ENOMEM, "stream %d: hypothesis has %d words (> %d)", s_i, k, d->res_cap);
             k = d->res_cap;
         }
+        if (d->models) {
+            // model-level output: the chain as it is (entry 0 and the totals carry the final-state weight) ...
+            const size_t km = (size_t)std::max(k, 0);
+            const int *row = hres.data() + (size_t)i * 5 * kmax;
+            R.m_n = S.res_n < 0 ? -1 : k;
+            R.m_model.assign(km ? hmod.data() + (size_t)i * kmax : nullptr, km ? hmod.data() + (size_t)i * kmax + km : nullptr);
+            R.m_label.assign(row, row + km); R.m_time.assign(row + kmax, row + kmax + km);
+            R.m_score.assign((const float *)(row + 2 * (size_t)kmax), (const float *)(row + 2 * (size_t)kmax) + km);
+            R.m_ac.assign((const float *)(row + 3 * (size_t)kmax), (const float *)(row + 3 * (size_t)kmax) + km);
+            R.m_lm.assign((const float *)(row + 4 * (size_t)kmax), (const float *)(row + 4 * (size_t)kmax) + km);
+            if (km) { R.m_tot[0] = K.best_final.score; R.m_tot[1] = K.best_final.ac; R.m_tot[2] = K.best_final.lm; }
+            else { R.m_tot[0] = LZ; R.m_tot[1] = LZ; R.m_tot[2] = LZ; }
+            // ... and the word result word mode gives: its labelled entries, the first of them with the final-state weight
+            int w = 0;
+            for (size_t j = 0; j < km; ++j)
+                if (R.m_label[j] != 0) {
+                    int *rw = hres.data() + (size_t)i * 5 * kmax;
+                    for (int a = 0; a < 5; ++a) rw[(size_t)a * kmax + w] = rw[(size_t)a * kmax + j];
+                    ++w;
+                }
+            if (w > 0) {
+                float *rf = (float *)(hres.data() + (size_t)i * 5 * kmax);
+                rf[2 * (size_t)kmax] = K.best_final.score; rf[3 * (size_t)kmax] = K.best_final.ac; rf[4 * (size_t)kmax] = K.best_final.lm;
+            }
+            if (S.res_n >= 0) k = w;
+        } else R.m_n = -1;
         H.n = S.res_n < 0 ? -1 : k;
         const size_t kk = (size_t)std::max(k, 0);
         R.label.resize(kk); R.time.resize(kk); R.score.resize(kk); R.ac.resize(kk); R.lm.resize(kk);
@@ -1509,7 +1562,7 @@ static int decode_wave(jd_dec *d, int nb, const float *d_feats, const int64_t *u
         d->pf_armed = false; d->fg_bank = -1;
         if (rc) { for (int u = 0; u < nb; ++u) d->stream_dirty[(size_t)(s0 + u)] = 1; return rc; }   // (nobody looks at the streams' error words)
     }
-    hipLaunchKernelGGL(jd_finish_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, s0, nb);
+    hipLaunchKernelGGL(jd_finish_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, s0, nb, res_model_of(d));
     HIPCHK(hipGetLastError());
     {   // (a table being scored ahead is waited for by the wave that uses it)
         bool scoring = false;
@@ -1583,7 +1636,7 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
     // (lazily composed) network now - before the first jd_lazy_enter, which starts a new arena generation only when
     // nobody is inside, or a full network would fail this call and, the release below never reached, every later one
     for (int s = 0; s < d->max_streams; ++s) {
-        d->stream_started[(size_t)s] = 0; d->stream_T[(size_t)s] = 0;
+        d->stream_started[(size_t)s] = 0; d->stream_T[(size_t)s] = 0; d->stream_open[(size_t)s] = 0;
         if (d->lazy_in[(size_t)s]) { d->lazy_in[(size_t)s] = 0; jd_lazy_leave(d->net, 1); }
     }
     // Scoring ahead inside the batch: every wave but the last announces the wave behind it, whose table is then scored

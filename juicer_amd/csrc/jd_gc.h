@@ -357,9 +357,12 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     if (tid == 0) { sh_max = -1; sh_bad = 0; sh_cnt = 0; sh_depth = 0; sh_D = 0; out[0] = 0; out[1] = 0; }
     __syncthreads();
     if (!c.started || c.needs_init || c.error != 0 || c.lst_nw <= 0) return;
+    // (model-level output writes records without a word label as well: the trace is of the WORD records - a tip stands for
+    // its newest labelled record, a record for its labelled predecessor.  Word mode has no other records.)
+    auto word_rec = [&](int q) { while (q >= 0 && S.paths[q].label == 0) q = S.paths[q].prev; return q; };
     {
         int mx = -1, bad = 0, cnt = 0;
-        jd_for_each_tip<NE>(C, c, S, [&](int tip) { ++cnt; if (tip < 0) bad = 1; else mx = max(mx, tip); });
+        jd_for_each_tip<NE>(C, c, S, [&](int tip) { ++cnt; tip = word_rec(tip); if (tip < 0) bad = 1; else mx = max(mx, tip); });
         if (mx >= 0) atomicMax(&sh_max, mx);
         if (bad) atomicOr(&sh_bad, 1);
         if (cnt) atomicAdd(&sh_cnt, cnt);
@@ -370,7 +373,7 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     int *ch = S.gc_idx;                                                // the chain of the highest tip, newest first
     if (tid == 0) {
         int n = 0;
-        for (int q = sh_max; q >= 0; q = S.paths[q].prev) ch[n++] = q;
+        for (int q = sh_max; q >= 0; q = word_rec(S.paths[q].prev)) ch[n++] = q;
         sh_depth = n;
     }
     __syncthreads();
@@ -378,11 +381,11 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     {
         int dmax = 0;
         jd_for_each_tip<NE>(C, c, S, [&](int tip) {
-            int i = 0, q = tip;
+            int i = 0, q = word_rec(tip);
             for (;;) {
                 while (i < depth && ch[i] > q) ++i;
                 if (i == depth || ch[i] == q) break;
-                q = S.paths[q].prev;
+                q = word_rec(S.paths[q].prev);
                 if (q < 0) { i = depth; break; }
             }
             dmax = max(dmax, i);
@@ -401,8 +404,9 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     if (tid == 0) { out[0] = 1; out[1] = n; }
 }
 
-// recognitionFinish (:230-309): walk the Path chain of bestFinalToken.
-__global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int n)
+// recognitionFinish (:230-309): walk the Path chain of bestFinalToken.  res_model (model-level output, else null): the records'
+// models beside the five arrays, [stream][res_cap] - every record then, and the host picks the words out.
+__global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int n, int *res_model)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -416,6 +420,7 @@ __global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int
             const PathRec pr = S.paths[p];
             S.res_label[k] = pr.label; S.res_time[k] = pr.frame;
             S.res_score[k] = pr.score; S.res_ac[k] = pr.ac; S.res_lm[k] = pr.lm;
+            if (res_model) res_model[(size_t)(s0 + s) * S.res_cap + k] = pr.model;
             if (k == 0) { S.res_score[0] = best.score; S.res_ac[0] = best.ac; S.res_lm[0] = best.lm; }   // :293-300
         }
         ++k;
@@ -426,9 +431,10 @@ __global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int
 // ... and the same for the batch pipeline (jd_pipe_*): the utterances of a list of streams, exported to VIRTUAL result slots -
 // word count, the five result arrays, a copy of the control block (statistics, error, bestFinalToken) - so that the stream
 // can take its next utterance before the batch this one belongs to is handed back.  One 64-thread block per utterance.
+// vres_model (model-level output, else null): the records' models, [vslot][res_cap].
 struct ExportList { int n; int slot[64]; int vslot[64]; };
 __global__ void jd_finish_export_kernel(const StreamCtl *ctl, const StreamDev *streams, ExportList L, StreamCtl *vctl, int *vres_n, int *vres,
-                                        int res_cap)
+                                        int res_cap, int *vres_model)
 {
     const int i = blockIdx.x;
     if (i >= L.n) return;
@@ -450,6 +456,7 @@ __global__ void jd_finish_export_kernel(const StreamCtl *ctl, const StreamDev *s
         if (k < res_cap) {
             const PathRec pr = S.paths[p];
             lab[k] = pr.label; tim[k] = pr.frame; sc[k] = pr.score; ac[k] = pr.ac; lm[k] = pr.lm;
+            if (vres_model) vres_model[(size_t)v * res_cap + k] = pr.model;
             if (k == 0) { sc[0] = best.score; ac[0] = best.ac; lm[0] = best.lm; }     // :293-300
         }
         ++k;

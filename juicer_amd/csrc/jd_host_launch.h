@@ -24,15 +24,17 @@ static int learn_load(jd_dec *d, const std::vector<int2> &work_in)
 }
 
 // the flavours of k_search (jd_search.h): HMMs of up to 5 / 8 states, agent-scope / XCD-local memory model, static / lazily
-// composed graph
+// composed graph, word / model-level output
 typedef void (*SearchKernel)(SearchArgs);
-static SearchKernel search_kernel(bool ne3, bool xl, bool lazy)
+static SearchKernel search_kernel(bool ne3, bool xl, bool lazy, bool mdl)
 {
-    static const SearchKernel tab[8] = {
-        k_search<6, false, false>, k_search<6, false, true>, k_search<6, true, false>, k_search<6, true, true>,
-        k_search<3, false, false>, k_search<3, false, true>, k_search<3, true, false>, k_search<3, true, true>,
+    static const SearchKernel tab[16] = {
+        k_search<6, false, false, false>, k_search<6, false, true, false>, k_search<6, true, false, false>, k_search<6, true, true, false>,
+        k_search<3, false, false, false>, k_search<3, false, true, false>, k_search<3, true, false, false>, k_search<3, true, true, false>,
+        k_search<6, false, false, true>, k_search<6, false, true, true>, k_search<6, true, false, true>, k_search<6, true, true, true>,
+        k_search<3, false, false, true>, k_search<3, false, true, true>, k_search<3, true, false, true>, k_search<3, true, true, true>,
     };
-    return tab[(ne3 ? 4 : 0) + (xl ? 2 : 0) + (lazy ? 1 : 0)];
+    return tab[(mdl ? 8 : 0) + (ne3 ? 4 : 0) + (xl ? 2 : 0) + (lazy ? 1 : 0)];
 }
 
 // Advance the streams of `work` ({stream, likelihood slot}) through frames [.., f_end) with ONE
@@ -338,7 +340,7 @@ static int launch_search(jd_dec *d, const std::vector<int2> &work_first, const f
             const bool lz = d->C.lazy != nullptr;
             for (int v = 0; v < 2; ++v) {
                 int per_cu = 0;
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)search_kernel(ne3, v != 0, lz), SNT, 0));
+                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)search_kernel(ne3, v != 0, lz, d->models), SNT, 0));
                 if (per_cu < WG_PER_CU)
                     return jd_fail(JD_EHIP, "k_search needs %d workgroup(s) of %d threads resident per CU, the device takes %d: "
                                    "its clusters could not all be resident at once", WG_PER_CU, SNT, per_cu);
@@ -391,10 +393,13 @@ static int launch_search(jd_dec *d, const std::vector<int2> &work_first, const f
                            hold_replan ? 1 : 0);
         HIPCHK(hipEventRecord(e0, st));
         if (slot_batch) {
-            if (ne3) hipLaunchKernelGGL(k_slot_batch<3>, dim3((unsigned)n_work), dim3(SNT), 0, st, A);
-            else hipLaunchKernelGGL(k_slot_batch<6>, dim3((unsigned)n_work), dim3(SNT), 0, st, A);
+            if (d->models) {
+                if (ne3) hipLaunchKernelGGL((k_slot_batch<3, true>), dim3((unsigned)n_work), dim3(SNT), 0, st, A);
+                else hipLaunchKernelGGL((k_slot_batch<6, true>), dim3((unsigned)n_work), dim3(SNT), 0, st, A);
+            } else if (ne3) hipLaunchKernelGGL((k_slot_batch<3, false>), dim3((unsigned)n_work), dim3(SNT), 0, st, A);
+            else hipLaunchKernelGGL((k_slot_batch<6, false>), dim3((unsigned)n_work), dim3(SNT), 0, st, A);
         } else
-        hipLaunchKernelGGL(search_kernel(ne3, xl, d->C.lazy != nullptr), dim3(grid), dim3(SNT), 0, st, A);
+        hipLaunchKernelGGL(search_kernel(ne3, xl, d->C.lazy != nullptr, d->models), dim3(grid), dim3(SNT), 0, st, A);
         HIPCHK(hipEventRecord(e1, st));
         HIPCHK(hipGetLastError());
         if (d->pf_armed && pf_wants_scoring(d)) {

@@ -174,8 +174,11 @@ int jd_res_start(jd_dec *d, int n_streams, int rows_per_buf)
     if (const char *e = jd_dev_env("JD_RES_SLOT")) R->slot = R->slot && atoi(e) != 0;
     {
         int per_cu = 0;
-        const void *kf = R->slot ? (ne3 ? (const void *)k_slot<3> : (const void *)k_slot<6>)
-                                 : (ne3 ? (const void *)k_resident<3, false> : (const void *)k_resident<6, false>);
+        const bool m = d->models;
+        const void *kf = R->slot ? (ne3 ? (m ? (const void *)k_slot<3, true> : (const void *)k_slot<3, false>)
+                                        : (m ? (const void *)k_slot<6, true> : (const void *)k_slot<6, false>))
+                                 : (ne3 ? (m ? (const void *)k_resident<3, false, true> : (const void *)k_resident<3, false, false>)
+                                        : (m ? (const void *)k_resident<6, false, true> : (const void *)k_resident<6, false, false>));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, SNT, 0));
         const int need = R->slot ? SLOT_WG_PER_CU : WG_PER_CU;
         if (per_cu < need)
@@ -219,7 +222,8 @@ int jd_res_start(jd_dec *d, int n_streams, int rows_per_buf)
     const bool slot = R->slot;
     if (const char *e = jd_dev_env("JD_RES_XL")) xl = xl && atoi(e) != 0;   // development
     typedef void (*ResKernel)(SearchArgs, const ResPost *, ResMail *, const unsigned *, ResDone *, int, const unsigned *);
-    const ResKernel rk = ne3 ? (xl ? k_resident<3, true> : k_resident<3, false>) : (xl ? k_resident<6, true> : k_resident<6, false>);
+    const ResKernel rk = d->models ? (ne3 ? (xl ? k_resident<3, true, true> : k_resident<3, false, true>) : (xl ? k_resident<6, true, true> : k_resident<6, false, true>))
+                                   : (ne3 ? (xl ? k_resident<3, true, false> : k_resident<3, false, false>) : (xl ? k_resident<6, true, false> : k_resident<6, false, false>));
     // HIP maps streams onto a few hardware queues, and whatever is queued BEHIND a kernel that stays waits until it leaves:
     // the side stream's scoring, the null stream's copies back.  Which queue a stream gets is the runtime's business
     // (tools/resident_alias_probe.py: one fresh stream in fourteen lands behind the kernel), so the kernel is started, a
@@ -270,8 +274,11 @@ int jd_res_start(jd_dec *d, int n_streams, int rows_per_buf)
                     std::this_thread::sleep_for(std::chrono::microseconds(20));
             }
             unsigned *started = parked ? d->h_park + 4 : nullptr;
-            if (ne3) hipLaunchKernelGGL(k_slot<3>, rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
-            else hipLaunchKernelGGL(k_slot<6>, rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
+            if (d->models) {
+                if (ne3) hipLaunchKernelGGL((k_slot<3, true>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
+                else hipLaunchKernelGGL((k_slot<6, true>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
+            } else if (ne3) hipLaunchKernelGGL((k_slot<3, false>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
+            else hipLaunchKernelGGL((k_slot<6, false>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
             if (parked) {                                              // every slot is on its CU (or 100 ms are over): the parked CUs are the scoring's
                 const auto tp = std::chrono::steady_clock::now();
                 while (__atomic_load_n(&d->h_park[4], __ATOMIC_ACQUIRE) < (unsigned)park_fill &&
@@ -370,7 +377,7 @@ int jd_res_init(jd_dec *d, int s)
     }
     hipLaunchKernelGGL(jd_mark_init_kernel, dim3(1), dim3(64), 0, d->s_gmm, d->d_ctl, s, 1);
     HIPCHK(hipGetLastError());
-    d->stream_T[(size_t)s] = 0; d->stream_started[(size_t)s] = 1;
+    d->stream_T[(size_t)s] = 0; d->stream_started[(size_t)s] = 1; d->stream_open[(size_t)s] = 0;
     R->T_posted[(size_t)s] = 0; R->T_done[(size_t)s] = 0; R->err_done[(size_t)s] = 0;
     return res_bump(d, 1, &s);
 }
@@ -487,7 +494,7 @@ int jd_res_finish(jd_dec *d, int s, jd_hyp *out)
     if (rc0) return rc0;
     Resident *R = d->res;
     if (!R || !R->on || s < 0 || s >= R->n || !out) return jd_fail(JD_ESTATE, "jd_res_finish: no resident kernel for stream %d", s);
-    hipLaunchKernelGGL(jd_finish_kernel, dim3(1), dim3(64), 0, d->s_gmm, d->d_ctl, d->d_streams, s, 1);
+    hipLaunchKernelGGL(jd_finish_kernel, dim3(1), dim3(64), 0, d->s_gmm, d->d_ctl, d->d_streams, s, 1, res_model_of(d));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->s_gmm));
     std::vector<jd_hyp> tmp((size_t)d->max_streams);
@@ -522,6 +529,7 @@ struct Pipe {
     float *d_ll = nullptr;                             // K tables
     int *d_ident = nullptr;                            // row r is frame r of the batch's features
     StreamCtl *d_vctl = nullptr; int *d_vresn = nullptr, *d_vres = nullptr;   // K x max_batch virtual result slots
+    int *d_vres_model = nullptr;                       // ... their models (model-level output)
     std::deque<PipeBatch> q;
     std::vector<char> table_used;
     std::vector<int> slot_batch_id, slot_utt;          // per slot: the batch (its serial number) and utterance it runs, -1: free
@@ -546,6 +554,7 @@ static void pipe_free(jd_dec *d)
     if (P->d_vctl) (void)hipFree(P->d_vctl);
     if (P->d_vresn) (void)hipFree(P->d_vresn);
     if (P->d_vres) (void)hipFree(P->d_vres);
+    if (P->d_vres_model) (void)hipFree(P->d_vres_model);
     if (P->ev_piece) (void)hipEventDestroy(P->ev_piece);
     delete P;
     d->pipe = nullptr;
@@ -583,7 +592,7 @@ static int pipe_pump(jd_dec *d)
     auto flush_exports = [&]() -> int {
         if (EL.n == 0) return JD_OK;
         hipLaunchKernelGGL(jd_finish_export_kernel, dim3((unsigned)EL.n), dim3(64), 0, d->s_gmm, d->d_ctl, d->d_streams, EL, P->d_vctl, P->d_vresn,
-                           P->d_vres, d->res_cap);
+                           P->d_vres, d->res_cap, d->models ? P->d_vres_model : nullptr);
         HIPCHK(hipGetLastError());
         EL.n = 0;
         return JD_OK;
@@ -720,6 +729,58 @@ extern "C" int jd_dec_set_pipeline(jd_dec *d, int32_t mode, int32_t depth, int32
     return JD_OK;
 }
 
+// What a decode returns (include/juicer_amd.h): words, or words and the model-level chain.  The search kernels come in a flavour
+// for each (MDL): the resident pipeline's kernel leaves, and whatever is announced under the old setting is dropped.
+extern "C" int jd_dec_set_output_level(jd_dec *d, int32_t level)
+{
+    if (!d) return jd_fail(JD_EINVAL, "jd_dec_set_output_level: null");
+    if (level != JD_OUTPUT_WORDS && level != (JD_OUTPUT_WORDS | JD_OUTPUT_MODELS))
+        return jd_fail(JD_EINVAL, "jd_dec_set_output_level: level %d (JD_OUTPUT_WORDS or JD_OUTPUT_WORDS | JD_OUTPUT_MODELS)", level);
+    const bool m = (level & JD_OUTPUT_MODELS) != 0;
+    if (m == d->models) return JD_OK;
+    if (d->res && d->res->on && !d->pipe_on) return jd_fail(JD_ESTATE, "jd_dec_set_output_level: a broker drives this decoder's resident kernel");
+    if (m && d->partial_interval > 0)
+        return jd_fail(JD_EINVAL, "jd_dec_set_output_level: partial traces (jd_dec_set_partial_interval) are not available with model-level output");
+    // (an utterance under way keeps the records of the level it began with: its result would mix the two)
+    for (int s = 0; s < d->max_streams; ++s)
+        if (d->stream_started[(size_t)s] && d->stream_open[(size_t)s])
+            return jd_fail(JD_ESTATE, "jd_dec_set_output_level: stream %d has an utterance under way (frames pushed since its jd_stream_init, "
+                           "no jd_stream_finish yet) - between utterances only", s);
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    pipe_drain(d);
+    pipe_free(d);                                                      // (its result slots are sized for the level)
+    pf_discard(d);
+    if (m && d->arenas_ready && !d->d_res_model) {
+        rc = dmalloc(d, &d->d_res_model, (size_t)d->max_streams * d->res_cap);
+        if (rc) return rc;
+    }
+    d->models = m;
+    d->occupancy_ok = false;                                           // (asked again for the flavours it now launches)
+    for (HostResult &R : d->results) R.m_n = -1;
+    return JD_OK;
+}
+
+extern "C" int jd_dec_get_output_level(const jd_dec *d, int32_t *level)
+{
+    if (!d || !level) return jd_fail(JD_EINVAL, "jd_dec_get_output_level: null");
+    *level = JD_OUTPUT_WORDS | (d->models ? JD_OUTPUT_MODELS : 0);
+    return JD_OK;
+}
+
+extern "C" int jd_dec_model_result(jd_dec *d, int32_t i, jd_model_hyp *out)
+{
+    if (!d || !out || i < 0 || (size_t)i >= d->results.size()) return jd_fail(JD_EINVAL, "jd_dec_model_result: bad argument");
+    if (!d->models) return jd_fail(JD_ESTATE, "jd_dec_model_result: the decoder's output level is JD_OUTPUT_WORDS");
+    const HostResult &R = d->results[(size_t)i];
+    memset(out, 0, sizeof *out);
+    out->n = R.m_n;
+    out->model = R.m_model.data(); out->label = R.m_label.data(); out->time = R.m_time.data();
+    out->score = R.m_score.data(); out->ac = R.m_ac.data(); out->lm = R.m_lm.data();
+    out->tot_score = R.m_tot[0]; out->tot_ac = R.m_tot[1]; out->tot_lm = R.m_tot[2];
+    return JD_OK;
+}
+
 // How the likelihood tables are scored (include/juicer_amd.h).  Whatever was scored or announced under the other setting is dropped.
 extern "C" int jd_dec_set_scoring(jd_dec *d, int32_t mode)
 {
@@ -788,7 +849,8 @@ static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int6
         if (hipMalloc(&P->d_ll, (size_t)P->K * P->table_rows * G * sizeof(float)) != hipSuccess ||
             hipMalloc(&P->d_ident, P->table_rows * sizeof(int)) != hipSuccess ||
             hipMalloc(&P->d_vctl, V * sizeof(StreamCtl)) != hipSuccess || hipMalloc(&P->d_vresn, V * sizeof(int)) != hipSuccess ||
-            hipMalloc(&P->d_vres, V * 5 * (size_t)d->res_cap * sizeof(int)) != hipSuccess) {
+            hipMalloc(&P->d_vres, V * 5 * (size_t)d->res_cap * sizeof(int)) != hipSuccess ||
+            (d->models && hipMalloc(&P->d_vres_model, V * (size_t)d->res_cap * sizeof(int)) != hipSuccess)) {
             (void)hipGetLastError();
             pipe_free(d);
             return jd_fail(JD_ENOMEM, "jd_dec_prefetch_scores: no memory for %d likelihood tables of %zu rows", d->pipe_depth, rows);
@@ -877,7 +939,8 @@ static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_
     for (int u = 0; u < n_utts; ++u) slot_of[(size_t)u] = F.u[(size_t)u].slot;
     if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);
     d->timing = jd_timing();
-    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), F.table * P->max_batch, n_utts, out, 0, nullptr);
+    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), F.table * P->max_batch, n_utts, out, 0, nullptr,
+                                      P->d_vres_model);
     for (int u = 0; u < n_utts; ++u) d->timing.search_frames += F.u[(size_t)u].T;
     d->timing.gmm_frames = d->timing.search_frames; d->timing.gmm_states = d->am->n_gmm;
     d->timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();

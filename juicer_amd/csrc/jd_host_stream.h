@@ -28,6 +28,7 @@ extern "C" int jd_stream_init(jd_dec *d, int32_t s)
     HIPCHK(hipStreamSynchronize(d->s_search));
     d->stream_T[(size_t)s] = 0;
     d->stream_started[(size_t)s] = 1;
+    d->stream_open[(size_t)s] = 0;
     d->last_collect[(size_t)s] = -1; d->last_trace[(size_t)s] = -1;    // WFSTDecoderLite.cpp:179-181, 202-206
     d->n_collect_host[(size_t)s] = 0;
     d->partial_label[(size_t)s].clear(); d->partial_time[(size_t)s].clear();
@@ -68,6 +69,7 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
     if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_push before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
+    if (n_frames > 0) d->stream_open[(size_t)s] = 1;
     const int D = d->am->D, G = d->am->n_gmm, Fc = d->Fc;
     hipStream_t st = d->s_search;
     pf_discard(d);                                                     // (the streaming path scores into table 0)
@@ -167,6 +169,7 @@ extern "C" int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, con
             return jd_fail(JD_EINVAL, "jd_streams_push: bad stream %d (each stream once)", s);
         if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_streams_push before jd_stream_init (stream %d)", s);
         seen[(size_t)s] = 1;
+        if (n_frames[i] > 0) d->stream_open[(size_t)s] = 1;
         rows += n_frames[i];
     }
     if (rows == 0) return JD_OK;
@@ -302,6 +305,9 @@ extern "C" int jd_debug_closure_path_counts(const jd_net *net, const jd_am *am, 
 extern "C" int jd_dec_set_partial_interval(jd_dec *d, int32_t interval)
 {
     if (!d || interval < 0) return jd_fail(JD_EINVAL, "jd_dec_set_partial_interval: traceInterval >= 0");
+    if (interval > 0 && d->models)
+        return jd_fail(JD_EINVAL, "jd_dec_set_partial_interval: partial traces are not available with model-level output "
+                       "(jd_stream_partial with trace_now is)");
     d->partial_interval = interval;
     d->C.path_rule = interval > 0 ? 1 : 0;             // (the kernel then watches collectPaths' count rule as well)
     d->C.pcount = nullptr;
@@ -375,13 +381,14 @@ extern "C" int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out)
         rc = launch_search(d, std::vector<int2>(1, make_int2(s, 0)), d->d_ll[0], 0, 0, 0, d->s_search);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(jd_finish_kernel, dim3(1), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, s, 1);
+    hipLaunchKernelGGL(jd_finish_kernel, dim3(1), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, s, 1, res_model_of(d));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->s_search));
     // results of stream s are stored at result slot s
     std::vector<jd_hyp> tmp((size_t)d->max_streams);
     rc = fetch_results(d, s, 1, tmp.data(), s);
     *out = tmp[(size_t)s];
+    d->stream_open[(size_t)s] = 0;
     if (d->lazy_in[(size_t)s]) { d->lazy_in[(size_t)s] = 0; jd_lazy_leave(d->net, 1); }   // the utterance has left the network
     if (d->partial_interval > 0 && out->n >= 0) {                      // :245-251 one more trace, from the best token
         std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];

@@ -60,7 +60,7 @@ __global__ void jd_res_reset_kernel(StreamCtl *ctl, ResMail *mail, unsigned *rea
 // XL: the workgroup-scope flavour of the search's memory operations (plain stores, atomics performed in the XCD's L2 - see
 // jd_search.h) - for clusters of ONE workgroup, which sit on one XCD by definition; a command's closing release writes
 // the L2 back for the kernels beside it, its opening acquire drops what they have made stale.
-template <int NE, bool XL>
+template <int NE, bool XL, bool MDL>
 // beat: a host-mapped word the host counts up whenever it looks after the kernel (jd_res_poll / jd_res_post / the batch pipeline's pump).  A cluster
 // without a command does not leave while that word moves: one caller of a broker may pause for as long as it likes while the others keep the
 // kernel busy (round 4 left after 5 s without a command for ITS stream, and the paused caller's next command was never served).  It leaves when
@@ -148,7 +148,7 @@ __global__ JD_KBOUNDS void k_resident(SearchArgs A, const ResPost *post, ResMail
         const long long t_cmd = wall_clock64();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __builtin_amdgcn_s_dcache_inv();
-        run_stream<NE, XL, false>(A, sh, s, ll_slot, jw, Cw, true, &nbar);
+        run_stream<NE, XL, false, MDL>(A, sh, s, ll_slot, jw, Cw, true, &nbar);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         // every workgroup of the cluster is through with the command (its end-of-launch words are written) before the host
         // hears of it: the collection and the finish kernels read them

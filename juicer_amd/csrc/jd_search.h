@@ -1041,8 +1041,14 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
 // record is written).  Closure items and slices: x = ordered score of the best arrival BEFORE this one
 // (0: none - this one is the first), label = the arc's word label.  flags & 3: 0 = to be expanded in
 // a later round, 1 = done (expanded by its producer, or superseded), 2 = a slice (>> 2: its number).
+//
+// Model-level output (MDL, jd_dec_set_output_level): a Path record is written for every WINNING exit token as well - its spare
+// word holds the arc's in-label (the model) - and for every expanded closure item whose arc had a tee model or a word label.
+// A closure item then carries its tee model in flags >> 2 (0: an epsilon arc); one this wave queued for itself keeps it in
+// LDS beside its queue entry.  Records are reserved behind the winner test (winners only), and only labelled records count
+// as Path statistics: the search itself, and what word mode reads of the records, do not change.
 struct XOut { int item_cnt; int new_cnt; int dirty_cnt; };
-template <bool XL, bool LZY>
+template <bool XL, bool LZY, bool MDL>
 __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, StreamCtl &c, const StreamView &V,
                                         const Geo &gin, const Geo &gout, int Q, int KX, int round, int jw, int Cw, int gw,
                                         int p, int pframe, bool init, bool last_frame, float endTh, float wordTh,
@@ -1061,6 +1067,8 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
     v4i *qtok = sh.qtok[wid], *qinfo = sh.qinfo[wid];
     int2 *qrow = sh.qrow[wid];
     int q_n = 0;                                                       // closure items waiting in this wave's queue
+    __shared__ int qmdl_[MDL ? SW : 1][QCAP];                          // MDL: the tee model of every queued closure item
+    int *qmdl = qmdl_[MDL ? wid : 0];
     int c_arcs = 0, c_paths = 0, c_pend = 0, c_new = 0, c_xitems = 0, c_walk = 0, c_clos = 0;
     int c_ref = 0;                                                     // Path objects the reference creates for this wave's exit tokens
     unsigned mo = 0u;
@@ -1088,12 +1096,14 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
         int slice_no = 0;                                              // > 0: this item is a slice of a state with many arcs
         const bool from_q = q_n > 0;                                   // (wave-uniform)
         int2 row_q = make_int2(0, 0);
+        int cmdl = 0;                                                  // MDL: a closure item's tee model
         if (from_q) {
             valid = lane < q_n;
             exit_kind = false;
             t = as_tok(qtok[lane & (QCAP - 1)]);
             info = qinfo[lane & (QCAP - 1)];
             row_q = qrow[lane & (QCAP - 1)];
+            if constexpr (MDL) cmdl = qmdl[lane & (QCAP - 1)];
             ii = (unsigned)info.w;                                     // (the queue keeps the item's index here)
             info.w = 0;
             q_n = 0;
@@ -1110,6 +1120,7 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
             exit_kind = round == 0;
             if (!exit_kind && (info.w & 3) == 1) valid = false;        // expanded by its producer / superseded
             if (!exit_kind && (info.w & 3) == 2) slice_no = info.w >> 2;
+            if constexpr (MDL) cmdl = exit_kind ? 0 : info.w >> 2;
         }
         XFINE(0);                                                      // hop 1: the items
         const unsigned ioff = valid ? icur + ii * 32u : OOB_OFF;
@@ -1139,9 +1150,11 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
         // Path records (:497-509) are reserved for every labelled item that passed its threshold, winner or not, so that
         // the reservation is in flight together with the loads below: it is issued BEHIND them (the compiler waits
         // for a returning atomic where it stands, and that wait then is the wait for the loads as well)
-        const bool labelled = real && have && info.y != 0;
+        // (MDL: behind the winner test, below)
+        const bool labelled = !MDL && real && have && info.y != 0;
         const unsigned long long blab = __ballot(labelled);
         int pbase = 0;
+        int amdl = 0;                                                  // MDL: an exit token's model (its arc's in-label)
         auto reserve = [&]() __attribute__((always_inline)) {
             if (blab) {
                 const int first = __ffsll((long long)blab) - 1;
@@ -1166,7 +1179,12 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
             if (!LZY) { const int sti = valid ? state : 0; srow = make_int2(C.row_ptr[sti], C.row_ptr[sti + 1]); }
             const bool lab_on = exit_kind && real && info.y != 0;      // (labelled exit tokens: a few per cent of the items)
             int lb;
-            if (LZY) lb = ld16(V.larcs, lab_on ? (unsigned)info.x * 16u : OOB_OFF).w;
+            if constexpr (MDL) {                                       // (every exit token's arc: its model, and its label)
+                const bool arc_on = exit_kind && real;
+                if (LZY) { const v4i la = ld16(V.larcs, arc_on ? (unsigned)info.x * 16u : OOB_OFF); lb = la.w; amdl = la.z; }
+                else { const JdArc la = C.arcs[arc_on ? info.x : 0]; lb = la.out; amdl = la.in; }
+                amdl &= ~ARC_FLAGS;
+            } else if (LZY) lb = ld16(V.larcs, lab_on ? (unsigned)info.x * 16u : OOB_OFF).w;
             else lb = C.arcs[lab_on ? info.x : 0].out;
             v4i lr = {0, 0, 0, 0};
             if (LZY) lr = ld16(V.lrows, (unsigned)state * 16u);        // {first arc, arcs, status, final weight}: ready by the invariant
@@ -1189,8 +1207,29 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
             if (winner && exit_kind && !sole) CS(info.y != 0 ? &SREC_BID(V.srec, C, state).keyL : &SREC_BID(V.srec, C, state).key0, 0ULL);
             have = have && winner;
         }
+        if constexpr (MDL) {                                           // a record for every winner that passed a model or a word label
+            const int mdl = exit_kind ? amdl : cmdl;
+            const bool rec = have && real && (label != 0 || mdl != 0);
+            const unsigned long long brec = __ballot(rec);
+            if (brec) {
+                const int first = __ffsll((long long)brec) - 1;
+                if (lane == first) pbase = GADD(&c.n_paths, __popcll(brec));
+                pbase = __shfl(pbase, first);
+            }
+            if (rec) {
+                const int pp = pbase + rank_in(brec);
+                if (pp < C.cap_paths) {
+                    // PathRec {prev, frame, label, model; score, ac, lm, -}
+                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, mdl};
+                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
+                    t.path = pp;
+                    st16(V.items, ioff, as_v4(t));
+                    if (label != 0) ++c_paths;
+                } else CS(&c.err[p], (int)JDE_PATHS);
+            }
+        }
         if (have && real) {
-            if (info.y != 0) {
+            if (!MDL && info.y != 0) {
                 const int pp = pbase + rank_in(blab);
                 if (pp < C.cap_paths) {
                     // PathRec {prev, frame, label, -; score, ac, lm, -}: two plain 16-byte stores (read by later launches only)
@@ -1427,11 +1466,12 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
                     const bool inq = keep && rank_in(bk) < room;       // expanded by this wave, right after this batch
                     if (pass) {
                         st16(V.items, icur + k * 32u, as_v4(un));
-                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, (keep && !inq) ? 0 : 1});
+                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, ((keep && !inq) ? 0 : 1) | (MDL && is_tee ? inl << 2 : 0)});
                     }
                     if (inq) {
                         const int qi = q_n + rank_in(bk);
                         qtok[qi] = as_v4(un); qinfo[qi] = (v4i){(int)ceo, Bk.out, Bk.to, (int)k}; qrow[qi] = nrow;
+                        if constexpr (MDL) qmdl[qi] = is_tee ? inl : 0;
                     }
                     const int nk = __popcll(bk);
                     const int n_inq = nk < room ? nk : room;
@@ -1465,7 +1505,7 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
 
 // nbar_io (or null): the cluster's barrier count so far, when the stream's barrier word is NOT zeroed between calls (the
 // resident kernel, jd_resident.h); updated on every normal return.
-template <int NE, bool XL, bool LZY>
+template <int NE, bool XL, bool LZY, bool MDL>
 __device__ __forceinline__ void run_stream(const SearchArgs &A, SearchShared &sh, int s, int ll_slot, int jw, int Cw, bool prio,
                                            unsigned *nbar_io = nullptr)
 {
@@ -1755,7 +1795,7 @@ __device__ __forceinline__ void run_stream(const SearchArgs &A, SearchShared &sh
             CLK(4);                                                    // phase X work lists
             const int round_start = xo.item_cnt;
             int deferred = 0;
-            phase_x<XL, LZY>(C, sh, c, V, gin, gout, Q, KX, round, jw, Cw, gw, p, init ? 0 : f, init, last_frame, endTh, wordTh, bestA, xo, deferred);
+            phase_x<XL, LZY, MDL>(C, sh, c, V, gin, gout, Q, KX, round, jw, Cw, gw, p, init ? 0 : f, init, last_frame, endTh, wordTh, bestA, xo, deferred);
             CLK(5);                                                    // phase X (wave 0's share)
             if (lane == 0) {
                 CS(tot_of(TOT_CL0 + ((round + 1) & 1)) + gw, deferred > 0 ? xo.item_cnt - round_start : 0);
@@ -1865,7 +1905,7 @@ __device__ __forceinline__ void run_stream(const SearchArgs &A, SearchShared &sh
 // one stream per workgroup): stream k owns the workgroups [first_k, first_k + n_k) - the host sizes
 // the clusters by the streams' recent load.  All workgroups of the grid must be resident at once:
 // the host sizes the grid to the device (one 512-thread workgroup per CU).
-template <int NE, bool XL, bool LZY>
+template <int NE, bool XL, bool LZY, bool MDL>
 __global__ JD_KBOUNDS void k_search(SearchArgs A)
 {
     __shared__ SearchShared sh;
@@ -1885,5 +1925,5 @@ __global__ JD_KBOUNDS void k_search(SearchArgs A)
         k = (jw < Cw) ? lo : A.n_work; kstep = A.n_work;
     }
     for (; k < A.n_work; k += kstep)
-        run_stream<NE, XL, LZY>(A, sh, RFL(A.work[k].x), RFL(A.work[k].y), jw, Cw, A.n_slots == 0 && (RFL(A.work[k].w) & 0x40000000) != 0);
+        run_stream<NE, XL, LZY, MDL>(A, sh, RFL(A.work[k].x), RFL(A.work[k].y), jw, Cw, A.n_slots == 0 && (RFL(A.work[k].w) & 0x40000000) != 0);
 }

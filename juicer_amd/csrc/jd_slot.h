@@ -367,7 +367,9 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
 
 // ------------------------------------------------------------------ phase X (see jd_search.h: phase_x)
 // xp / xc / xs: lanes 0 .. SW-1 of the calling wave hold, per writer segment, the chunks before it, its items and where
-// they start (built by the caller from the counts in LDS: every wave has its own copy - no barrier, no shared table)
+// they start (built by the caller from the counts in LDS: every wave has its own copy - no barrier, no shared table).
+// MDL: model-level output, as in phase_x.
+template <bool MDL>
 __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, const StreamView &V, const Geo &g, int Q, int KX, int round,
                                              int xp, int xc, int xs, int *next, int p, int pframe, bool init, bool last_frame,
                                              float endTh, float wordTh, float bestA, XOut &out, int &deferred)
@@ -386,6 +388,8 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
     v4i *qtok = sh.qtok[wid], *qinfo = sh.qinfo[wid];
     int2 *qrow = sh.qrow[wid];
     int q_n = 0;
+    __shared__ int qmdl_[MDL ? SW : 1][QCAP];                          // MDL: the tee model of every queued closure item
+    int *qmdl = qmdl_[MDL ? wid : 0];
     int c_arcs = 0, c_paths = 0, c_pend = 0, c_new = 0, c_ref = 0;
     unsigned mo = 0u;
     auto list_dirty = [&](bool first, int state) __attribute__((always_inline)) {
@@ -408,12 +412,14 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
         int slice_no = 0;
         const bool from_q = q_n > 0;                                   // (wave-uniform)
         int2 row_q = make_int2(0, 0);
+        int cmdl = 0;                                                  // MDL: a closure item's tee model
         if (from_q) {
             valid = lane < q_n;
             exit_kind = false;
             t = as_tok(qtok[lane & (QCAP - 1)]);
             info = qinfo[lane & (QCAP - 1)];
             row_q = qrow[lane & (QCAP - 1)];
+            if constexpr (MDL) cmdl = qmdl[lane & (QCAP - 1)];
             ii = (unsigned)info.w;
             info.w = 0;
             q_n = 0;
@@ -432,6 +438,7 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
             exit_kind = round == 0;
             if (!exit_kind && (info.w & 3) == 1) valid = false;        // expanded by its producer / superseded
             if (!exit_kind && (info.w & 3) == 2) slice_no = info.w >> 2;
+            if constexpr (MDL) cmdl = exit_kind ? 0 : info.w >> 2;
         }
         const unsigned ioff = valid ? icur + ii * 32u : OOB_OFF;
         const bool start_tok = valid && exit_kind && info.x < 0;       // recognitionStart's token: it has traversed no arc
@@ -449,9 +456,10 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
         if (C.pcount != nullptr && ((real && exit_kind && have) || start_tok))
             c_ref += (start_tok ? 0 : (info.y != 0 ? 1 : 0)) + C.pcount[state];
         // Path records (:497-509) are reserved for every labelled item that passed its threshold, winner or not: the cursor is in LDS
-        const bool labelled = real && have && info.y != 0;
+        const bool labelled = !MDL && real && have && info.y != 0;    // (MDL: behind the winner test, below)
         const unsigned long long blab = __ballot(labelled);
         int pbase = 0;
+        int amdl = 0;                                                  // MDL: an exit token's model (its arc's in-label)
         if (blab) {
             const int first = __ffsll((long long)blab) - 1;
             if (lane == first) pbase = atomicAdd(&sh.n_paths, __popcll(blab));
@@ -468,7 +476,9 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
             const int sti = valid ? state : 0;
             const int2 srow = make_int2(C.row_ptr[sti], C.row_ptr[sti + 1]);
             const bool lab_on = exit_kind && real && info.y != 0;
-            const int lb = C.arcs[lab_on ? info.x : 0].out;
+            int lb;
+            if constexpr (MDL) { const JdArc la = C.arcs[exit_kind && real ? info.x : 0]; lb = la.out; amdl = la.in & ~ARC_FLAGS; }
+            else lb = C.arcs[lab_on ? info.x : 0].out;
             label = lab_on ? lb : label;
             rs = srow.x; rs1 = srow.y;
             kv = ((unsigned long long)(unsigned)(info.y != 0 ? sk.w : sk.y) << 32) | (unsigned)(info.y != 0 ? sk.z : sk.x);
@@ -478,8 +488,28 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
             if (winner && exit_kind && !sole) CS(info.y != 0 ? &SREC_BID(V.srec, C, state).keyL : &SREC_BID(V.srec, C, state).key0, 0ULL);
             have = have && winner;
         }
+        if constexpr (MDL) {                                           // a record for every winner that passed a model or a word label
+            const int mdl = exit_kind ? amdl : cmdl;
+            const bool rec = have && real && (label != 0 || mdl != 0);
+            const unsigned long long brec = __ballot(rec);
+            if (brec) {
+                const int first = __ffsll((long long)brec) - 1;
+                if (lane == first) pbase = atomicAdd(&sh.n_paths, __popcll(brec));
+                pbase = __shfl(pbase, first);
+            }
+            if (rec) {
+                const int pp = pbase + rank_in(brec);
+                if (pp < C.cap_paths) {
+                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, mdl};
+                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
+                    t.path = pp;
+                    st16(V.items, ioff, as_v4(t));
+                    if (label != 0) ++c_paths;
+                } else slot_err(sh, (int)JDE_PATHS);
+            }
+        }
         if (have && real) {
-            if (info.y != 0) {
+            if (!MDL && info.y != 0) {
                 const int pp = pbase + rank_in(blab);
                 if (pp < C.cap_paths) {
                     V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, 0};
@@ -683,11 +713,12 @@ if (arrive) { eold = GMAX(&SREC_E(V.srec, C, state, p), ((unsigned long long)f2o
                     const bool inq = keep && rank_in(bk) < room;
                     if (pass) {
                         st16(V.items, icur + k * 32u, as_v4(un));
-                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, (keep && !inq) ? 0 : 1});
+                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, ((keep && !inq) ? 0 : 1) | (MDL && is_tee ? inl << 2 : 0)});
                     }
                     if (inq) {
                         const int qi = q_n + rank_in(bk);
                         qtok[qi] = as_v4(un); qinfo[qi] = (v4i){(int)ceo, Bk.out, Bk.to, (int)k}; qrow[qi] = nrow;
+                        if constexpr (MDL) qmdl[qi] = is_tee ? inl : 0;
                     }
                     const int nk = __popcll(bk);
                     const int n_inq = nk < room ? nk : room;
@@ -714,7 +745,7 @@ if (arrive) { eold = GMAX(&SREC_E(V.srec, C, state, p), ((unsigned long long)f2o
 }
 
 // ------------------------------------------------------------------ one stream, one command (see jd_search.h: run_stream)
-template <int NE>
+template <int NE, bool MDL>
 __device__ __forceinline__ void slot_run(const SearchArgs &A, SlotShared &sh, int s, int ll_slot)
 {
     constexpr bool XL_ = true;
@@ -952,7 +983,7 @@ __device__ __forceinline__ void slot_run(const SearchArgs &A, SlotShared &sh, in
             const int round_start = xo.item_cnt;
             int deferred = 0;
 #ifndef SLOT_EXP_NO_X
-            slot_phase_x(C, sh, V, g, Q, KX, round, xp, cnt, start, &sh.nextX[rb], p, init ? 0 : f, init, last_frame, endTh, wordTh, bestA, xo, deferred);
+            slot_phase_x<MDL>(C, sh, V, g, Q, KX, round, xp, cnt, start, &sh.nextX[rb], p, init ? 0 : f, init, last_frame, endTh, wordTh, bestA, xo, deferred);
 #endif
             SCLK(5);
             if (lane == 0) {
@@ -1038,19 +1069,19 @@ __device__ __forceinline__ void slot_run(const SearchArgs &A, SlotShared &sh, in
 // to nobody - so a batch with more utterances than the chip has room for needs no slots dealt by the host: the dispatcher puts the
 // next workgroup on a CU the moment one leaves, two per CU.  (launch_search: batches of more streams than CUs; and what the PMC
 // passes of profiles/ count - under the counters kernels run one after the other, and k_slot waits for the kernels beside it.)
-template <int NE>
+template <int NE, bool MDL>
 __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot_batch(SearchArgs A)
 {
     __shared__ SlotShared sh;
     const int k = (int)blockIdx.x;
     if (k >= A.n_work) return;
-    slot_run<NE>(A, sh, RFL(A.work[k].x), RFL(A.work[k].y));
+    slot_run<NE, MDL>(A, sh, RFL(A.work[k].x), RFL(A.work[k].y));
 }
 
 // The slot kernel under the mailbox of jd_resident.h (the same commands, reports, ready numbers and host heartbeat as
 // k_resident; grid = streams, one workgroup each, SLOT_WG_PER_CU of them per CU - all resident at once).
 // started (host-mapped, or null): counted up by every workgroup when it is on its CU - the host releases the parked CUs then (jd_park_kernel)
-template <int NE>
+template <int NE, bool MDL>
 __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot(SearchArgs A, const ResPost *post, const unsigned *ready, ResDone *done, const unsigned *beat,
                                                         unsigned *started)
 {
@@ -1117,7 +1148,7 @@ __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot(SearchArgs A, const ResP
         const long long t_cmd = wall_clock64();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __builtin_amdgcn_s_dcache_inv();
-        slot_run<NE>(A, sh, s, ll_slot);
+        slot_run<NE, MDL>(A, sh, s, ll_slot);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();                                               // every wave's end-of-command words are written before the host hears of it
