@@ -561,8 +561,8 @@ int jd_am_score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const 
  *   score / ac / lm  the token's there; entry 0 and the totals with the final state's weight, as in jd_hyp.
  * The search kernels write a Path record for every model the best paths pass: more records, more collections on heavy graphs.
  * Set between utterances: refused (JD_ESTATE) while a stream has frames pushed since its jd_stream_init and no jd_stream_finish
- * yet.  The result arrays of model-level output are allocated when it is first switched on.  Not with partial traces (jd_dec_set_partial_interval > 0; jd_stream_partial with trace_now works and
- * gives words), not under a broker (jd_broker_create refuses such a decoder; set it before creating one), and jd_multi_* decode
+ * yet.  The result arrays of model-level output are allocated when it is first switched on.  Not with partial traces (jd_dec_set_partial_interval > 0; jd_stream_partial / jd_stream_partial_models with trace_now work, the first
+ * gives words, the second models), not under a broker (jd_broker_create refuses such a decoder; set it before creating one), and jd_multi_* decode
  * words only.  jd_dec_model_result: result i of the decoder's last jd_stream_finish (i = the stream) or jd_decode_batch /
  * jd_decode_batch_device (i = the utterance); valid until the next decode, finish or jd_dec_set_output_level.  n = -1: no result
  * (as in jd_hyp); n is capped by the result capacity (8192 entries), a longer chain fails the decode with JD_ENOMEM.
@@ -582,6 +582,22 @@ typedef struct jd_model_hyp {
 int jd_dec_set_output_level(jd_dec *d, int32_t level);
 int jd_dec_get_output_level(const jd_dec *d, int32_t *level);
 int jd_dec_model_result(jd_dec *d, int32_t i, jd_model_hyp *out);
+/* The models' names, for printing phones (HTKModels::getHMMName / PhoneLookup::getModelStr): *name = the name of HMM i (HMM
+ * index i = in-label i + 1), as jd_am_load_mmf (the ~h name) or jd_am_load_jmbi (the JMHM record's name) read it - "" for an
+ * unnamed record of a file whose other records have names; NULL when the model set has no names (jd_am_create_htk / _flat /
+ * _hybrid, a JMBI file without names).  The string lives as long as a.  jd_am_save_jmbi writes the names back.
+ * JD_EINVAL: a null handle or i outside [0, jd_am_num_hmms). */
+int jd_am_hmm_name(const jd_am *a, int32_t i, const char **name);
+/* jd_stream_partial's trace at model level (JD_OUTPUT_MODELS; JD_ESTATE on a word-level decoder): the same trace_now, the same
+ * trace, and the list of the last trace that found something - every record of the chain from the root up to the record the
+ * word list ends at, model records and word records alike, OLDEST first, entries as in jd_model_hyp (no final-state weight:
+ * the utterance has not ended).  A trace through either call updates both lists: the word list is this list's entries with a
+ * label, and its last entry carries a word.  *n = the length (copied up to cap; any output pointer may be NULL).  A chain
+ * longer than the result capacity fails the trace with JD_ENOMEM.  Explicit traces only: jd_dec_set_partial_interval > 0
+ * stays refused at model level. */
+int jd_stream_partial_models(jd_dec *d, int32_t s, int32_t trace_now, int32_t cap, int32_t *n,
+                             int32_t *model, int32_t *label, int32_t *time, float *score, float *ac, float *lm,
+                             int32_t *found);
 
 /* What JD_FLOW_RESIDENT has done so far (cumulative over the decoder's life; a bench reads it on either side of its
  * timed region: frames_searched is what the slots really advanced in between, whatever was announced or handed back). */

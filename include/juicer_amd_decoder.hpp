@@ -3,10 +3,13 @@
 //
 //   class IDecoder        src/Decoder.h:18-30
 //   DecHyp / DecHypHist   src/DecHypHistPool.h:38-49, 146-165
+//   LabDecHypHist         src/DecHypHistPool.h:50-56, 106-107 (model-level output)
 //   WFSTDecoderLite ctor  src/WFSTDecoderLite.h:81-89
 //
 // Inside the Juicer tree include Juicer's own "Decoder.h" BEFORE this header:
 // GpuWFSTDecoder then derives from Juicer::IDecoder and returns Juicer::DecHyp.
+// Model-level output (setModelLevelOutput) needs Juicer::LabDecHypHist as well: include
+// "DecHypHistPool.h" before this header too.
 // Stand-alone, equivalent mirror types are declared here.
 #ifndef JUICER_AMD_DECODER_HPP
 #define JUICER_AMD_DECODER_HPP
@@ -23,6 +26,10 @@ using Juicer::DecHyp;
 using Juicer::DecHypHist;
 using Juicer::IDecoder;
 typedef Juicer::WFSTLattice LatticeT;     // src/WFSTLattice.h:52 (namespace Juicer, :20)
+#ifdef DECHYPHISTPOOL_INC                 // src/DecHypHistPool.h's include guard: the word label records of model-level output
+#define JUICER_AMD_HAVE_LABHIST 1
+using Juicer::LabDecHypHist;
+#endif
 }
 #else
 namespace JuicerAmd {
@@ -33,10 +40,20 @@ struct DecHypHist {                  // DecHypHistPool.h:38-49
     unsigned char type;
     int nConnect;
     DecHypHist *prev;
-    int state;                       // output label (word id + 1)
+    int state;                       // output label (word id + 1); model level: the model's in-label (HMM index + 1)
     int time;
     float score, acousticScore, lmScore;
 };
+#ifndef LABDHHTYPE
+#define LABDHHTYPE 2                  // DecHypHistPool.h:107
+#endif
+struct LabDecHypHist {               // DecHypHistPool.h:50-56: a word label in a model-level chain
+    unsigned char type;
+    int nConnect;
+    DecHypHist *prev;
+    int label;                       // output label (word id + 1)
+};
+#define JUICER_AMD_HAVE_LABHIST 1
 struct DecHyp {                      // DecHypHistPool.h:146-165 (fields used by the Lite core)
     DecHypHist *hist;
     int state;
@@ -186,7 +203,7 @@ public:
     GpuWFSTDecoder(const jd_net *network, const jd_am *models, float phoneStartPruneWin, float emitPruneWin,
                    float phoneEndPruneWin, float wordPruneWin, int maxEmitHyps, int device = 0,
                    int blockSize = 5, int flushFrames = 64)
-        : dec_(0), vecSize_(jd_am_vec_size(models)), nextFrame_(0), flush_(flushFrames)
+        : dec_(0), vecSize_(jd_am_vec_size(models)), nextFrame_(0), flush_(flushFrames), models_(false)
     {
         create(network, models, phoneStartPruneWin, emitPruneWin, phoneEndPruneWin, wordPruneWin, maxEmitHyps, device, blockSize);
     }
@@ -196,7 +213,7 @@ public:
     // Like the reference it does not own network / models; it keeps its own copies of what it read from them.
     GpuWFSTDecoder(Juicer::WFSTNetwork *network_, Juicer::IModels *models_, real phoneStartPruneWin_, real emitPruneWin_,
                    real phoneEndPruneWin_, real wordPruneWin_, int maxEmitHyps_)
-        : BridgedInputs_(network_, models_), dec_(0), vecSize_(jd_am_vec_size(bridgedAm_)), nextFrame_(0), flush_(64)
+        : BridgedInputs_(network_, models_), dec_(0), vecSize_(jd_am_vec_size(bridgedAm_)), nextFrame_(0), flush_(64), models_(false)
     {
         int device = 0, blockSize = 5;
         if (const char *e = getenv("JUICER_AMD_DEVICE")) device = atoi(e);
@@ -206,8 +223,26 @@ public:
 #endif
     virtual ~GpuWFSTDecoder() { jd_dec_destroy(dec_); }
 
-    bool modelLevelOutput() { return false; }      // WFSTDecoderLite.h:106
+    bool modelLevelOutput() { return models_; }    // WFSTDecoderLite.h:106 (false unless set below)
     LatticeT *getLattice() { return 0; }           // WFSTDecoderLite.h:107
+
+    // basicCore's modelLevelOutput (WFSTDecoder's constructor argument): finish() then returns the chain
+    // extendModelEndState builds (WFSTDecoder.cpp:803-855) - a DHHTYPE record per model the best path passed (state =
+    // the model's in-label, time = the frame it was left) and a LABDHHTYPE LabDecHypHist per word label, the label's
+    // record older than the model record of the same arc - as DecoderSingleTest::extractResultsFromHypPhoneMode reads it.
+    // Between utterances (jd_dec_set_output_level).
+    void setModelLevelOutput(bool on)
+    {
+#ifndef JUICER_AMD_HAVE_LABHIST
+        if (on) {
+            fprintf(stderr, "juicer_amd: setModelLevelOutput(true) needs Juicer's LabDecHypHist: include \"DecHypHistPool.h\" "
+                            "before juicer_amd_decoder.hpp\n");
+            exit(1);
+        }
+#endif
+        check(jd_dec_set_output_level(dec_, on ? (JD_OUTPUT_WORDS | JD_OUTPUT_MODELS) : JD_OUTPUT_WORDS));
+        models_ = on;
+    }
 
     void init()                                     // recognitionStart
     {
@@ -240,6 +275,9 @@ public:
             fprintf(stderr, "WARNING: no token survived at the end of decoding\n");   // WFSTDecoderLite.cpp:266
             return 0;
         }
+#ifdef JUICER_AMD_HAVE_LABHIST
+        if (models_) return finishModels();
+#endif
         hist_.assign(h.n > 0 ? h.n : 0, DecHypHist());
         for (int k = 0; k < h.n; ++k) {             // chain order: hist_[0] is hyp->hist (newest word)
             DecHypHist &d = hist_[k];
@@ -275,6 +313,43 @@ public:
     }
 
 private:
+#ifdef JUICER_AMD_HAVE_LABHIST
+    // the jd_model_hyp of the same decode (newest first) as one DecHypHist chain: an entry with a model gives a DHHTYPE
+    // record, one with a word label a LABDHHTYPE record, one with both the two, the DHHTYPE one newer (addLabelHist, then
+    // addHistToDecHyp: WFSTDecoder.cpp:833-845)
+    DecHyp *finishModels()
+    {
+        jd_model_hyp m;
+        check(jd_dec_model_result(dec_, 0, &m));
+        int nd = 0, nl = 0;
+        for (int k = 0; k < m.n; ++k) { nd += m.model[k] != 0; nl += m.label[k] != 0; }
+        hist_.assign((size_t)nd, DecHypHist());
+        lab_.assign((size_t)nl, LabDecHypHist());
+        DecHypHist *head = 0, **link = &head;
+        int id = 0, il = 0;
+        for (int k = 0; k < m.n; ++k) {
+            if (m.model[k] != 0) {
+                DecHypHist &d = hist_[(size_t)id++];
+                d.type = DHHTYPE; d.nConnect = 1; d.prev = 0;
+                d.state = m.model[k]; d.time = m.time[k];
+                d.score = m.score[k]; d.acousticScore = m.ac[k]; d.lmScore = m.lm[k];
+                *link = &d; link = &d.prev;
+            }
+            if (m.label[k] != 0) {
+                LabDecHypHist &l = lab_[(size_t)il++];
+                l.type = LABDHHTYPE; l.nConnect = 1; l.prev = 0; l.label = m.label[k];
+                *link = reinterpret_cast<DecHypHist *>(&l);     // (DecHypHistPool.h:30-36: the records share their first three fields)
+                link = &l.prev;
+            }
+        }
+        hyp_ = DecHyp();
+        if (head) {
+            hyp_.hist = head;
+            hyp_.score = m.tot_score; hyp_.acousticScore = m.tot_ac; hyp_.lmScore = m.tot_lm;
+        }
+        return &hyp_;                               // valid until the next init(), like the reference
+    }
+#endif
     void create(const jd_net *network, const jd_am *models, float startWin, float emitWin, float endWin, float wordWin,
                 int maxEmitHyps, int device, int blockSize)
     {
@@ -294,8 +369,12 @@ private:
     }
     jd_dec *dec_;
     int vecSize_, nextFrame_, flush_;
+    bool models_;
     std::vector<float> pending_;
     std::vector<DecHypHist> hist_;
+#ifdef JUICER_AMD_HAVE_LABHIST
+    std::vector<LabDecHypHist> lab_;
+#endif
     DecHyp hyp_;
     jd_stats stats_;
 };
@@ -303,8 +382,8 @@ private:
 // Drop-in for `new WFSTOnTheFlyDecoder(clNetwork, gNetwork, models, mainBeam, phoneEndBeam, maxHyps,
 // modelLevelOutput, latticeGeneration, doLabelAndWeightPushing, true)` (juicer.cpp:594-598): C.L and G stay
 // apart and are composed where the search goes (jd_net_create_lazy).  The composed network is owned here and
-// keeps what has been expanded from one utterance to the next.  modelLevelOutput / latticeGeneration are not
-// offered (as in GpuWFSTDecoder); doPushing: JD_PUSH_WEIGHTS | JD_PUSH_LABELS is the reference's doLabelAndWeightPushing
+// keeps what has been expanded from one utterance to the next.  modelLevelOutput: setModelLevelOutput (as in
+// GpuWFSTDecoder); latticeGeneration is not offered; doPushing: JD_PUSH_WEIGHTS | JD_PUSH_LABELS is the reference's doLabelAndWeightPushing
 // = true; maxStates / maxArcs: the room the network may grow into (0 = defaults; when it fills up the arena starts
 // again between utterances, jd_net_lazy_set_high_water).
 struct LazyNetHolder_ {
@@ -390,6 +469,13 @@ public:
     }
     virtual ~GpuWFSTPooledDecoder() { if (client_ >= 0) (void)jd_broker_close(b_, client_); }
     bool modelLevelOutput() { return false; }      // WFSTDecoderLite.h:106
+    void setModelLevelOutput(bool on)               // a broker serves word output only (jd_broker_create)
+    {
+        if (on) {
+            fprintf(stderr, "juicer_amd: jd_broker_create: a broker serves word output only (the decoder's output level has JD_OUTPUT_MODELS)\n");
+            exit(1);
+        }
+    }
     LatticeT *getLattice() { return 0; }           // WFSTDecoderLite.h:107
     void init()
     {

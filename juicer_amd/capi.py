@@ -124,6 +124,7 @@ EXPORTS = [
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
     "jd_dec_set_scoring", "jd_am_score_frames_mode", "jd_debug_log1pe", "jd_debug_log_add",
     "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
+    "jd_am_hmm_name", "jd_stream_partial_models",
 ]
 
 _lib = None
@@ -380,6 +381,17 @@ class Models:
     def n_hmms(self):
         return int(lib().jd_am_num_hmms(self.h))
 
+    def hmm_names(self) -> Optional[List[str]]:
+        """The HMMs' names in index order (jd_am_hmm_name; HMM i = in-label i + 1), or None: models built from arrays."""
+        out = []
+        for i in range(self.n_hmms):
+            nm = C.c_char_p()
+            _check(lib().jd_am_hmm_name(self.h, C.c_int32(i), C.byref(nm)))
+            if nm.value is None:
+                return None
+            out.append(nm.value.decode())
+        return out
+
     @property
     def n_gmms(self):
         return int(lib().jd_am_num_gmms(self.h))
@@ -586,6 +598,26 @@ class Decoder:
                 break
             cap, trace_now = n.value, False
         return was_found, [(int(lab[i]), int(tim[i])) for i in range(n.value)]
+
+    def stream_partial_models(self, s: int = 0, trace_now: bool = False):
+        """(found, ModelHyp): stream_partial's trace at model level (jd_stream_partial_models) - every record from the root up
+        to the record the word list ends at, OLDEST first (unlike Hyp.models); tot_* are 0."""
+        n, found = C.c_int32(0), C.c_int32(0)
+        cap, was_found = 256, False
+        while True:
+            mod, lab, tim = (np.zeros(cap, np.int32) for _ in range(3))
+            sc, ac, lm = (np.zeros(cap, np.float32) for _ in range(3))
+            _check(lib().jd_stream_partial_models(self.h, C.c_int32(s), C.c_int32(1 if trace_now else 0), C.c_int32(cap), C.byref(n),
+                                                  _p(mod, C.c_int32), _p(lab, C.c_int32), _p(tim, C.c_int32),
+                                                  _p(sc, C.c_float), _p(ac, C.c_float), _p(lm, C.c_float), C.byref(found)))
+            if trace_now:
+                was_found = bool(found.value)
+            if n.value <= cap:
+                break
+            cap, trace_now = n.value, False
+        k = n.value
+        return was_found, ModelHyp(n=k, model=mod[:k].copy(), label=lab[:k].copy(), time=tim[:k].copy(), score=sc[:k].copy(),
+                                   ac=ac[:k].copy(), lm=lm[:k].copy(), tot_score=0.0, tot_ac=0.0, tot_lm=0.0)
 
     # -- DecoderBatchTest inner loop
     def decode_batch(self, feats: Sequence[np.ndarray]) -> List[Hyp]:

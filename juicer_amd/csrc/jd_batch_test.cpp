@@ -6,6 +6,9 @@
 //   -refFName expected results (MLF or one line per file), "Expected :" lines, insertion /
 //   deletion / substitution totals at HTK costs 7/7/10                                      (:145-201, :804-939)
 //   DecoderSingleTest::extractResultsFromHypWordMode  label-1, start/end frames       (DecoderSingleTest.cpp:403-468)
+//   -modelLevelOutput: DBT_MODE_WFSTDECODE_PHONES (DecoderBatchTest.cpp:44-56), the chain read as
+//   DecoderSingleTest::extractResultsFromHypPhoneMode does (DecoderSingleTest.cpp:471-565) and printed as
+//   DecoderBatchTest::outputResultPhones does (DecoderBatchTest.cpp:462-660): phones by HMM name
 //
 // Networks / models: the text FSM and HTK MMF, or - preferred when present, like
 // juicer.cpp:854-866 / :778-784 - Juicer's binary caches "<fsm>.bin" (JWNT) / "<mmf>.bin" (JMBI);
@@ -54,6 +57,55 @@ static jd_am *load_jdam(const char *path)
                          ht.data(), NT, tn.data(), tp.data()))
         die("jd_am_create_htk");
     return am;
+}
+
+// One record of a model-level DecHypHist chain, newest first: a model (DHHTYPE: state = in-label, time, scores) or a
+// word label (LABDHHTYPE: label = output label).
+struct ChainRec { int type, id, time; float ac, lm; };
+
+// jd_dec_model_result's entries as the chain the adapter builds from them (juicer_amd_decoder.hpp, finishModels): the
+// label record of an entry older than its model record
+static std::vector<ChainRec> chain_of(const jd_model_hyp &m)
+{
+    std::vector<ChainRec> c;
+    for (int k = 0; k < m.n; ++k) {
+        if (m.model[k] != 0) c.push_back(ChainRec{DHHTYPE, m.model[k], m.time[k], m.ac[k], m.lm[k]});
+        if (m.label[k] != 0) c.push_back(ChainRec{LABDHHTYPE, m.label[k], 0, 0.0f, 0.0f});
+    }
+    return c;
+}
+
+// DecoderSingleTest::extractResultsFromHypPhoneMode (DecoderSingleTest.cpp:471-565), restated: level 0 the phones (index =
+// state - 1, start = the previous phone's end, 0 for the first; ac / lm = differences of neighbouring phone records), level
+// 1 the words (label - 1, or -1), word k from the end beside phone k from the end (the two counters run independently)
+struct PhoneResult { std::vector<int> phone, start, end, word; std::vector<float> ac, lm; };
+static PhoneResult extract_phones(const std::vector<ChainRec> &c)
+{
+    PhoneResult r;
+    int nP = 0, nW = 0;
+    for (const ChainRec &x : c) (x.type == DHHTYPE ? nP : nW) += 1;
+    if (nP < nW) { fprintf(stderr, "DST::extractResultsFromHypPhoneMode - number of words exceeded num phones in result\n"); exit(1); }
+    if (nP == 0) return r;
+    if (nW == 0) { fprintf(stderr, "DST::extractResultsFromHypPhoneMode - no words found in result\n"); exit(1); }
+    r.phone.assign((size_t)nP, -1); r.start.assign((size_t)nP, -1); r.end.assign((size_t)nP, -1); r.word.assign((size_t)nP, -1);
+    r.ac.assign((size_t)nP, JD_LOG_ZERO); r.lm.assign((size_t)nP, JD_LOG_ZERO);
+    int p = nP - 1, w = nP - 1;
+    for (const ChainRec &x : c) {
+        if (x.type == DHHTYPE) {
+            r.phone[(size_t)p] = x.id - 1; r.ac[(size_t)p] = x.ac; r.lm[(size_t)p] = x.lm; r.end[(size_t)p] = x.time;
+            if (p < nP - 1) {
+                r.start[(size_t)p + 1] = r.end[(size_t)p];
+                r.ac[(size_t)p + 1] -= r.ac[(size_t)p];
+                r.lm[(size_t)p + 1] -= r.lm[(size_t)p];
+            }
+            --p;
+        } else {
+            r.word[(size_t)w] = x.id - 1;
+            --w;
+        }
+    }
+    r.start[0] = 0;
+    return r;
 }
 
 static bool file_exists(const std::string &p) { FILE *f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != 0; }
@@ -127,6 +179,7 @@ int main(int argc, char **argv)
     int removeSentMarks = 0;                   // -removeSentMarks (juicer.cpp:273)
     std::string sentStartWord, sentEndWord;    // -sentStartWord / -sentEndWord (DecVocabulary)
     int residentSlots = 0;
+    int modelLevel = 0;                        // -modelLevelOutput: phones (DBT_MODE_WFSTDECODE_PHONES)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto nxt = [&]() -> const char * { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -153,6 +206,10 @@ int main(int argc, char **argv)
         else if (a == "-refFName") refFName = nxt(); else if (a == "-removeSentMarks") removeSentMarks = 1;
         else if (a == "-outputFName") outputFName = nxt();
         else if (a == "-sentStartWord") sentStartWord = nxt(); else if (a == "-sentEndWord") sentEndWord = nxt();
+        else if (a == "-modelLevelOutput") modelLevel = 1;
+        // juicer.cpp's phone-lookup options (-monoListFName, -tiedListFName, -cdSepChars, -silMonophone, -pauseMonophone):
+        // accepted for the command lines that carry them; phones are printed by the models' own names
+        else if (a == "-monoListFName" || a == "-tiedListFName" || a == "-cdSepChars" || a == "-silMonophone" || a == "-pauseMonophone") (void)nxt();
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (!fsm || (!amf && !mmf) || !list) {
@@ -165,8 +222,18 @@ int main(int argc, char **argv)
                         "       [-residentSlots N   (a list longer than N goes through N one-workgroup slots of a search kernel that stays: a slot takes the\n"
                         "        next utterance the moment its own is through - jd_dec_set_pipeline, JD_FLOW_RESIDENT; -batch is then at least N)]\n"
                         "       [-gramFsmFName G [-gramInSymsFName S] [-gramOutSymsFName S] [-pushing | -weightPushing] [-lazy]   (-fsmFName is then C.L: composed with G on the\n"
-                        "        device, as a whole before the search or - with -lazy - by the search, where it goes)]\n");
+                        "        device, as a whole before the search or - with -lazy - by the search, where it goes)]\n"
+                        "       [-modelLevelOutput   (phones: the HMMs the best path passed, by the models' names, words beside them in mlf / xmlf;\n"
+                        "        not with -threads, -devices or -refFName)]\n"
+                        "       [-monoListFName F] [-tiedListFName F] [-cdSepChars C] [-silMonophone P] [-pauseMonophone P]   (accepted, no effect:\n"
+                        "        phones are printed by the HMM names of the models file)\n");
         return 2;
+    }
+    if (modelLevel) {                          // what cannot give models: refused before anything is loaded
+        const char *why = nThreads > 0 ? "-threads (a broker serves word output only)"
+                        : nDevices > 0 ? "-devices (jd_multi decodes words only)"
+                        : (refFName && refFName[0]) ? "-refFName (scoring against a phone reference is not offered)" : 0;
+        if (why) { fprintf(stderr, "jd_batch_test: -modelLevelOutput cannot be combined with %s\n", why); return 1; }
     }
     if (outputFName && outputFName[0] && strcmp(outputFName, "stdout") != 0) {     // DecoderBatchTest::openOutputFile
         if (strcmp(outputFName, "stderr") == 0) { if (dup2(2, 1) < 0) { perror("dup2"); return 1; } }
@@ -209,6 +276,22 @@ int main(int argc, char **argv)
         }
     } else am = load_jdam(amf);
     const int D = jd_am_vec_size(am);
+    std::vector<std::string> hmmNames;         // PhoneLookup::getModelStr (juicer.cpp:606-621): the models' names
+    if (modelLevel) {
+        for (int h = 0; h < jd_am_num_hmms(am); ++h) {
+            const char *nm = 0;
+            if (jd_am_hmm_name(am, h, &nm)) die("jd_am_hmm_name");
+            if (!nm) {
+                fprintf(stderr, "jd_batch_test: -modelLevelOutput needs the HMMs' names (an MMF or JMBI models file; %s has none)\n", amf ? amf : mmf);
+                return 1;
+            }
+            hmmNames.push_back(nm);
+        }
+    }
+    auto phone_name = [&](int index) -> std::string {
+        if (index >= 0 && (size_t)index < hmmNames.size()) return hmmNames[(size_t)index];
+        return std::to_string(index);
+    };
     if (lazy_cl && (useAdapter || nDevices > 0)) {
         // the decoder object composes for itself (GpuWFSTOnTheFlyDecoder, the mirror of juicer.cpp:594-598), resp.
         // every device gets a lazily composed network of its own (jd_multi_create_lazy)
@@ -314,6 +397,48 @@ int main(int argc, char **argv)
     // DecoderBatchTest::outputResult (DecoderBatchTest.cpp:339-430) on the word list that
     // DecoderSingleTest::extractResultsFromHypWordMode (DecoderSingleTest.cpp:403-468) derives from the
     // DecHyp chain: chain is newest first; start time = previous end time; per-word score deltas.
+    // DecoderBatchTest::outputResultPhones (DecoderBatchTest.cpp:528-645): the phone result of one utterance
+    auto print_utt_phones = [&](size_t u, const std::vector<ChainRec> &chain, double decTime) {
+        fprintf(stderr, "File: %s\n", files[u].c_str());
+        const PhoneResult r = extract_phones(chain);
+        const int n = (int)r.phone.size();
+        if (outputFormat == "ref") {
+            for (int j = 0; j < n; ++j) printf("%s ", phone_name(r.phone[j]).c_str());
+            printf("\n");
+        } else if (outputFormat == "trans") {
+            for (int j = 0; j < n; ++j) printf("%s ", phone_name(r.phone[j]).c_str());
+            printf("(trans-%d)\n", n);
+        } else if (outputFormat == "mlf" || outputFormat == "xmlf") {
+            std::string base = files[u];
+            size_t sl = base.rfind('/'); if (sl != std::string::npos) base = base.substr(sl + 1);
+            size_t dot = base.rfind('.'); if (dot != std::string::npos) base = base.substr(0, dot);
+            printf("\"*/%s.rec\"\n", base.c_str());
+            for (int j = 0; j < n; ++j) {
+                if (outputFormat == "mlf") printf("%s", phone_name(r.phone[j]).c_str());
+                else {                                 // HTK 100 ns units (:590-606)
+                    double s0 = (float)1.0e7 / (float)framesPerSec * (float)r.start[j];
+                    if (s0 > 0) s0 += (float)1.0e7 / (float)framesPerSec;
+                    double e0 = (float)1.0e7 / (float)framesPerSec * (float)r.end[j];
+                    if (e0 > 0) e0 += (float)1.0e7 / (float)framesPerSec;
+                    printf("%.0f %.0f %s %f", s0, e0, phone_name(r.phone[j]).c_str(), r.ac[j] + r.lm[j]);
+                }
+                if (r.word[j] >= 0) printf(" %s", word(r.word[j] + 1).c_str());
+                printf("\n");
+            }
+            printf(".\n");
+        } else {                                       // verbose
+            printf("%s\n", files[u].c_str());
+            printf("\tActual :    ");
+            for (int j = 0; j < n; ++j) printf("%s ", phone_name(r.phone[j]).c_str());
+            printf("  [ ");
+            for (int j = 0; j < n; ++j) printf("%d ", r.end[j] + 1);
+            printf("(%d) ]\n", nfr[u]);
+        }
+        const double uttTime = (double)nfr[u] / framesPerSec;
+        fprintf(stderr, "CPU time %.3f  speech time %.3f  RT factor %.3f\n", decTime, uttTime,
+                uttTime > 0 ? decTime / uttTime : 0.0);
+        decodeTime += decTime; speechTime += uttTime;
+    };
     auto print_utt = [&](size_t u, int n, const int32_t *label, const int32_t *time, const float *ac, const float *lm,
                          double decTime) {
         fprintf(stderr, "File: %s\n", files[u].c_str());
@@ -384,6 +509,7 @@ int main(int argc, char **argv)
             ? new JuicerAmd::GpuWFSTOnTheFlyDecoder(lazy_cl, lazy_g, am, mainBeam, endBeam, maxHyps, pushing, device)
             : new JuicerAmd::GpuWFSTDecoder(net, am, startBeam, mainBeam, endBeam, wordBeam, maxHyps, device);
         JuicerAmd::GpuWFSTDecoder &dec = *decp;
+        if (modelLevel) dec.setModelLevelOutput(true);
         if (lazy_cl) fprintf(stderr, "C.L (%lld arcs) o G (%lld arcs): composed by the search on device %d\n", (long long)jd_net_num_arcs(lazy_cl),
                              (long long)jd_net_num_arcs(lazy_g), device);
         for (size_t u = 0; u < files.size(); ++u) {
@@ -404,6 +530,21 @@ int main(int argc, char **argv)
                 fprintf(stderr, "Partial paths recovered at frames: ");
                 for (size_t k = 0; k < pf.size(); ++k) fprintf(stderr, "%03d ", pf[k]);
                 fprintf(stderr, "\n");
+            }
+            if (modelLevel) {                          // the DHHTYPE / LABDHHTYPE chain, newest first
+                std::vector<ChainRec> chain;
+                for (JuicerAmd::DecHypHist *h = hyp ? hyp->hist : 0; h;) {
+                    if (h->type == LABDHHTYPE) {
+                        const JuicerAmd::LabDecHypHist *l = reinterpret_cast<const JuicerAmd::LabDecHypHist *>(h);
+                        chain.push_back(ChainRec{LABDHHTYPE, l->label, 0, 0.0f, 0.0f});
+                        h = l->prev;
+                    } else {
+                        chain.push_back(ChainRec{DHHTYPE, h->state, h->time, h->acousticScore, h->lmScore});
+                        h = h->prev;
+                    }
+                }
+                print_utt_phones(u, chain, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                continue;
             }
             std::vector<int32_t> lab, tim;
             std::vector<float> hac, hlm;
@@ -485,6 +626,7 @@ int main(int argc, char **argv)
         jd_dec *dec = 0;
         if (residentSlots > batch) batch = residentSlots;
         if (jd_dec_create(&dec, net, am, startBeam, mainBeam, endBeam, wordBeam, maxHyps, 5, device, batch)) die("jd_dec_create");
+        if (modelLevel && jd_dec_set_output_level(dec, JD_OUTPUT_WORDS | JD_OUTPUT_MODELS)) die("jd_dec_set_output_level");
         if (residentSlots > 0 && jd_dec_set_pipeline(dec, JD_FLOW_RESIDENT, 2, residentSlots)) die("jd_dec_set_pipeline");
         std::vector<const float *> ptr(files.size());
         for (size_t u = 0; u < files.size(); ++u) ptr[u] = feats[u].data();
@@ -496,6 +638,12 @@ int main(int argc, char **argv)
         for (size_t u = 0; u < files.size(); ++u) tot += nfr[u];
         for (size_t u = 0; u < files.size(); ++u) {
             if (hyps[u].n < 0) fprintf(stderr, "WARNING: no token survived at the end of decoding\n");
+            if (modelLevel) {
+                jd_model_hyp mh;
+                if (jd_dec_model_result(dec, (int)u, &mh)) die("jd_dec_model_result");
+                print_utt_phones(u, chain_of(mh), tot ? dt * nfr[u] / tot : 0.0);
+                continue;
+            }
             print_utt(u, hyps[u].n > 0 ? hyps[u].n : 0, hyps[u].label, hyps[u].time, hyps[u].ac, hyps[u].lm,
                       tot ? dt * nfr[u] / tot : 0.0);
         }

@@ -315,6 +315,11 @@ struct jd_dec {
     std::vector<int> n_collect_host;           // collections of the stream's utterance so far (jd_stream_collect_info)
     std::vector<std::vector<int32_t>> partial_label, partial_time;   // partialPaths, oldest first
     int *d_partial_out = nullptr;
+    // ... the model-level list of the same traces (jd_stream_partial_models), oldest first, and k_partial's export of it,
+    // [model, label, time, score, ac, lm][res_cap] (model-level output only, allocated with d_res_model)
+    struct PartialModels { std::vector<int32_t> model, label, time; std::vector<float> score, ac, lm; };
+    std::vector<PartialModels> partial_m;
+    int *d_partial_model = nullptr;
     bool return_on_collect = false, collected_now = false;   // jd_stream_push: launch_search comes back after a collection by the count rule
     float *d_push = nullptr; size_t push_cap = 0;
     char *h_stage = nullptr; size_t stage_cap = 0;     // pinned staging of jd_streams_push
@@ -724,6 +729,7 @@ extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, f
     d->last_trace.assign((size_t)max_streams, -1);
     d->partial_label.resize((size_t)max_streams);
     d->partial_time.resize((size_t)max_streams);
+    d->partial_m.resize((size_t)max_streams);
     d->results.resize((size_t)max_streams);
     if (const char *e = jd_dev_env("JD_RES_CAP")) { const int v = atoi(e); if (v >= 16 && v <= (1 << 20)) d->res_cap = v; }   // (tests)
 #undef TRY
@@ -867,6 +873,8 @@ static int ensure_arenas_try(jd_dec *d, double mem_fraction)
     if (d->models) {                                                   // (model-level output only; else jd_dec_set_output_level)
         rc = dmalloc(d, &d->d_res_model, (size_t)B * d->res_cap);
         if (rc) return rc;
+        rc = dmalloc(d, &d->d_partial_model, (size_t)6 * d->res_cap);
+        if (rc) return rc;
     }
     size_t stream_bytes = 0;                                           // (the same for every stream: known after the first sizing pass)
     for (int s = 0; s < B; ++s) {
@@ -954,7 +962,7 @@ static int ensure_arenas(jd_dec *d)
         d->slab = ArenaSlab();
         if (d->h_status) { (void)hipHostFree(d->h_status); d->h_status = nullptr; }
         if (d->d_ll_slab) { (void)hipFree(d->d_ll_slab); d->d_ll_slab = nullptr; d->ll_cap = 0; for (int i = 0; i < 3; ++i) d->d_ll[i] = nullptr; }
-        d->d_res = nullptr; d->d_res_model = nullptr; d->d_streams = nullptr; d->d_T = nullptr; d->d_ctl = nullptr; d->d_status = nullptr;
+        d->d_res = nullptr; d->d_res_model = nullptr; d->d_partial_model = nullptr; d->d_streams = nullptr; d->d_T = nullptr; d->d_ctl = nullptr; d->d_status = nullptr;
         (void)hipGetLastError();
         if (rc != JD_ENOMEM || attempt == 3 || (u_slots > 0 && u_items > 0 && u_paths > 0)) return rc;
         d->cap_slots = u_slots; d->cap_items = u_items; d->cap_paths = u_paths; d->cap_new = 0;

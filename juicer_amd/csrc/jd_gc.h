@@ -347,12 +347,15 @@ __device__ __forceinline__ void jd_for_each_tip(const DecConst &C, const StreamC
     }
 }
 
+// pm (model-level output, else null): the model-level export of the same trace, [model, label, time, score, ac, lm][res_cap] -
+// every record of the chain from the found word record down to the root, oldest first; out[2] = their count (> res_cap: not
+// written, the host fails the trace)
 template <int NE>
-__global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, StreamDev *streams, int s, int last_frame, int *out)
+__global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, StreamDev *streams, int s, int last_frame, int *out, int *pm)
 {
     StreamCtl &c = ctl[s];
     StreamDev &S = streams[s];
-    __shared__ int sh_max, sh_bad, sh_cnt, sh_depth, sh_D;
+    __shared__ int sh_max, sh_bad, sh_cnt, sh_depth, sh_D, sh_nm;
     const int tid = threadIdx.x;
     if (tid == 0) { sh_max = -1; sh_bad = 0; sh_cnt = 0; sh_depth = 0; sh_D = 0; out[0] = 0; out[1] = 0; }
     __syncthreads();
@@ -400,6 +403,28 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     for (int k = tid; k < n && k < S.res_cap; k += blockDim.x) {       // traceWinningPaths :874-890, oldest first
         const PathRec pr = S.paths[ch[depth - 1 - k]];
         S.res_label[k] = pr.label; S.res_time[k] = pr.frame;
+    }
+    if (pm) {
+        // the whole chain below ch[D0] (the walk is serial, as the one that built ch): counted, then its record indices put
+        // in the model row oldest first, which every thread then replaces by the fields of its records
+        const int cap = S.res_cap;
+        if (tid == 0) {
+            int nm = 0;
+            for (int q = ch[D0]; q >= 0; q = S.paths[q].prev) ++nm;
+            if (nm <= cap) {
+                int k = nm;
+                for (int q = ch[D0]; q >= 0; q = S.paths[q].prev) pm[--k] = q;
+            }
+            sh_nm = nm; out[2] = nm;
+        }
+        __syncthreads();
+        const int nm = sh_nm;
+        if (nm <= cap)
+            for (int k = tid; k < nm; k += blockDim.x) {
+                const PathRec pr = S.paths[pm[k]];
+                pm[k] = pr.model; pm[cap + k] = pr.label; pm[2 * cap + k] = pr.frame;
+                pm[3 * cap + k] = __float_as_int(pr.score); pm[4 * cap + k] = __float_as_int(pr.ac); pm[5 * cap + k] = __float_as_int(pr.lm);
+            }
     }
     if (tid == 0) { out[0] = 1; out[1] = n; }
 }

@@ -462,6 +462,12 @@ extern "C" int jd_am_get_trans(const jd_am *a, float *trP, int16_t *se, float *t
     return JD_OK;
 }
 
+extern "C" int jd_am_hmm_name(const jd_am *a, int32_t i, const char **name)
+{
+    if (!a || !name || i < 0 || i >= a->n_hmm) return jd_fail(JD_EINVAL, "jd_am_hmm_name: bad argument");
+    *name = a->hmm_name.empty() ? nullptr : a->hmm_name[(size_t)i].c_str();
+    return JD_OK;
+}
 extern "C" void jd_am_destroy(jd_am *a) { delete a; }
 
 // ------------------------------------------------------------ HTK MMF text loader
@@ -526,7 +532,7 @@ extern "C" int jd_am_load_mmf(jd_am **out, const char *mmf_path)
     std::vector<std::string> sh_state_names;
     std::vector<MmfTm> tms;
     std::vector<std::string> sh_tm_names;
-    struct Hmm { int n; std::vector<int> gmm; int tm; };
+    struct Hmm { int n; std::vector<int> gmm; int tm; std::string name; };
     std::vector<Hmm> hmms;
 #define MMF_FAIL(...) return jd_fail(JD_EFORMAT, __VA_ARGS__)
     auto tag_int = [&](const std::string &tagname, int *v) -> bool {   // "<TAG> int" (htkparse.l: tag + INT is one token)
@@ -627,9 +633,9 @@ extern "C" int jd_am_load_mmf(jd_am **out, const char *mmf_path)
             MMF_FAIL("MMF: ~m tied-mixture pools are not supported by the flat models (HTKFlatModels.h:61-63)");
         } else if (m == "~h" || m == "~H") {
             if (D <= 0) MMF_FAIL("MMF: ~h before the global <VECSIZE>");
-            L.next();                                  // name (HMM index = order of appearance)
+            const std::string name = unquote(L.next());   // (HMM index = order of appearance)
             if (upper(L.next()) != "<BEGINHMM>") MMF_FAIL("MMF: <BEGINHMM> expected");
-            Hmm h; h.n = 0; h.tm = -1;
+            Hmm h; h.n = 0; h.tm = -1; h.name = name;
             if (!tag_int("<NUMSTATES>", &h.n) || h.n < 3) MMF_FAIL("MMF: <NUMSTATES> expected");
             h.gmm.assign((size_t)h.n, -1);
             while (upper(L.peek()) == "<VECSIZE>" || (L.peek().size() > 1 && L.peek()[0] == '<' && upper(L.peek()) != "<STATE>" &&
@@ -703,8 +709,11 @@ extern "C" int jd_am_load_mmf(jd_am **out, const char *mmf_path)
         hn[(size_t)h] = hmms[(size_t)h].n; ht[(size_t)h] = hmms[(size_t)h].tm;
         for (int j = 0; j < hmms[(size_t)h].n; ++j) hg[(size_t)h * max_n + j] = hmms[(size_t)h].gmm[(size_t)j];
     }
-    return jd_am_create_htk(out, D, G, max_mix, n_mix.data(), wt.data(), mu.data(), var.data(), H, max_n, hn.data(),
-                            hg.data(), ht.data(), NT, tn.data(), tp.data());
+    const int rc = jd_am_create_htk(out, D, G, max_mix, n_mix.data(), wt.data(), mu.data(), var.data(), H, max_n, hn.data(),
+                                    hg.data(), ht.data(), NT, tn.data(), tp.data());
+    if (rc == JD_OK)
+        for (const Hmm &h : hmms) (*out)->hmm_name.push_back(h.name);
+    return rc;
 }
 
 // ------------------------------------------------- Juicer binary caches: JWNT / JMBI
@@ -722,11 +731,15 @@ struct BinReader {
     template <typename T> T get() { T v{}; if (ok && fread(&v, sizeof(T), 1, f) != 1) ok = false; return v; }
     template <typename T> bool get_n(T *dst, size_t n) { if (ok && n && fread(dst, sizeof(T), n, f) != n) ok = false; return ok; }
     bool id(const char *tag) { char b[4] = {0, 0, 0, 0}; get_n(b, 4); return ok && memcmp(b, tag, 4) == 0; }
-    bool skip_name()                              // int len (incl. NUL) + len bytes
+    bool skip_name(std::string *name = nullptr)   // int len (incl. NUL) + len bytes
     {
         int len = get<int>();
         if (!ok || len < 0 || len > (1 << 20)) return ok = false;
-        if (len > 0) { std::vector<char> nm((size_t)len); get_n(nm.data(), (size_t)len); }
+        if (len > 0) {
+            std::vector<char> nm((size_t)len);
+            get_n(nm.data(), (size_t)len);
+            if (ok && name) name->assign(nm.data(), strnlen(nm.data(), (size_t)len));
+        }
         return ok;
     }
 };
@@ -735,6 +748,12 @@ struct BinWriter {
     template <typename T> void put(T v) { fwrite(&v, sizeof(T), 1, f); }
     template <typename T> void put_n(const T *p, size_t n) { if (n) fwrite(p, sizeof(T), n, f); }
     void id(const char *tag) { fwrite(tag, 1, 4, f); }
+    void name(const std::string &s)               // as BinReader::skip_name reads it; "" is the unnamed record (length 0)
+    {
+        if (s.empty()) { put<int>(0); return; }
+        put<int>((int)s.size() + 1);
+        put_n(s.c_str(), s.size() + 1);
+    }
 };
 // WFSTAlphabet::readBinary (WFSTNetwork.cpp:250-297): contents are not needed by this path
 bool skip_alphabet(BinReader &r, bool *has_aux)
@@ -975,11 +994,11 @@ extern "C" int jd_am_load_jmbi(jd_am **out, const char *path)
         if (!r.ok) JM_FAIL("HTKModels::readBinaryTransMat - error reading matrix %d", t);
         max_n = std::max(max_n, m.n);
     }
-    struct Hm { int n; std::vector<int> g; int tm; };
+    struct Hm { int n; std::vector<int> g; int tm; std::string name; };
     std::vector<Hm> hmms((size_t)n_hmm);
     for (int h = 0; h < n_hmm; ++h) {
         Hm &m = hmms[(size_t)h];
-        if (!r.id("JMHM") || !r.skip_name()) JM_FAIL("HTKModels::readBinaryHMM - error (HMM %d)", h);
+        if (!r.id("JMHM") || !r.skip_name(&m.name)) JM_FAIL("HTKModels::readBinaryHMM - error (HMM %d)", h);
         m.n = r.get<int>();
         if (!r.ok || m.n < 3 || m.n > JD_MAXN) JM_FAIL("HMM %d: %d states (3..%d supported)", h, m.n, JD_MAXN);
         m.g.resize((size_t)m.n); r.get_n(m.g.data(), (size_t)m.n);
@@ -1043,6 +1062,10 @@ extern "C" int jd_am_load_jmbi(jd_am **out, const char *path)
     a->hmm_n.resize((size_t)n_hmm); a->hmm_tm.resize((size_t)n_hmm);
     a->hmm_tee.assign((size_t)n_hmm, LZ);
     a->hmm_gmm.assign((size_t)n_hmm * max_n, -1);
+    bool named = false;                                                // (a file whose HMMs are all unnamed: no names)
+    for (const Hm &m : hmms) named = named || !m.name.empty();
+    if (named)
+        for (const Hm &m : hmms) a->hmm_name.push_back(m.name);
     for (int h = 0; h < n_hmm; ++h) {
         const Hm &m = hmms[(size_t)h];
         a->hmm_n[(size_t)h] = m.n; a->hmm_tm[(size_t)h] = m.tm; a->hmm_tee[(size_t)h] = tm_tee[(size_t)m.tm];
@@ -1110,7 +1133,7 @@ extern "C" int jd_am_save_jmbi(const jd_am *a, const char *path)
     }
     for (int h = 0; h < a->n_hmm; ++h) {
         const int n = a->hmm_n[(size_t)h];
-        w.id("JMHM"); w.put<int>(0); w.put<int>(n);
+        w.id("JMHM"); w.name(a->hmm_name.empty() ? std::string() : a->hmm_name[(size_t)h]); w.put<int>(n);
         w.put_n(&a->hmm_gmm[(size_t)h * MN], (size_t)n);
         w.put<int>(a->hmm_tm[(size_t)h]);
     }

@@ -755,6 +755,10 @@ extern "C" int jd_dec_set_output_level(jd_dec *d, int32_t level)
         rc = dmalloc(d, &d->d_res_model, (size_t)d->max_streams * d->res_cap);
         if (rc) return rc;
     }
+    if (m && d->arenas_ready && !d->d_partial_model) {
+        rc = dmalloc(d, &d->d_partial_model, (size_t)6 * d->res_cap);
+        if (rc) return rc;
+    }
     d->models = m;
     d->occupancy_ok = false;                                           // (asked again for the flavours it now launches)
     for (HostResult &R : d->results) R.m_n = -1;

@@ -32,33 +32,50 @@ extern "C" int jd_stream_init(jd_dec *d, int32_t s)
     d->last_collect[(size_t)s] = -1; d->last_trace[(size_t)s] = -1;    // WFSTDecoderLite.cpp:179-181, 202-206
     d->n_collect_host[(size_t)s] = 0;
     d->partial_label[(size_t)s].clear(); d->partial_time[(size_t)s].clear();
+    d->partial_m[(size_t)s] = jd_dec::PartialModels();
     return JD_OK;
 }
 
 // tracePartialPath (:824-868) on stream s at the frame it has reached; extends the stream's
-// partialPaths when a converged record is found
+// partialPaths when a converged record is found.  Model-level output: the same launch exports the whole chain below that
+// record as well (jd_stream_partial_models).
 static int trace_partial(jd_dec *d, int s, int *found)
 {
-    if (!d->d_partial_out) { int rc = dmalloc(d, &d->d_partial_out, 2); if (rc) return rc; }
+    if (!d->d_partial_out) { int rc = dmalloc(d, &d->d_partial_out, 3); if (rc) return rc; }
+    if (d->models && !d->d_partial_model) { int rc = dmalloc(d, &d->d_partial_model, (size_t)6 * d->res_cap); if (rc) return rc; }
     std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
     const int last_frame = Tm.empty() ? -1 : Tm.back();
+    int *pm = d->models ? d->d_partial_model : nullptr;
     hipStream_t st = d->s_search;
     if (d->am->max_n <= 5)
-        hipLaunchKernelGGL(k_partial<3>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out);
-    else hipLaunchKernelGGL(k_partial<6>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out);
+        hipLaunchKernelGGL(k_partial<3>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out, pm);
+    else hipLaunchKernelGGL(k_partial<6>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out, pm);
     HIPCHK(hipGetLastError());
-    int ho[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(ho, d->d_partial_out, sizeof ho, hipMemcpyDeviceToHost, st));
+    int ho[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(ho, d->d_partial_out, (pm ? 3 : 2) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     d->last_trace[(size_t)s] = d->stream_T[(size_t)s] - 1;             // :867
     if (found) *found = ho[0];
     if (!ho[0]) return JD_OK;
     if (ho[1] > d->res_cap) return jd_fail(JD_ENOMEM, "stream %d: partial path has %d records (> %d)", s, ho[1], d->res_cap);
+    if (pm && ho[2] > d->res_cap)
+        return jd_fail(JD_ENOMEM, "stream %d: the model-level partial path has %d records (> %d, the result capacity)", s, ho[2], d->res_cap);
     // the chain from the root to the found record; the records traced before are its prefix
     L.resize((size_t)ho[1]); Tm.resize((size_t)ho[1]);
     const int *base = d->d_res + (size_t)s * 5 * d->res_cap;           // res_label, res_time: arrays 0 and 1 of the stream
     HIPCHK(hipMemcpy(L.data(), base, (size_t)ho[1] * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(Tm.data(), base + d->res_cap, (size_t)ho[1] * 4, hipMemcpyDeviceToHost));
+    if (pm) {
+        const size_t nm = (size_t)ho[2];
+        std::vector<int32_t> h(6 * nm);
+        if (nm)
+            HIPCHK(hipMemcpy2D(h.data(), nm * 4, pm, (size_t)d->res_cap * 4, nm * 4, 6, hipMemcpyDeviceToHost));
+        jd_dec::PartialModels &P = d->partial_m[(size_t)s];
+        const float *f = (const float *)h.data();
+        P.model.assign(h.begin(), h.begin() + nm); P.label.assign(h.begin() + nm, h.begin() + 2 * nm);
+        P.time.assign(h.begin() + 2 * nm, h.begin() + 3 * nm);
+        P.score.assign(f + 3 * nm, f + 4 * nm); P.ac.assign(f + 4 * nm, f + 5 * nm); P.lm.assign(f + 5 * nm, f + 6 * nm);
+    }
     return JD_OK;
 }
 
@@ -366,6 +383,34 @@ extern "C" int jd_stream_partial(jd_dec *d, int32_t s, int32_t trace_now, int32_
     for (int k = 0; k < std::min<int>(cap, *n); ++k) {
         if (labels) labels[k] = L[(size_t)k];
         if (times) times[k] = Tm[(size_t)k];
+    }
+    if (found) *found = fnd;
+    return JD_OK;
+}
+
+extern "C" int jd_stream_partial_models(jd_dec *d, int32_t s, int32_t trace_now, int32_t cap, int32_t *n, int32_t *model,
+                                        int32_t *label, int32_t *time, float *score, float *ac, float *lm, int32_t *found)
+{
+    if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_partial_models: bad argument");
+    if (!d->models) return jd_fail(JD_ESTATE, "jd_stream_partial_models: the decoder's output level is JD_OUTPUT_WORDS");
+    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_partial_models before jd_stream_init");
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    int fnd = 0;
+    if (trace_now && d->stream_T[(size_t)s] > 0) {
+        rc = trace_partial(d, s, &fnd);
+        if (rc) return rc;
+    }
+    const jd_dec::PartialModels &P = d->partial_m[(size_t)s];
+    *n = (int32_t)P.model.size();
+    const size_t k = (size_t)std::min<int>(cap, *n);
+    if (k) {
+        if (model) memcpy(model, P.model.data(), k * 4);
+        if (label) memcpy(label, P.label.data(), k * 4);
+        if (time) memcpy(time, P.time.data(), k * 4);
+        if (score) memcpy(score, P.score.data(), k * 4);
+        if (ac) memcpy(ac, P.ac.data(), k * 4);
+        if (lm) memcpy(lm, P.lm.data(), k * 4);
     }
     if (found) *found = fnd;
     return JD_OK;

@@ -65,6 +65,9 @@ struct jd_am {
     // the feature vector holds one log posterior per model, output = x[model] - log prior (:481-512)
     bool hybrid = false;
     std::vector<float> log_prior;                 // [n_hmm]
+    // HMM names (HTKModels::getHMMName, for phone output): the MMF's ~h names / JMBI's JMHM names; empty when the models
+    // were built from arrays
+    std::vector<std::string> hmm_name;            // [n_hmm] or empty
 };
 
 int jd_fail(int code, const char *fmt, ...);      // sets jd_last_error(), returns code
