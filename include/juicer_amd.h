@@ -656,6 +656,14 @@ int jd_debug_expf(int32_t device, const float *x, int64_t n, float *out);
  * JD_SCORE_FAST kernel's (device only).  tests/test_logadd.py compares them with the host libm and the CPU oracle. */
 int jd_debug_log1pe(int32_t device, int32_t variant, const float *d, int64_t n, double *out);
 int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const float *y, int64_t n, float *out);
+/* ... and of the histogram pruning (Histogram.cpp:64-100 / 134-158).  jd_debug_hist_bin: the search kernels' bin of s[i]
+ * (jd_hist_bin: s rounded half away from zero in double, minus hist_min), -1 when it falls below hist_min, JD_EHIST above
+ * hist_max; device -1 runs the host twin; every s[i] must lie in (-2^31, 2^31) (no NaN, no infinity: JD_EINVAL).  jd_debug_hist_threshold: the kernels' one-wave calcThresh (hist_threshold) for
+ * each case c over the counts bins[c * nb .. c * nb + nb) of bins hist_min .. hist_min + nb - 1, nb in [1, 2048], with
+ * max_hyps[c] >= 1; device only.  tests/test_hist_cpu.py and tests/test_gpu_hist.py compare them with the CPU oracle. */
+int jd_debug_hist_bin(int32_t device, const float *s, int64_t n, int32_t hist_min, int32_t hist_max, int32_t *out);
+int jd_debug_hist_threshold(int32_t device, const int32_t *bins, int64_t n_cases, int32_t nb, const int32_t *max_hyps,
+                            int32_t hist_min, float *out);
 
 const char *jd_last_error(void);
 const char *jd_version(void);

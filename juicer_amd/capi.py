@@ -123,6 +123,7 @@ EXPORTS = [
     "jd_broker_create", "jd_broker_destroy", "jd_broker_open", "jd_broker_close", "jd_broker_init", "jd_broker_push",
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
     "jd_dec_set_scoring", "jd_am_score_frames_mode", "jd_debug_log1pe", "jd_debug_log_add",
+    "jd_debug_hist_bin", "jd_debug_hist_threshold",
     "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
     "jd_am_hmm_name", "jd_stream_partial_models",
 ]
@@ -481,6 +482,31 @@ def debug_log1pe(d, variant: int, device: int = -1):
     out = np.empty(d.shape[0], np.float64)
     _check(lib().jd_debug_log1pe(C.c_int32(device), C.c_int32(variant), _p(d, C.c_float), C.c_int64(d.shape[0]),
                                  _p(out, C.c_double)))
+    return out
+
+
+# jd_debug_hist_bin's sentinel below hist_min (above hist_max it gives JD_EHIST)
+HIST_BELOW = -1
+
+
+def debug_hist_bin(s, hist_min: int, hist_max: int, device: int = -1):
+    """The search kernels' Histogram::addScore bin of s[i]: the bin index, HIST_BELOW or JD_EHIST (device -1: the host twin)."""
+    s = _f32(s)
+    assert s.ndim == 1
+    out = np.empty(s.shape[0], np.int32)
+    _check(lib().jd_debug_hist_bin(C.c_int32(device), _p(s, C.c_float), C.c_int64(s.shape[0]), C.c_int32(hist_min),
+                                   C.c_int32(hist_max), _p(out, C.c_int32)))
+    return out
+
+
+def debug_hist_threshold(bins, max_hyps, hist_min: int, device: int = 0):
+    """The search kernels' Histogram::calcThresh (one wave per case): bins is n_cases x nb, max_hyps n_cases (device only)."""
+    bins, max_hyps = _i32(bins), _i32(max_hyps)
+    assert bins.ndim == 2 and max_hyps.shape == (bins.shape[0],)
+    out = np.empty(bins.shape[0], np.float32)
+    _check(lib().jd_debug_hist_threshold(C.c_int32(device), _p(bins, C.c_int32), C.c_int64(bins.shape[0]),
+                                         C.c_int32(bins.shape[1]), _p(max_hyps, C.c_int32), C.c_int32(hist_min),
+                                         _p(out, C.c_float)))
     return out
 
 

@@ -1928,6 +1928,84 @@ extern "C" int jd_debug_log_add(int32_t device, int32_t variant, const float *x,
     return JD_OK;
 }
 
+// Test hooks for the histogram pruning of the search kernels (Histogram.cpp:64-100 / 134-158).  jd_debug_hist_bin: out[i] =
+// jd_hist_bin(s[i], hist_min, hist_max) - the bin, JD_HIST_BELOW (-1) or JD_EHIST; device == -1 runs the host twin.
+// jd_debug_hist_threshold: out[c] = hist_threshold over bins[c * nb .. c * nb + nb) with max_hyps[c], one wave per case,
+// the very function k_search and the slot kernels call (device only: it is a wave-parallel search).
+__global__ void jd_debug_hist_bin_kernel(const float *s, long long n, int hist_min, int hist_max, int *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = jd_hist_bin(s[i], hist_min, hist_max);
+}
+__global__ void __launch_bounds__(64) jd_debug_hist_threshold_kernel(const int *bins, int nb, const int *max_hyps, int hist_min, float *out)
+{
+    __shared__ int sh_hist[HIST_MAX_BINS];
+    const int lane = threadIdx.x;
+    const size_t c = blockIdx.x;
+    for (int b = lane; b < nb; b += 64) sh_hist[b] = bins[c * (size_t)nb + b];
+    __syncthreads();
+    DecConst C;
+    memset(&C, 0, sizeof C);
+    C.max_hyps = max_hyps[c]; C.hist_min = hist_min; C.hist_nbins = nb;
+    const float th = hist_threshold(C, sh_hist, lane);
+    if (lane == 0) out[c] = th;
+}
+extern "C" int jd_debug_hist_bin(int32_t device, const float *s, int64_t n, int32_t hist_min, int32_t hist_max, int32_t *out)
+{
+    if (!s || !out || n < 0 || hist_min > hist_max) return jd_fail(JD_EINVAL, "jd_debug_hist_bin: bad argument");
+    for (int64_t i = 0; i < n; ++i)                          // (int)(s -+ 0.5) is defined, and equal on host and device, only here
+        if (!(s[i] > -2147483648.0f && s[i] < 2147483648.0f)) return jd_fail(JD_EINVAL, "jd_debug_hist_bin: s[%lld] not in (-2^31, 2^31)", (long long)i);
+    if (device == -1) {
+        for (int64_t i = 0; i < n; ++i) out[i] = jd_hist_bin(s[i], hist_min, hist_max);
+        return JD_OK;
+    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    float *ds = nullptr;
+    int *dy = nullptr;
+    HIPCHK(hipMalloc(&ds, std::max<size_t>((size_t)n, 1) * sizeof(float)));
+    HIPCHK(hipMalloc(&dy, std::max<size_t>((size_t)n, 1) * sizeof(int)));
+    HIPCHK(hipMemcpy(ds, s, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (n) hipLaunchKernelGGL(jd_debug_hist_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds, (long long)n,
+                              (int)hist_min, (int)hist_max, dy);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dy, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(ds); (void)hipFree(dy);
+    return JD_OK;
+}
+extern "C" int jd_debug_hist_threshold(int32_t device, const int32_t *bins, int64_t n_cases, int32_t nb, const int32_t *max_hyps,
+                                       int32_t hist_min, float *out)
+{
+    if (!bins || !max_hyps || !out || n_cases < 0 || n_cases > INT32_MAX || nb < 1 || nb > HIST_MAX_BINS)
+        return jd_fail(JD_EINVAL, "jd_debug_hist_threshold: bad argument");
+    if (device == -1) return jd_fail(JD_EINVAL, "jd_debug_hist_threshold: hist_threshold has no host twin (device only)");
+    for (int64_t c = 0; c < n_cases; ++c) {                // the kernels' domain: max_hyps > 0, counts that fit an int
+        if (max_hyps[c] < 1) return jd_fail(JD_EINVAL, "jd_debug_hist_threshold: max_hyps[%lld] < 1", (long long)c);
+        int64_t total = 0;
+        for (int b = 0; b < nb; ++b) {
+            const int32_t v = bins[c * nb + b];
+            if (v < 0) return jd_fail(JD_EINVAL, "jd_debug_hist_threshold: negative count in case %lld", (long long)c);
+            total += v;
+        }
+        if (total > INT32_MAX) return jd_fail(JD_EINVAL, "jd_debug_hist_threshold: case %lld counts more than INT32_MAX", (long long)c);
+    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    int *db = nullptr, *dm = nullptr;
+    float *dy = nullptr;
+    const size_t nc = std::max<size_t>((size_t)n_cases, 1);
+    HIPCHK(hipMalloc(&db, nc * (size_t)nb * sizeof(int)));
+    HIPCHK(hipMalloc(&dm, nc * sizeof(int)));
+    HIPCHK(hipMalloc(&dy, nc * sizeof(float)));
+    HIPCHK(hipMemcpy(db, bins, (size_t)n_cases * (size_t)nb * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dm, max_hyps, (size_t)n_cases * sizeof(int), hipMemcpyHostToDevice));
+    if (n_cases) hipLaunchKernelGGL(jd_debug_hist_threshold_kernel, dim3((unsigned)n_cases), dim3(64), 0, 0, db, (int)nb, dm, (int)hist_min, dy);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dy, (size_t)n_cases * sizeof(float), hipMemcpyDeviceToHost));
+    (void)hipFree(db); (void)hipFree(dm); (void)hipFree(dy);
+    return JD_OK;
+}
+
 // Diagnostics: what part of a likelihood table does the search read?  (SURVEY.md 8d's Ug: the reference scores a tied
 // state only when a token that passed the emit threshold asks for it, WFSTDecoderLite.cpp:409-411; here every state of
 // every frame is scored.)  enable != 0: the slab's bitmap is cleared and every cell phase A adds to a token is marked from

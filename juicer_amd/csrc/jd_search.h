@@ -605,6 +605,26 @@ __device__ __forceinline__ void cluster_barrier(SearchShared &sh, StreamCtl &c, 
     __syncthreads();
 }
 
+// ---- Histogram::addScore (Histogram.cpp:64-100, binWidth 1): the score rounded half away from zero in double gives the bin
+// sc - hist_min; above(), the reference's fatal error, when sc > hist_max; nothing when sc < hist_min.  Both search kernels
+// call it (the outcomes as callbacks keep their code what it was when each wrote the comparisons out); jd_hist_bin is the
+// same decision as a value, which jd_debug_hist_bin runs on the device and as its host twin.
+template <class Above, class Add>
+__host__ __device__ __forceinline__ void jd_hist_add(float s, int hist_min, int hist_max, Above above, Add add)
+{
+    const double ds = (double)s;
+    const int sci = (s < 0.0f) ? (int)(ds - 0.5) : (int)(ds + 0.5);
+    if (sci > hist_max) above();
+    else if (sci >= hist_min) add(sci - hist_min);
+}
+#define JD_HIST_BELOW (-1)
+__host__ __device__ __forceinline__ int jd_hist_bin(float s, int hist_min, int hist_max)   // the bin, JD_HIST_BELOW or JD_EHIST
+{
+    int bin = JD_HIST_BELOW;
+    jd_hist_add(s, hist_min, hist_max, [&]() { bin = JD_EHIST; }, [&](int b) { bin = b; });
+    return bin;
+}
+
 // ---- Histogram::calcThresh (Histogram.cpp:134-158) over the bins of the previous frame, by one wave
 __device__ __forceinline__ float hist_threshold(const DecConst &C, const int *sh_hist, int lane)
 {
@@ -839,10 +859,8 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
                 nw[j].path = src.path;
                 live_mask |= 1 << j;
                 if (use_hist) {                                        // Histogram::addScore, Histogram.cpp:64-100
-                    const double ds = (double)nw[j].score;
-                    const int sci = (nw[j].score < 0.0f) ? (int)(ds - 0.5) : (int)(ds + 0.5);
-                    if (sci > C.hist_max) CS(&c.err[p], (int)JD_EHIST);
-                    else if (sci >= C.hist_min) atomicAdd(&sh.hist[sci - C.hist_min], 1);
+                    jd_hist_add(nw[j].score, C.hist_min, C.hist_max, [&]() __attribute__((always_inline)) { CS(&c.err[p], (int)JD_EHIST); },
+                                [&](int b) __attribute__((always_inline)) { atomicAdd(&sh.hist[b], 1); });
                 }
                 const unsigned so = f2o(nw[j].score);
                 mo = so > mo ? so : mo;

@@ -213,10 +213,8 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
                 nw[j].path = src.path;
                 live_mask |= 1 << j;
                 if (use_hist) {                                        // Histogram::addScore, Histogram.cpp:64-100
-                    const double ds = (double)nw[j].score;
-                    const int sci = (nw[j].score < 0.0f) ? (int)(ds - 0.5) : (int)(ds + 0.5);
-                    if (sci > C.hist_max) slot_err(sh, (int)JD_EHIST);
-                    else if (sci >= C.hist_min) atomicAdd(&hist[sci - C.hist_min], 1);
+                    jd_hist_add(nw[j].score, C.hist_min, C.hist_max, [&]() __attribute__((always_inline)) { slot_err(sh, (int)JD_EHIST); },
+                                [&](int b) __attribute__((always_inline)) { atomicAdd(&hist[b], 1); });
                 }
                 const unsigned so = f2o(nw[j].score);
                 mo = so > mo ? so : mo;

@@ -445,14 +445,22 @@ static Hist *hist_new(float minScore_, float maxScore_)
     return h;
 }
 static void hist_reset(Hist *h) { h->count = 0; memset(h->cnt, 0, sizeof(int) * (size_t)h->nBins); }
-/* Histogram::addScore :64-100 ; returns -5 on the reference's fatal error */
-static int hist_add(Hist *h, float score)
+/* the bin of Histogram::addScore :64-100: sc - minScore, -1 below minScore (not counted), -5 above maxScore */
+static int hist_bin(int minScore, int maxScore, float score)
 {
     int sc;
     if (score < 0.0) sc = (int)(score - 0.5); else sc = (int)(score + 0.5);
-    if (sc > h->maxScore) return -5;
-    if (sc < h->minScore) return 0;
-    h->cnt[sc - h->minScore]++;
+    if (sc > maxScore) return -5;
+    if (sc < minScore) return -1;
+    return sc - minScore;
+}
+/* Histogram::addScore :64-100 ; returns -5 on the reference's fatal error */
+static int hist_add(Hist *h, float score)
+{
+    const int bin = hist_bin(h->minScore, h->maxScore, score);
+    if (bin == -5) return -5;
+    if (bin < 0) return 0;
+    h->cnt[bin]++;
     h->count++;
     return 0;
 }
@@ -469,6 +477,7 @@ static float hist_thresh(const Hist *h, int maxN)
 }
 
 /* =================================================================== decoder */
+/* (the pruning sites of jo_dec_set_boundary: JO_SITE_* in juicer_oracle.h) */
 
 typedef struct { float score, ac, lm; int32_t path; } Tok;     /* Token, WFSTDecoderLite.h:58-63 */
 static const Tok NULLTOK = {LZ, LZ, LZ, -1};                    /* nullToken, .cpp:35 */
@@ -500,6 +509,13 @@ struct jo_dec {
     int32_t *jointCount; int64_t cap_joint;                  /* Path::jointCount */
     int32_t *p_label, *p_time;                               /* jo_partial_get view */
     int64_t tie_kind[4];                  /* bestFinal, entry token, HMM-internal, entry ties whose tokens differ */
+    /* boundary test aids (jo_dec_set_boundary): per pruning site, the comparisons whose two sides were equal; a mask of
+     * sites whose comparison is made inclusive (strict for the start beam); the probe log of one site: per comparison
+     * (frame, lhs, threshold, the best score the threshold was built from) */
+    int64_t site_hits[JO_N_SITES];
+    int flip_mask, probe_site;
+    float startBase, endBase;
+    float *probe; int64_t n_probe, cap_probe;
     /* HTKFlatModels cache state */
     int32_t *cacheT; float *cache; const float *const *currInput; int32_t currInputLen, amFrame;
     int err, started;
@@ -509,10 +525,38 @@ struct jo_dec {
     uint8_t *cells; int32_t cells_frames;   /* jo_set_cells: cells[frame * n_gmm + g] = 1 for every calcGMMOutput(g) call of that frame */
 };
 
+static void probe_push(jo_dec *d, float lhs, float th, float base)
+{
+    if (d->n_probe == d->cap_probe) {
+        int64_t cap = d->cap_probe ? 2 * d->cap_probe : 1024;
+        float *p = (float *)realloc(d->probe, (size_t)cap * 4 * sizeof(float));
+        if (!p) return;
+        d->probe = p; d->cap_probe = cap;
+    }
+    float *r = d->probe + 4 * d->n_probe++;
+    r[0] = (float)d->currFrame; r[1] = lhs; r[2] = th; r[3] = base;
+}
+/* lhs > th at a pruning site (lhs >= th when the site is flipped) */
+static inline int site_gt(jo_dec *d, int site, float lhs, float th, float base)
+{
+    if (lhs == th) ++d->site_hits[site];
+    if (d->probe_site == site) probe_push(d, lhs, th, base);
+    return (d->flip_mask >> site & 1) ? lhs >= th : lhs > th;
+}
+/* lhs < th (the start beam prunes below it; lhs <= th when flipped) */
+static inline int site_lt(jo_dec *d, int site, float lhs, float th, float base)
+{
+    if (lhs == th) ++d->site_hits[site];
+    if (d->probe_site == site) probe_push(d, lhs, th, base);
+    return (d->flip_mask >> site & 1) ? lhs <= th : lhs < th;
+}
+
+
 void jo_dec_destroy(jo_dec *d)
 {
     if (!d) return;
     if (d->hist) { free(d->hist->cnt); free(d->hist); }
+    free(d->probe);
     free(d->hook); free(d->insts); free(d->toks); free(d->paths); free(d->tokenBuf); free(d->pmark);
     free(d->cacheT); free(d->cache);
     free(d->r_label); free(d->r_time); free(d->r_score); free(d->r_ac); free(d->r_lm);
@@ -534,6 +578,7 @@ int jo_dec_create(jo_dec **out, const jo_net *net, const jo_am *am,
     d->net = net; d->am = am;
     d->startWin = start_beam; d->emitWin = main_beam; d->endWin = end_beam; d->wordWin = word_beam;
     d->maxHyps = max_hyps; d->fnBlock = block_size;
+    d->probe_site = -1;
     if (max_hyps > 0) {                       /* :76-82 */
         if (main_beam > 0.0) d->hist = hist_new((float)(-main_beam - 800.0), 200.0f);
         else d->hist = hist_new(-1000.0f, 200.0f);
@@ -681,7 +726,7 @@ static void propagate(jo_dec *d, Tok *tok, int32_t arc)
             Tok tmp = *tok;
             tmp.score += net->w[b];
             tmp.lm += net->w[b];
-            if (tmp.score > d->endTh) propagate(d, &tmp, b);
+            if (site_gt(d, JO_SITE_EPS, tmp.score, d->endTh, d->endBase)) propagate(d, &tmp, b);
         } else {
             int32_t inst = d->hook[b];                              /* :544-557 */
             if (inst < 0) inst = attach_inst(d, b);
@@ -714,8 +759,8 @@ static void propagate(jo_dec *d, Tok *tok, int32_t arc)
                 tmp.score = newScore;
                 tmp.ac += tee;
                 tmp.lm += net->w[b];
-                if (net->out[b] != 0) { if (newScore > d->wordTh) propagate(d, &tmp, b); }
-                else { if (newScore > d->endTh) propagate(d, &tmp, b); }
+                if (net->out[b] != 0) { if (site_gt(d, JO_SITE_TEE_WORD, newScore, d->wordTh, d->endBase)) propagate(d, &tmp, b); }
+                else { if (site_gt(d, JO_SITE_TEE_END, newScore, d->endTh, d->endBase)) propagate(d, &tmp, b); }
             }
         }
     }
@@ -739,6 +784,8 @@ int jo_init(jo_dec *d)
     d->startTh = d->endTh = d->wordTh = d->emitTh = LZ;             /* :197-200 */
     memset(&d->st, 0, sizeof d->st);
     memset(d->tie_kind, 0, sizeof d->tie_kind);
+    memset(d->site_hits, 0, sizeof d->site_hits);
+    d->n_probe = 0;
     d->nActiveInsts = d->nActiveEmitHyps = d->nActiveEndHyps = d->nEmitProc = d->nEndProc = 0;
     d->err = 0; d->started = 1; d->amFrame = -1;
     d->n_partial = 0;                                               /* :179-181 */
@@ -775,7 +822,7 @@ static void hmm_internal(jo_dec *d, int32_t ii)
             } else if (tmpScore == res->score && tmpScore > LZ) ++d->tie_kind[2];
         }
         res->score -= d->normaliseScore;
-        if (res->score > d->emitTh) {
+        if (site_gt(d, JO_SITE_EMIT, res->score, d->emitTh, 0.0f)) {
             ++d->nEmitProc;
             float outp = am_calc_gmm(d, am->hmm_gmm[(size_t)inst->hmm * maxN + j]);
             res->score += outp;
@@ -818,7 +865,7 @@ static void do_internal(jo_dec *d)
     int32_t prev = -1, inst = d->active;
     while (inst >= 0) {
         Tok *entry = &d->toks[(size_t)inst * d->maxN];
-        if (entry->score > LZ && entry->score < d->startTh) {       /* :915-918 */
+        if (entry->score > LZ && site_lt(d, JO_SITE_START, entry->score, d->startTh, d->startBase)) {   /* :915-918 */
             *entry = NULLTOK;
             --d->insts[inst].nact;
         }
@@ -843,9 +890,9 @@ static void do_external(jo_dec *d)
         Tok exit_tok = d->toks[(size_t)inst * d->maxN + n - 1];     /* copy: pools may move */
         if (exit_tok.score > LZ) {
             if (d->net->out[arc] == 0) {
-                if (exit_tok.score > d->endTh) { ++d->nEndProc; propagate(d, &exit_tok, arc); }
+                if (site_gt(d, JO_SITE_END, exit_tok.score, d->endTh, d->endBase)) { ++d->nEndProc; propagate(d, &exit_tok, arc); }
             } else {
-                if (exit_tok.score > d->wordTh) { ++d->nEndProc; propagate(d, &exit_tok, arc); }
+                if (site_gt(d, JO_SITE_WORD, exit_tok.score, d->wordTh, d->endBase)) { ++d->nEndProc; propagate(d, &exit_tok, arc); }
             }
             d->toks[(size_t)inst * d->maxN + n - 1] = NULLTOK;      /* :964 */
             if (--d->insts[inst].nact == 0) inst = return_inst(d, inst, prev);
@@ -958,8 +1005,10 @@ int jo_process_frame(jo_dec *d, const float *const *rows, int32_t frame, int32_t
         hist_reset(d->hist);
     } else d->emitTh = (d->emitWin > 0.0 ? -d->emitWin : LZ);      /* :331 */
     d->startTh = (d->startWin > 0.0 ? (d->bestEmitScore - d->startWin) : LZ);   /* :337 */
+    d->startBase = d->bestEmitScore;
     do_internal(d);                                                 /* :341 */
     d->endTh = (d->endWin > 0.0 ? (d->bestEmitScore - d->endWin) : LZ);        /* :349 */
+    d->endBase = d->bestEmitScore;
     d->wordTh = (d->wordWin > 0.0 ? (d->bestEmitScore - d->wordWin) : LZ);     /* :350 */
     do_external(d);                                                 /* :353 */
     /* path collection :355-370.  collectPaths (:699-747) frees the Path objects no token of an active instance
@@ -1294,6 +1343,27 @@ int jo_dec_set_tie_mode(jo_dec *d, int mode)
     return 0;
 }
 
+/* Test aid for the pruning comparisons at equality: flip_mask (bit JO_SITE_*) makes those sites inclusive, probe_site
+ * (-1: none) logs every comparison of one site.  Counters and log restart at every jo_init. */
+int jo_dec_set_boundary(jo_dec *d, int flip_mask, int probe_site)
+{
+    if (!d || flip_mask < 0 || flip_mask >= (1 << JO_N_SITES) || probe_site < -1 || probe_site >= JO_N_SITES) return -1;
+    d->flip_mask = flip_mask; d->probe_site = probe_site;
+    return 0;
+}
+int jo_dec_site_hits(const jo_dec *d, int64_t out[JO_N_SITES])
+{
+    if (!d || !out) return -1;
+    memcpy(out, d->site_hits, sizeof d->site_hits);
+    return 0;
+}
+int jo_dec_probe(const jo_dec *d, const float **rows, int64_t *n)
+{
+    if (!d || !rows || !n) return -1;
+    *rows = d->probe; *n = d->n_probe;
+    return 0;
+}
+
 /* the host libm's expf, elementwise (what HTKFlatModels::logAdd calls on a float, :266-293) */
 int jo_expf_array(const float *x, int64_t n, float *out)
 {
@@ -1314,5 +1384,33 @@ int jo_log1pe_array(const float *d, int64_t n, double *out)
 {
     if (!d || !out || n < 0) return -1;
     for (int64_t i = 0; i < n; ++i) out[i] = log(1.0 + (double)expf(d[i]));
+    return 0;
+}
+
+/* Histogram::addScore's bin (:64-100) elementwise: out[i] = the bin of s[i], -1 below hist_min, -5 above hist_max */
+int jo_hist_bin_array(const float *s, int64_t n, int32_t hist_min, int32_t hist_max, int32_t *out)
+{
+    if (!s || !out || n < 0 || hist_min > hist_max) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = hist_bin(hist_min, hist_max, s[i]);
+    return 0;
+}
+
+/* Histogram::calcThresh (:134-158) per case: bins[c * nb .. c * nb + nb) are the counts of bins hist_min .. hist_min + nb - 1 */
+int jo_hist_thresh_array(const int32_t *bins, int64_t n_cases, int32_t nb, const int32_t *max_hyps, int32_t hist_min, float *out)
+{
+    if (!bins || !max_hyps || !out || n_cases < 0 || nb < 1) return -1;
+    Hist h;
+    h.nBins = nb; h.minScore = hist_min; h.maxScore = hist_min + nb - 1;
+    for (int64_t c = 0; c < n_cases; ++c) {
+        h.cnt = (int *)(bins + c * nb);
+        int64_t count = 0;
+        for (int b = 0; b < nb; ++b) {
+            if (bins[c * nb + b] < 0) return -1;
+            count += bins[c * nb + b];
+        }
+        if (count > INT32_MAX) return -1;
+        h.count = (int)count;
+        out[c] = hist_thresh(&h, max_hyps[c]);
+    }
     return 0;
 }

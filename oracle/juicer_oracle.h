@@ -119,12 +119,26 @@ int jo_tie_breakdown(const jo_dec *d, int64_t out[4]);
 /* test aid: 0 = reference rule (first visited token keeps an equal-score recombination),
  * 1 = last visited wins.  jo_stats.ties counts the order-dependent ties only ([0] + [3]). */
 int jo_dec_set_tie_mode(jo_dec *d, int mode);
+/* test aid for the pruning comparisons at equality (single-thread decoder): sites are the start beam (entry token < startTh,
+ * :915-918), the emit beam (> emitTh, :409), exit tokens (> endTh / > wordTh, :937-982), epsilon closures (> endTh, :533-540) and
+ * tee closures (> wordTh / > endTh, :584-600).  jo_dec_set_boundary: bit s of flip_mask makes site s inclusive (the start beam
+ * strict); probe_site logs every comparison of one site (-1: none).  jo_dec_site_hits: per site, the comparisons of the last
+ * utterance whose two sides were equal.  jo_dec_probe: the log, 4 floats per comparison (frame, lhs, threshold, the best
+ * score the threshold was built from; 0 for the emit beam, whose threshold is -mainBeam).  All off by default. */
+enum { JO_SITE_START, JO_SITE_EMIT, JO_SITE_END, JO_SITE_WORD, JO_SITE_EPS, JO_SITE_TEE_WORD, JO_SITE_TEE_END, JO_N_SITES };
+int jo_dec_set_boundary(jo_dec *d, int flip_mask, int probe_site);
+int jo_dec_site_hits(const jo_dec *d, int64_t out[JO_N_SITES]);
+int jo_dec_probe(const jo_dec *d, const float **rows, int64_t *n);
 
 /* host libm expf, elementwise */
 int jo_expf_array(const float *x, int64_t n, float *out);
 /* HTKFlatModels::logAdd elementwise, and the double log(1.0 + (double)expf(d)) inside it */
 int jo_log_add_array(const float *x, const float *y, int64_t n, float *out);
 int jo_log1pe_array(const float *d, int64_t n, double *out);
+/* Histogram::addScore's bin elementwise (-1: below hist_min, -5: above hist_max), and Histogram::calcThresh per case over
+ * bins[c * nb .. c * nb + nb) (the counts of bins hist_min ..) with max_hyps[c] */
+int jo_hist_bin_array(const float *s, int64_t n, int32_t hist_min, int32_t hist_max, int32_t *out);
+int jo_hist_thresh_array(const int32_t *bins, int64_t n_cases, int32_t nb, const int32_t *max_hyps, int32_t hist_min, float *out);
 
 const char *jo_last_error(void);
 

@@ -224,6 +224,29 @@ def log1pe_array(d):
     return out
 
 
+def hist_bin_array(s, hist_min: int, hist_max: int):
+    """Histogram::addScore's bin (:64-100) elementwise: the bin index, -1 below hist_min, -5 (fatal) above hist_max"""
+    s = _f32(s)
+    out = np.empty(s.shape[0], np.int32)
+    _check(lib().jo_hist_bin_array(_p(s, C.c_float), C.c_int64(s.shape[0]), C.c_int32(hist_min), C.c_int32(hist_max),
+                                   _p(out, C.c_int32)))
+    return out
+
+
+def hist_thresh_array(bins, max_hyps, hist_min: int):
+    """Histogram::calcThresh (:134-158) per case: bins is n_cases x nb (the counts of bins hist_min ..), max_hyps n_cases"""
+    bins, max_hyps = _i32(bins), _i32(max_hyps)
+    assert bins.ndim == 2 and max_hyps.shape == (bins.shape[0],)
+    out = np.empty(bins.shape[0], np.float32)
+    _check(lib().jo_hist_thresh_array(_p(bins, C.c_int32), C.c_int64(bins.shape[0]), C.c_int32(bins.shape[1]),
+                                      _p(max_hyps, C.c_int32), C.c_int32(hist_min), _p(out, C.c_float)))
+    return out
+
+
+# the pruning sites of jo_dec_set_boundary, in bit order
+SITES = ("start", "emit", "end", "word", "eps", "tee_word", "tee_end")
+
+
 class OracleDecoder:
     """Restated WFSTDecoderLite; decode() follows DecoderSingleTest's frame loop."""
 
@@ -235,6 +258,23 @@ class OracleDecoder:
         _check(L.jo_dec_create(C.byref(self.h), net.h, am.h, C.c_float(start_beam), C.c_float(main_beam),
                                C.c_float(end_beam), C.c_float(word_beam), C.c_int32(max_hyps),
                                C.c_int32(block_size)))
+
+    def set_boundary(self, flip_mask: int = 0, probe_site: int = -1):
+        """test aid (jo_dec_set_boundary): make the sites in flip_mask (bits of SITES) inclusive, log one site's comparisons"""
+        _check(lib().jo_dec_set_boundary(self.h, C.c_int(flip_mask), C.c_int(probe_site)))
+
+    def site_hits(self):
+        """{site: comparisons of the last utterance whose two sides were equal}"""
+        out = (C.c_int64 * len(SITES))()
+        _check(lib().jo_dec_site_hits(self.h, out))
+        return {s: int(out[i]) for i, s in enumerate(SITES)}
+
+    def probe(self):
+        """the probe log of the last utterance: n x 4 (frame, lhs, threshold, the best score it was built from)"""
+        rows = C.POINTER(C.c_float)()
+        n = C.c_int64(0)
+        _check(lib().jo_dec_probe(self.h, C.byref(rows), C.byref(n)))
+        return np.ctypeslib.as_array(rows, shape=(n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
 
     def decode(self, feats, trace: Optional[np.ndarray] = None, tie_mode: int = 0, threading: bool = False) -> OracleHyp:
         """threading=True: the reference's two-thread organisation (WFSTDecoderLiteThreading +
