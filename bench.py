@@ -13,8 +13,7 @@ hands back ITS batch's 64 results, decoded in full.  The announced
 batch is the same synthetic batch again, scored from its features every time: K timed steps hold K scorings and K batches' worth of
 search.  `value` = the stream-frames the slots REALLY advanced between the two brackets (`jd_dec_pipeline_stats`) / the bracketed
 time - a batch handed back inside the region was partly searched before it, batches announced inside it are partly searched behind
-it.  What ONE batch costs a caller that does not announce that far ahead is printed beside it (`single_batch`: nothing announced /
-one batch announced), measured behind the timed region.  --pipeline-depth 0: two batches in flight, one k_search launch per step.
+it.  --pipeline-depth 0: two batches in flight, one k_search launch per step.
 
 N > 1: one rank per GPU, utterances sharded across ranks, no data-path collective, every rank on the same path as N = 1.  A
 collective's kernels must not be queued on a device whose search kernel stays, so the 1-best records of the K timed steps travel in
@@ -28,11 +27,17 @@ The timed region is bracketed by jd_dec_quiesce (the resident kernel lets its co
 synchronisation waits for every kernel), barrier and torch.cuda.synchronize() on both sides; the kernel comes back with the first
 timed step, inside the brackets.
 
-After the timed region rank 0 of a 1-GPU run also times the other single-GPU workloads of BASELINE.json and reports them under
-"legs" (each with its own roofline and a CPU-oracle sample): configs[1] + maxHyps 6000, configs[1] with two batches in flight,
-configs[2]'s 512-utterance batch on one GPU (one launch of the slot kernel per pass), configs[1]'s graph with HMMs of 1-6 emitting
-states, the north_star target (14 M-arc graph, beam 200), configs[3] (~48M-arc trigram-shaped graph, beam 300), configs[4] (C.L and G
-composed on the device).  --no-extra-legs skips them.
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line (`roofline` there: what the timed steps' own counters give).  Everything else is measured and checked behind the timed region
+with --full only:
+  * what ONE batch costs a caller that does not announce that far ahead (`single_batch`: nothing announced / one batch announced),
+    the scoring kernel's own roofline (`roofline.gmm`) and the batch in the serial order (`roofline.serial_order`), every rank;
+  * rank 0 of a 1-GPU run: the CPU baselines and the WER of the step against the CPU oracle (`cpu_baseline`, `wer_vs_oracle`;
+    --no-cpu-baseline skips them), and the other single-GPU workloads of BASELINE.json under "legs" (each with its own roofline and
+    a CPU-oracle sample): configs[1] + maxHyps 6000, configs[1] with two batches in flight, configs[2]'s 512-utterance batch on one
+    GPU (one launch of the slot kernel per pass), configs[1]'s graph with HMMs of 1-6 emitting states, the north_star target (14 M-arc
+    graph, beam 200), configs[3] (~48M-arc trigram-shaped graph, beam 300), configs[4] (C.L and G composed on the device);
+    --no-extra-legs skips them.
 
 Prints ONE JSON line on rank 0.
 """
@@ -481,9 +486,12 @@ def main():
     ap.add_argument("--arcs", type=int, default=1_000_000)
     ap.add_argument("--beam", type=float, default=150.0)
     ap.add_argument("--max-hyps", type=int, default=0)
-    ap.add_argument("--cpu-sample-utts", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what the headline does not need: single-batch figures, the scoring "
+                         "kernel's roofline, the CPU baselines and the WER against the CPU oracle, the other workloads (legs)")
+    ap.add_argument("--cpu-sample-utts", type=int, default=12, help="with --full: utterances of the one-core CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines, no WER against the CPU oracle")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: not the other workloads")
     ap.add_argument("--no-score-ahead", action="store_true",
                     help="score every batch's table right before its search (serial) instead of beside the previous batch's search")
     ap.add_argument("--no-search-ahead", action="store_true",
@@ -763,36 +771,39 @@ def main():
     # that is what its slots report having advanced (jd_dec_pipeline_stats: a batch handed back inside the region was partly
     # searched before it, batches announced inside it are partly searched behind it); with one launch per step it is K batches
     frames_timed = (ps1["frames_searched"] - ps0["frames_searched"]) if depth else frames_local * args.steps
-    # (outside the timed region) what a caller gets who cannot announce that far ahead: ONE batch of 64 at a time.
-    #   serial order:  nothing announced - the batch's table is scored, then it is searched (re-planned at will)
-    #   one ahead:     the next batch announced before each decode - its table is scored beside this batch's search
+    # (outside the timed region, every run) the decoder leaves the pipeline and drops what is still announced: it ends in the same
+    # state whether or not the figures below are taken
     dec.set_pipeline(capi.FLOW_SERIAL)
     dec.prefetch_scores(0, None)
-    dec.decode_batch_device(d_feats.data_ptr(), offs, stream)          # (a launch of this shape has been planned once)
-    t1 = time.perf_counter()
-    dec.decode_batch_device(d_feats.data_ptr(), offs, stream)
-    torch.cuda.synchronize()
-    serial_ms = (time.perf_counter() - t1) * 1e3
-    tm_serial = dec.last_timing()
-    one_ahead = []
-    dec.prefetch_scores(d_feats.data_ptr(), offs, stream)
-    for i in range(5):
-        torch.cuda.synchronize()
+    if args.full:
+        # (outside the timed region) what a caller gets who cannot announce that far ahead: ONE batch of 64 at a time.
+        #   serial order:  nothing announced - the batch's table is scored, then it is searched (re-planned at will)
+        #   one ahead:     the next batch announced before each decode - its table is scored beside this batch's search
+        dec.decode_batch_device(d_feats.data_ptr(), offs, stream)          # (a launch of this shape has been planned once)
         t1 = time.perf_counter()
-        dec.prefetch_scores(d_feats.data_ptr(), offs, stream)
         dec.decode_batch_device(d_feats.data_ptr(), offs, stream)
         torch.cuda.synchronize()
-        if i >= 2:
-            one_ahead.append(((time.perf_counter() - t1) * 1e3, dec.last_timing()))
-    one_ahead.sort(key=lambda r: r[0])
-    one_ahead_ms, tm_one = one_ahead[len(one_ahead) // 2]
-    dec.prefetch_scores(0, None)
-    # (outside the timed region) which part of the likelihood table does the search read?  SURVEY.md 8d's Ug: the reference
-    # scores a tied state only when a token that passed the emit threshold asks for it; every state of every frame is scored here
-    dec.debug_cells(True)
-    dec.decode_batch_device(d_feats.data_ptr(), offs, stream)
-    cells_read, cells_total = dec.debug_cells(False)
-    mark("single-batch figures, cells read")
+        serial_ms = (time.perf_counter() - t1) * 1e3
+        tm_serial = dec.last_timing()
+        one_ahead = []
+        dec.prefetch_scores(d_feats.data_ptr(), offs, stream)
+        for i in range(5):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            dec.prefetch_scores(d_feats.data_ptr(), offs, stream)
+            dec.decode_batch_device(d_feats.data_ptr(), offs, stream)
+            torch.cuda.synchronize()
+            if i >= 2:
+                one_ahead.append(((time.perf_counter() - t1) * 1e3, dec.last_timing()))
+        one_ahead.sort(key=lambda r: r[0])
+        one_ahead_ms, tm_one = one_ahead[len(one_ahead) // 2]
+        dec.prefetch_scores(0, None)
+        # (outside the timed region) which part of the likelihood table does the search read?  SURVEY.md 8d's Ug: the reference
+        # scores a tied state only when a token that passed the emit threshold asks for it; every state of every frame is scored here
+        dec.debug_cells(True)
+        dec.decode_batch_device(d_feats.data_ptr(), offs, stream)
+        cells_read, cells_total = dec.debug_cells(False)
+        mark("single-batch figures, cells read")
     if world > 1:
         t = torch.tensor([elapsed, float(frames_local), float(frames_timed)], dtype=torch.float64, device=dev)
         tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -837,42 +848,43 @@ def main():
         roofline["launch"] = "ONE launch spans the timed region; a batch's share = region x batch frames / frames the slots advanced"
         roofline["l2_requests"] = slot_l2_requests(fps) if default_cfg else None
     roofline["frac_is"] = "SURVEY 8(d) bytes of the REFERENCE's work / time; frac_design: bytes this design requests; frac_measured: counted HBM bytes"
-    gmm_flops = frames_local * G * M * (3.0 * D + 4.0)
-    gmm_bytes = G * M * (2 * D + 1) * 4.0 + frames_local * D * 4.0 / max(1, tm["gmm_launches"])
     roofline["search_ms_per_step"] = round(step_tm["search_ms"], 3)
     # one batch's counters per stream-frame: the reference's figures (tot_insts_in .. tot_paths) and what the kernels took up (tot_recs_read ..)
     roofline["per_stream_frame"] = {k: round(v / max(1, frames_local), 1) for k, v in st.items() if k.startswith("tot_")}
-    # the companion kernel is VALU-bound: per (frame pair, mixture) 4 packed fp32 instructions per dimension
-    # + ~116 for the two logAdd steps, 4 cycles each on 1024 SIMDs; fast scoring: 2 packed FMAs per dimension + ~24
-    per_mix = (4.0 * D + 116.0) if args.scoring == "exact" else (2.0 * D + 24.0)
-    gmm_valu_ms = (frames_local / 128.0) * G * M * per_mix * 4.0 / 1024.0 / 2.4e9 * 1e3
-    gmm_ms = tm_serial["gmm_ms"]                                   # the kernel on its own (the serial step behind the timed region)
-    n_ahead = acc["prefetched"]
-    roofline["gmm"] = {"kernel": ("jd_gmm_kernel39" if args.scoring == "exact" else "jd_gmm_fast39") if D == 39 else "jd_gmm_kernel", "bound": "valu",
-                       "scoring": args.scoring,
-                       "ms_per_step": round(gmm_ms, 3),
-                       "valu_bound_ms": round(gmm_valu_ms, 3),
-                       "frac": round(gmm_valu_ms / max(gmm_ms, 1e-9), 4),
-                       "valu_tflops": round(gmm_flops / max(gmm_ms, 1e-9) / 1e9, 3),
-                       "algorithmic_bytes_per_launch": round(gmm_bytes, 1),
-                       "search_waited_ms_per_step": round(acc["gmm_wait_ms"] / steps, 3),
-                       "scored_ahead_steps": int(n_ahead),
-                       "cells_scored": int(cells_total), "cells_read_by_the_search": int(cells_read),
-                       "cells_read_frac": round(cells_read / max(cells_total, 1), 4),
-                       "span_beside_search_ms": round(acc["gmm_ms"] / steps, 3) if n_ahead else None,
-                       "serial_order_ms_per_step": round(serial_ms, 3),
-                       "serial_order_search_ms": round(tm_serial["search_ms"], 3)}
+    if args.full:                                                  # (the scoring kernel's and the serial order's figures take runs of their own)
+        gmm_flops = frames_local * G * M * (3.0 * D + 4.0)
+        gmm_bytes = G * M * (2 * D + 1) * 4.0 + frames_local * D * 4.0 / max(1, tm["gmm_launches"])
+        # the companion kernel is VALU-bound: per (frame pair, mixture) 4 packed fp32 instructions per dimension
+        # + ~116 for the two logAdd steps, 4 cycles each on 1024 SIMDs; fast scoring: 2 packed FMAs per dimension + ~24
+        per_mix = (4.0 * D + 116.0) if args.scoring == "exact" else (2.0 * D + 24.0)
+        gmm_valu_ms = (frames_local / 128.0) * G * M * per_mix * 4.0 / 1024.0 / 2.4e9 * 1e3
+        gmm_ms = tm_serial["gmm_ms"]                                   # the kernel on its own (the serial step behind the timed region)
+        n_ahead = acc["prefetched"]
+        roofline["gmm"] = {"kernel": ("jd_gmm_kernel39" if args.scoring == "exact" else "jd_gmm_fast39") if D == 39 else "jd_gmm_kernel", "bound": "valu",
+                           "scoring": args.scoring,
+                           "ms_per_step": round(gmm_ms, 3),
+                           "valu_bound_ms": round(gmm_valu_ms, 3),
+                           "frac": round(gmm_valu_ms / max(gmm_ms, 1e-9), 4),
+                           "valu_tflops": round(gmm_flops / max(gmm_ms, 1e-9) / 1e9, 3),
+                           "algorithmic_bytes_per_launch": round(gmm_bytes, 1),
+                           "search_waited_ms_per_step": round(acc["gmm_wait_ms"] / steps, 3),
+                           "scored_ahead_steps": int(n_ahead),
+                           "cells_scored": int(cells_total), "cells_read_by_the_search": int(cells_read),
+                           "cells_read_frac": round(cells_read / max(cells_total, 1), 4),
+                           "span_beside_search_ms": round(acc["gmm_ms"] / steps, 3) if n_ahead else None,
+                           "serial_order_ms_per_step": round(serial_ms, 3),
+                           "serial_order_search_ms": round(tm_serial["search_ms"], 3)}
 
-    # the same batch in the serial order (scored, then searched with re-planning at will): the kernel's own best figure
-    ser = roofline_of(st, MN, tm_serial, leg_traffic("c2", max(1, tm_serial["search_launches"])) if default_cfg else None)
-    roofline["serial_order"] = {"ms_per_step": round(serial_ms, 3), "search_ms": round(tm_serial["search_ms"], 3),
-                                "launches": tm_serial["search_launches"], "achieved": ser["achieved"], "frac": ser["frac"],
-                                "frac_measured": ser["frac_measured"]}
+        # the same batch in the serial order (scored, then searched with re-planning at will): the kernel's own best figure
+        ser = roofline_of(st, MN, tm_serial, leg_traffic("c2", max(1, tm_serial["search_launches"])) if default_cfg else None)
+        roofline["serial_order"] = {"ms_per_step": round(serial_ms, 3), "search_ms": round(tm_serial["search_ms"], 3),
+                                    "launches": tm_serial["search_launches"], "achieved": ser["achieved"], "frac": ser["frac"],
+                                    "frac_measured": ser["frac_measured"]}
 
     # ---- CPU baseline: the oracle (a port of the reference algorithm) on a bounded sample, one core
     cpu = None
     wer = None
-    if not args.no_cpu_baseline and world == 1:                   # (rank 0 at N = 1 only: the other ranks would wait for it)
+    if args.full and not args.no_cpu_baseline and world == 1:     # (rank 0 at N = 1 only: the other ranks would wait for it)
         from oracle.oracle import OracleAM, OracleDecoder, OracleNet
         ns = min(args.cpu_sample_utts, U)
         od = OracleDecoder(OracleNet(net), OracleAM(am), main_beam=args.beam, max_hyps=args.max_hyps)
@@ -914,13 +926,18 @@ def main():
         cpu["identical_1best_whole_step"] = "%d/%d" % (wer["identical_1best"], wer["utterances"])
         cpu["identical_scores_bitwise_whole_step"] = "%d/%d" % (wer["identical_scores_bitwise"], wer["utterances"])
 
-    # what ONE batch of 64 costs a caller that does not announce nine batches ahead - beside `value`, not inside it
-    one = roofline_of(st, MN, tm_one, leg_traffic("c2", max(1, tm_one["search_launches"])) if default_cfg else None)
-    single_batch = {"serial_order": {"ms": round(serial_ms, 3), "frames_per_s": round(frames_local / serial_ms * 1e3, 1), "frac": ser["frac"],
-                                     "what": "nothing announced: the batch's table is scored, then it is searched"},
-                    "one_ahead": {"ms": round(one_ahead_ms, 3), "frames_per_s": round(frames_local / one_ahead_ms * 1e3, 1), "frac": one["frac"],
-                                  "what": "the next batch announced before each decode (jd_dec_prefetch_scores); one batch on the chip at a time"},
-                    "note": "measured behind the timed region on rank 0 (one pass / median of 3); not part of `value`"}
+    single_batch, single_cfg = None, {}
+    if args.full:
+        # what ONE batch of 64 costs a caller that does not announce nine batches ahead - beside `value`, not inside it
+        one = roofline_of(st, MN, tm_one, leg_traffic("c2", max(1, tm_one["search_launches"])) if default_cfg else None)
+        single_batch = {"serial_order": {"ms": round(serial_ms, 3), "frames_per_s": round(frames_local / serial_ms * 1e3, 1), "frac": ser["frac"],
+                                         "what": "nothing announced: the batch's table is scored, then it is searched"},
+                        "one_ahead": {"ms": round(one_ahead_ms, 3), "frames_per_s": round(frames_local / one_ahead_ms * 1e3, 1), "frac": one["frac"],
+                                      "what": "the next batch announced before each decode (jd_dec_prefetch_scores); one batch on the chip at a time"},
+                        "note": "measured behind the timed region on rank 0 (one pass / median of 3); not part of `value`"}
+        # (ONE batch at a time, a caller that cannot announce nine batches ahead: measured behind the timed region)
+        single_cfg = {"single_batch_serial_ms": round(serial_ms, 3), "single_batch_serial_fps": round(frames_local / serial_ms * 1e3, 1),
+                      "single_batch_one_ahead_ms": round(one_ahead_ms, 3), "single_batch_one_ahead_fps": round(frames_local / one_ahead_ms * 1e3, 1)}
     name = "configs[1]" if default_cfg else "configs[1]-shaped (non-default size / pruning / scoring)"
     # The line: what a reader needs first comes first, and every string inside config / roofline / cpu_baseline stays under 128
     # characters (the driver's record keeps those objects and cuts longer strings)
@@ -941,9 +958,7 @@ def main():
                       "pipeline_error": pipeline_error[:120] if pipeline_error else None,
                       "gather": None if world == 1 else ("one all_gather per step" if per_step_gather else
                                                          "ONE all_gather of the %d steps' records, inside the timed region, behind jd_dec_quiesce" % steps),
-                      # ONE batch at a time (a caller that cannot announce nine batches ahead): measured behind the timed region
-                      "single_batch_serial_ms": round(serial_ms, 3), "single_batch_serial_fps": round(frames_local / serial_ms * 1e3, 1),
-                      "single_batch_one_ahead_ms": round(one_ahead_ms, 3), "single_batch_one_ahead_fps": round(frames_local / one_ahead_ms * 1e3, 1),
+                      **single_cfg,
                       "predicted_rank_ms": predicted_rank_ms if strong else None,
                       "search_ahead_frames_per_step": int(acc["ahead_frames"] // max(steps, 1)),
                       "streams_per_gpu": dec.max_streams},
@@ -955,7 +970,7 @@ def main():
            "ms_each_step": each if steps <= 32 else None}
 
     # ---- the other single-GPU workloads of BASELINE.json (not part of `value`)
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         dec.close()
         del d_feats
         torch.cuda.empty_cache()

@@ -1,6 +1,6 @@
 """N>1 path on real hardware: two ranks (one process each, torch.distributed) drive the HIP decoder
 on the one GPU of the box; their gathered 1-best records equal a single-rank decode.  Also the
-bench's own rank spawning (`python bench.py --gpus 2` without torchrun)."""
+bench's own rank spawning (`python bench.py --gpus 2` without torchrun), and what its plain and --full runs report."""
 import json
 import os
 import socket
@@ -69,12 +69,12 @@ def test_bench_spawns_its_own_ranks(built):
     gloo, JD_BENCH_SHARE_GPU=1 - the numbers are meaningless, the path is what is tested).  Several ranks run the
     headline's own path: batches through the resident slot kernel, nine announced ahead, the steps' 1-best records in ONE
     all_gather behind jd_dec_quiesce at the end of the timed region; --gather-every 1 keeps a collective per step and
-    two batches in flight."""
+    two batches in flight.  --full: every rank also takes the single-batch figures behind the timed region."""
     _free_this_process()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", JD_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--utts-per-gpu", "6",
-            "--arcs", "60000", "--no-cpu-baseline", "--no-extra-legs", "--pipeline-slots", "8"]
+            "--arcs", "60000", "--full", "--no-cpu-baseline", "--no-extra-legs", "--pipeline-slots", "8"]
     out = _run(base, env, 400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -88,6 +88,32 @@ def test_bench_spawns_its_own_ranks(built):
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["config"]["pipeline"] is None and d["config"]["batches_in_flight"] == 2 and d["config"]["gathered_hyps"] == 12
     assert d["frames_timed"] == 3 * d["config"]["frames_per_step"]
+
+
+def test_bench_plain_run_is_lean_and_full_run_checks(built):
+    """`python bench.py --gpus 1` (toy size): a plain run does only what the headline needs - no single-batch figures, no scoring
+    kernel roofline, no CPU baselines, no legs; --full takes them behind the timed region, and the step's 1-best records are the CPU
+    oracle's."""
+    _free_this_process()
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--utts-per-gpu", "6",
+            "--arcs", "60000", "--pipeline-slots", "8"]
+    out = _run(base, env, 300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["config"]["pipeline_error"] is None and d["roofline"]["kernel"] == "k_slot" and d["frames_timed"] > 0
+    assert d["cpu_baseline"] is None and d["wer_vs_oracle"] is None and d["single_batch"] is None and "legs" not in d
+    assert "gmm" not in d["roofline"] and "serial_order" not in d["roofline"] and "single_batch_serial_ms" not in d["config"]
+    out = _run(base + ["--full", "--no-extra-legs", "--cpu-sample-utts", "3"], env, 300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["value"] > 0 and "legs" not in d
+    assert d["single_batch"]["serial_order"]["ms"] > 0 and d["config"]["single_batch_one_ahead_ms"] > 0
+    assert d["roofline"]["gmm"]["ms_per_step"] > 0 and d["roofline"]["serial_order"]["launches"] > 0
+    assert d["cpu_baseline"]["identical_1best"] == "3/3", d["cpu_baseline"]
+    assert d["wer_vs_oracle"]["utterances"] == 6 and d["wer_vs_oracle"]["identical_1best"] == 6, d["wer_vs_oracle"]
 
 
 def test_bench_strong_scaling_mode(built):
@@ -120,6 +146,7 @@ def test_bench_four_ranks_share_one_gpu(built):
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 4 and d["config"]["gathered_hyps"] == 16 and d["value"] > 0
     assert d["config"]["pipeline_error"] is None and d["config"]["batches_in_flight"] == 10 and d["roofline"]["kernel"] == "k_slot", d["config"]
+    assert d["single_batch"] is None and "gmm" not in d["roofline"]            # (a plain run: the headline only)
     assert "wall-clock budget" in out.stderr                    # (what the run's time went to, for the driver's limit)
 
 

@@ -3,7 +3,7 @@
 #   1. rocprofv3 --kernel-trace --stats of the bench command itself (two batches in flight: three warm-up steps fill the pipeline)
 #   2. the SQ / instruction-mix PMC passes of the same command (each in its own run, --kernel-trace only)
 #   3. tools/leg_pmc.sh <leg>: FETCH_SIZE / WRITE_SIZE passes of every workload -> calibrated traffic (+ the hash of the kernel sources)
-#   4. python bench.py: the full line with its legs, reading the traffic files just written
+#   4. python bench.py --full: the full line with its legs, reading the traffic files just written
 # Results land in gpurun_out/r04/ with the names they get in profiles/.
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
@@ -33,6 +33,6 @@ for l in ${LEGS:-c2 hyps c512 north c3 clg}; do
     cp gpurun_out/prof_$l/leg_traffic.json "profiles/r04_${l}_traffic.json"     # (on the box: bench.py reads them below)
     cp gpurun_out/prof_$l/pmc_summary.json "$R/r04_${l}_leg_pmc_summary.json"
 done
-python bench.py > "$R/r04_bench_full_with_legs.json" 2> "$R/bench.err"
+python bench.py --full > "$R/r04_bench_full_with_legs.json" 2> "$R/bench.err"
 tail -c 400 "$R/r04_bench_full_with_legs.json"
 ls -la "$R"

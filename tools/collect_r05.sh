@@ -4,7 +4,7 @@
 #   2. SQ / instruction-mix / L1 / L2 PMC passes of the slot kernel as a plain launch (k_slot_batch over configs[2]'s 512 utterances:
 #      under --pmc kernels run one after the other, and the pipeline's k_slot waits for the kernels beside it)
 #   3. tools/leg_pmc.sh <leg>: FETCH_SIZE / WRITE_SIZE passes of every workload -> calibrated traffic (+ the hash of the kernel sources)
-#   4. python bench.py: the full line with its legs, reading the traffic files just written
+#   4. python bench.py --full: the full line with its legs, reading the traffic files just written
 # Results land in gpurun_out/r05/ with the names they get in profiles/.
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
@@ -35,6 +35,6 @@ for l in ${LEGS:-c512slot c2 hyps north c3 clg}; do
     cp gpurun_out/prof_$l/leg_traffic.json "profiles/r05_${l}_traffic.json"     # (on the box: bench.py reads them below)
     cp gpurun_out/prof_$l/pmc_summary.json "$R/r05_${l}_leg_pmc_summary.json"
 done
-python bench.py > "$R/r05_bench_full_with_legs.json" 2> "$R/bench.err"
+python bench.py --full > "$R/r05_bench_full_with_legs.json" 2> "$R/bench.err"
 tail -c 400 "$R/r05_bench_full_with_legs.json"
 ls -la "$R"
