@@ -268,6 +268,7 @@ struct SearchArgs {
 typedef int v4i __attribute__((ext_vector_type(4)));
 #define AUX_SC1 16
 #define X_SLICE 256                  // phase X: arcs of one state a wave walks itself; the rest becomes slices for the next round
+#define XLW 4                        // phase X: 8-byte words of a row's instance flags requested at once (XState)
 #define QCAP 64                      // closure items a wave keeps for itself (inline closure queue)
 // The descriptor inputs go through readfirstlane so that the compiler can PROVE them wave-uniform;
 // otherwise it wraps every buffer access in a "waterfall" loop (cdna_hip_programming.md, T20).
@@ -682,20 +683,6 @@ __device__ __forceinline__ unsigned rec_chunk_off(unsigned seg_rec, int w, int c
     return ((unsigned)w * (seg_rec >> 6) + (unsigned)ci) * (unsigned)RecLayout<NE>::CHUNK_BYTES;
 }
 
-// ------------------------------------------------------------------ phase A
-//
-// doHMMInternalPropagation (:899-935) + HMMInternalPropagation (:376-484).  One lane owns one
-// instance and updates its emitting states in turn, so a wave has 64 instances in flight and all
-// loads of a pass are issued back to back (no divergent load branches: lanes without work read
-// out of range and get zeros).  Waves take chunks of 64 (of ONE writer segment); survivors and exit
-// tokens go to the wave's own output segments - no atomics, no barriers.  Work items, in this
-// order: chunks of instance records (list 0), of newly entered arcs (1), of states whose arrival keys
-// of the frame before the previous one need zeroing (2).  An instance PULLS its entry token: the best
-// arrival at its arc's source state in the previous frame (StateRec::e) plus the arc's weight.
-//
-// LR: every transition matrix of the model set is plain left-to-right (state j is entered from j-1 and
-// itself, the exit state from the last emitting state; no skips): the predecessor loops become one
-// comparison per state, on a compact table a_k = log P(k-1 -> k), s_k = log P(k -> k) in LDS.
 #ifdef JD_FINE
 // development build (-DJD_FINE=1: phase A, =2: phase X): drains the memory counters and charges the time
 // since the last mark to slot k; thread 0 of every workgroup only.  Serialises the hops it measures -
@@ -722,6 +709,662 @@ __device__ __forceinline__ unsigned rec_chunk_off(unsigned seg_rec, int w, int c
 #define XFINE_COUNT(k) do { } while (0)
 #endif
 
+// ------------------------------------------------------------------ the token-passing arithmetic, once for both search kernels
+//
+// The cluster kernel (phase_a / phase_x below: k_search, k_resident) and the slot kernel (jd_slot.h: slot_phase_a / slot_phase_x:
+// k_slot, k_slot_batch) run the same algorithm on the same data formats.  What differs between them, on purpose, is the LOOP
+// STRUCTURE - how work reaches a wave, whether phase A is software-pipelined, barriers and mailboxes - and that stays in those four
+// functions.  What one lane does with one instance (phase A) or with one item and one arc (phase X) is written here, once, and is held
+// against WFSTDecoderLite.cpp here, once.
+//
+// Two forms, chosen unit by unit on tools/kres.sh (the bar: VGPRs, LDS and waves per SIMD equal, spilled VGPRs and scratch bytes of no
+// kernel instance above what the two-copy sources gave).  These kernels sit on their register caps (k_slot 128 VGPRs + 42-50 spilled,
+// k_search 256 + 22-66), and the same statements behind a function boundary - inlined away - can come out of register allocation
+// differently, so each function form was compiled and compared before it was kept.
+//   FUNCTIONS (held the bar): jd_a_totals / jd_x_totals, jd_list_dirty (assembly of all kernels unchanged), jd_reserve_paths,
+//     jd_prefix_walk (every instance equal, k_slot_batch<6,true> 31 -> 27 spilled).
+//   TEXT (JD_A_*, JD_X_*: expanded inside the four functions where the code stood; every unit lists the names it takes from there, both
+//     kernels use the same names), with the function form that lost, spilled VGPRs before -> after:
+//     * JD_X_ITEM_HEAD + JD_X_THRESHOLDS as jd_item_head(...) / jd_thresholds<MDL>(...) with their results by reference: k_slot<6,true>
+//       48 -> 50 (scratch 196 -> 204), k_resident<6,true,true> 61 -> 63 (208 -> 216); two k_search<3> instances 25 -> 22;
+//     * JD_A_ENTRY_TOKEN (with the record header of a new instance) as jd_entry_token<DEFER_HIST>(Tok &, ...) / jd_inst_header<NE>(...):
+//       k_slot<6> 50 / 48 -> 63 / 65, k_slot_batch<6,false> 27 -> 31, k_resident<6,true,true> 61 -> 63;
+//     * the general-topology half of JD_A_HMM_UPDATE as hmm_general<NE>(trP, se, MN, n, tk, nw, ex, emit): k_slot<3> 42 / 43 -> 44 / 45,
+//       k_slot_batch<3> 18 / 22 -> 20 / 24, k_search<3,0,0,0> 24 -> 28, k_slot_batch<6> 27 / 31 -> 94 / 94, k_slot<6> 50 / 48 -> 66 / 95,
+//       k_search<6,0,0,0> 64 -> 80;
+//     * all units' differences between the kernels through one struct of methods and always_inline lambdas (counters captured by
+//       reference): k_slot<6> 50 / 48 -> 65 / 65, k_slot_batch<6,false> 27 -> 31 - hence the few macros below for the text units.
+//     NOT TRIED as functions, and text only for that reason: JD_A_EMIT, the left-to-right half of JD_A_HMM_UPDATE, JD_A_WRITE_OUT,
+//     JD_X_WINNER, JD_X_POOL, JD_X_ARRIVE, JD_X_ARC_STEP.  They are the next candidates, one at a time, by the same test.
+// ONE unit stays per kernel: the record header of a new instance (attachNetInst :751-774; stage_k below, the new-arc branch of
+// slot_phase_a).  The two copies request the second half of the arc's template (NE = 6) at different places, and either order, given
+// to both, changes the other kernel's NE = 6 code (the cluster kernel's order: k_slot<6> / k_slot_batch<6> differ, VGPR spills equal,
+// one spilled SGPR less; the slot kernel's order: all twelve k_search<6> / k_resident<6> differ).  Eight lines, each naming the other.
+//
+// The kernels' real differences are one small struct (`words`, for the function-form units) and a few one-line macros (for the text
+// units), defined once per kernel - the cluster kernel's behind the units below, the slot kernel's in jd_slot.h, both sets undefined
+// again behind slot_phase_x - and three constants:
+//   words (CtlWords / SlotWords), JD_FAIL, JD_BID_FINAL   the words every wave of a stream updates during a frame - the first error, the
+//               Path reservation cursor, the final state's key, the reference's Path count: the stream's control block in HBM, at the
+//               scope of the launch (XL) / LDS;
+//   JD_HIST     the frame's histogram bins: the workgroup's share, published behind the phase / the stream's own, by frame parity;
+//   JD_TALLY, JD_COUNT_PASS   where the JD_COUNT counters go: registers, added up at the end of the phase (jd_a_totals / jd_x_totals take
+//               them) / LDS atomics at once (the slot kernel has no registers to spare);
+//   JD_GOUT, JD_GW   the geometry the output lists are written with and this wave's segment (slot kernel: eight segments, the wave's number);
+//   JD_X_ARRIVAL     the arrival of an exit token at its state.  A REC_SOLE token's is a plain store in the cluster kernel (nothing to read
+//               back: +1-2 % on the heavy graphs) and stays the atomic max in the slot kernel (the branch cost its headline 1.5 %) - both as
+//               measured in round 6, and meant;
+//   JD_ARC_AT, JD_TMAX, JD_NOTE_CELL   an arc's record (lazily composed networks keep theirs in an arena: cluster kernel), the models'
+//               largest entry transition (from LDS in the slot kernel), the `cells` diagnostic (cluster kernel);
+//   DEFER_HIST  phase A takes the entry token's history from the winning item BEHIND the arithmetic (slot kernel under LR: the item is a
+//               third dependent round trip and only state 1 can take the entry token; the cluster kernel's pipeline has the item by then);
+//   LZY         lazily composed networks exist in the cluster kernel only (slot kernel: false; it also always takes the prefix walk).
+
+// where the words live that every wave of a stream updates during a frame (first error, Path reservation cursor, final state's key, the
+// reference's Path count): the cluster kernel's are in the stream's control block in HBM; the slot kernel's in LDS (SlotWords, jd_slot.h)
+template <bool XL> struct CtlWords {
+    StreamCtl &c; int p;                                               // (p: the frame's parity - its error word)
+    __device__ __forceinline__ void fail(int code) const { CSx<XL>(&c.err[p], code); }
+    __device__ __forceinline__ int take_paths(int n) const { return GADDx<XL>(&c.n_paths, n); }
+    __device__ __forceinline__ void add_paths_ref(int n) const { (void)GADDx<XL>(&c.n_paths_ref, n); }
+};
+
+// states whose arrival key became non-zero go to the wave's segment of the dirty list: zeroed by the phase A of the frame after the next one
+template <bool XL_, class Words>
+__device__ __forceinline__ void jd_list_dirty(const Words &words, int &dirty_cnt, unsigned seg_new, GAS int *dirty_seg, int lane, bool first, int state)
+{
+    const unsigned long long bf = __ballot(first);
+    if (bf) {
+        const int nf = __popcll(bf);
+        if (dirty_cnt + nf > (int)seg_new) { if (lane == 0) words.fail((int)JDE_NEW); }
+        else {
+            if (first) CS(dirty_seg + (unsigned)(dirty_cnt + rank_in(bf)), state);
+            dirty_cnt += nf;
+        }
+    }
+}
+
+// Path records (:497-509) for the lanes in `mask`: one atomic on the reservation cursor per wave; returns the first record's index
+template <class Words>
+__device__ __forceinline__ int jd_reserve_paths(const Words &words, unsigned long long mask, int lane)
+{
+    int pbase = 0;
+    if (mask) {
+        const int first = __ffsll((long long)mask) - 1;
+        if (lane == first) pbase = words.take_paths(__popcll(mask));
+        pbase = __shfl(pbase, first);
+    }
+    return pbase;
+}
+
+// per-wave totals of a phase -> the workgroup's counters in LDS (Shared: SearchShared / SlotShared; best: the frame's best score of the phase).
+// c_recs, c_keys / c_xitems, c_walk, c_clos: the JD_COUNT counters of a kernel that keeps them in registers (the slot kernel passes 0)
+template <class Shared>
+__device__ __forceinline__ void jd_a_totals(Shared &sh, unsigned *best, int lane, unsigned mo, int c_insts, int c_pemit, int c_emit, int c_end, int c_surv,
+                                            int c_recs, int c_keys)
+{
+    mo = wave_umax(mo);
+    c_pemit = wave_sum(c_pemit); c_emit = wave_sum(c_emit);
+    if (lane == 0) {
+        if (mo) atomicMax(best, mo);
+        if (c_insts) { atomicAdd(&sh.stat[ST_INSTS], c_insts); atomicAdd(&sh.stat[ST_RECS], c_insts); }
+        if (c_pemit) atomicAdd(&sh.stat[ST_PEMIT], c_pemit);
+        if (c_emit) atomicAdd(&sh.stat[ST_EMIT], c_emit);
+        if (c_end) atomicAdd(&sh.stat[ST_END], c_end);
+        if (c_surv) { atomicAdd(&sh.stat[ST_MODELS], c_surv); atomicAdd(&sh.stat[ST_SURV], c_surv); }
+        if (c_recs) atomicAdd(&sh.stat[ST_NEWL], c_recs);
+        if (c_keys) atomicAdd(&sh.stat[ST_KEYS], c_keys);
+    }
+}
+template <class Shared, class Words>
+__device__ __forceinline__ void jd_x_totals(Shared &sh, const Words &words, unsigned *best, bool ref_count, int lane, unsigned mo, int c_arcs, int c_paths,
+                                            int c_pend, int c_new, int c_ref, int c_xitems, int c_walk, int c_clos)
+{
+    mo = wave_umax(mo);
+    c_arcs = wave_sum(c_arcs); c_paths = wave_sum(c_paths); c_pend = wave_sum(c_pend); c_new = wave_sum(c_new);
+    if (ref_count) {
+        c_ref = wave_sum(c_ref);
+        if (lane == 0 && c_ref) words.add_paths_ref(c_ref);
+    }
+    if (lane == 0) {
+        if (mo) atomicMax(best, mo);
+        if (c_arcs) atomicAdd(&sh.stat[ST_ARCS], c_arcs);
+        if (c_paths) atomicAdd(&sh.stat[ST_PATHS], c_paths);
+        if (c_pend) atomicAdd(&sh.stat[ST_PEND], c_pend);
+        if (c_xitems) atomicAdd(&sh.stat[ST_XITEMS], c_xitems);
+        if (c_walk) atomicAdd(&sh.stat[ST_WALK], c_walk);
+        if (c_clos) atomicAdd(&sh.stat[ST_CLOS], c_clos);
+        if (c_new) { atomicAdd(&sh.stat[ST_MODELS], c_new); atomicAdd(&sh.new_all, c_new); }   // attached instances are active models (:981)
+    }
+}
+
+// The prefix walk.  The arcs of a state that enter a model stand in descending order of w + tmax behind the ones every arrival walks (XState):
+// the item can only enter a PREFIX of them - the rest fails the "hopeless candidate" test whatever its flag says - and the prefix's upper bound
+// comes from the samples in the state's record x0 .. x3.  (Conservative by a margin far above the rounding of the sums: the test itself still
+// decides inside the prefix.)  What the walk did for the arcs left out: they count as visited (c_arcs), the best entry-token candidate of the
+// WHOLE row is score + wmax (mo; float addition is monotone), and the arcs entered without an instance are the row's model arcs less the
+// instance flags set in it - one byte per arc, the row's side by side (x_new: counted behind the arrival).  Rows of up to 8 * 2 * XLW - 7
+// arcs: their flags are one or two batches of loads; a longer row is walked whole and counted arc by arc (returns false: no prefix walk).
+// xcut: the cluster kernel switches the walk off for graphs of long rows and lazily composed ones.  rs1: cut back to the prefix's end.
+__device__ __forceinline__ bool jd_prefix_walk(const DecConst &C, const StreamView &V, bool xcut, bool have, int slice_no, int rs, int &rs1,
+                                               const int4 &x0, const int4 &x1, const int4 &x2, const int4 &x3, float score, float bestA,
+                                               bool can_filter, unsigned &mo, int &c_arcs, int &x_new)
+{
+    const bool xitem = xcut && have && slice_no == 0 && rs1 - (rs & ~7) <= 16 * XLW;
+    if (xitem) {
+        const int n_entry = x0.y, n_model = x0.w;
+        if (n_model > 0) { const unsigned sw = f2o(score + __int_as_float(x0.z)); mo = sw > mo ? sw : mo; }
+        const int a8 = rs & ~7;
+        const GAS unsigned long long *lw = (const GAS unsigned long long *)(V.live + a8);
+        auto in_row = [&](int base) __attribute__((always_inline)) {   // the bytes of the word at `base` that belong to the row
+            const int lo = max(rs - base, 0), hi = min(rs1 - base, 8);
+            const unsigned long long mh = hi >= 8 ? ~0ULL : ((1ULL << (8 * max(hi, 0))) - 1ULL);
+            const unsigned long long ml = (1ULL << (8 * lo)) - 1ULL;
+            return 0x0101010101010101ULL & mh & ~ml;
+        };
+        int lv_row = 0;
+        {
+            unsigned long long w8[XLW];
+#pragma unroll
+            for (int i = 0; i < XLW; ++i) w8[i] = (n_model > 0 && a8 + 8 * i < rs1) ? CL(lw + i) : 0ULL;
+#pragma unroll
+            for (int i = 0; i < XLW; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * i));
+        }
+        if (__ballot(n_model > 0 && a8 + 8 * XLW < rs1)) {               // (some lane's row goes on: the second batch)
+            unsigned long long w8[XLW];
+#pragma unroll
+            for (int i = 0; i < XLW; ++i) w8[i] = (n_model > 0 && a8 + 8 * (XLW + i) < rs1) ? CL(lw + XLW + i) : 0ULL;
+#pragma unroll
+            for (int i = 0; i < XLW; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * (XLW + i)));
+        }
+        x_new = n_model - lv_row;
+        if (can_filter && n_entry > 0) {
+            const float lim = (bestA - C.emit_win) - (1.0f + 1e-5f * (fabsf(bestA) + fabsf(score)));
+            const int kx[XNCAND] = {x1.x, x1.y, x1.z, x1.w, x2.x, x2.y, x2.z, x2.w, x3.x, x3.y, x3.z, x3.w};
+            int P = n_entry;
+#pragma unroll
+            for (int i = XNCAND - 1; i >= 0; --i)
+                if (xcand(i) < n_entry && score + __int_as_float(kx[i]) <= lim) P = xcand(i);
+            c_arcs += n_entry - P;
+            rs1 -= n_entry - P;
+        }
+    }
+    return xitem;
+}
+
+// entry token = the best token that arrived at the arc's source state in the previous frame (its key kv, its item itv), over the arc (:560-582).
+// DEFER_HIST: the score only - it is in the key; the history follows behind the arithmetic (JD_A_HMM_UPDATE).  Uses: kv, itv, h1, startTh, tk.
+#define JD_A_ENTRY_TOKEN                                                                                           \
+    tk[0] = null_tok();                                                                                            \
+    if (kv != 0ULL) {                                                                                              \
+        tk[0].score = o2f((unsigned)(kv >> 32)) + __int_as_float(h1.w);   /* :562 newScore = tok.score + weight */ \
+        if (!DEFER_HIST) {                                                                                         \
+            const Tok it = as_tok(itv);                                                                            \
+            tk[0].ac = it.ac; tk[0].lm = it.lm + __int_as_float(h1.w); tk[0].path = it.path;                       \
+        }                                                                                                          \
+        if (tk[0].score < startTh) tk[0] = null_tok();            /* :915-918 (a candidate is never LOG_ZERO) */   \
+    }
+
+// emit (:408-424): emitting state j takes `best` (over transition `btp`, from token `src`) if it passes the frame's threshold.
+// Uses: normalise, emitTh, outp, nw, live_mask, c_pemit, mo, use_hist, C; JD_HIST, JD_FAIL, JD_NOTE_CELL.
+#define JD_A_EMIT                                                                                                                  \
+    auto emit = [&](int j, float best, float btp, const Tok &src) __attribute__((always_inline)) {   /* :408-424 */                \
+        const float sc = best - normalise;                         /* :408 */                                                      \
+        if (sc > emitTh) {                                         /* :409 */                                                      \
+            ++c_pemit;                                                                                                             \
+            JD_NOTE_CELL(j)                                                                                                        \
+            nw[j].score = sc + outp[j - 1];                                                                                        \
+            nw[j].ac = (src.ac + btp) + outp[j - 1];                                                                               \
+            nw[j].lm = src.lm;                                                                                                     \
+            nw[j].path = src.path;                                                                                                 \
+            live_mask |= 1 << j;                                                                                                   \
+            if (use_hist) {                                        /* Histogram::addScore, Histogram.cpp:64-100 */                 \
+                jd_hist_add(nw[j].score, C.hist_min, C.hist_max, [&]() __attribute__((always_inline)) { JD_FAIL((int)JD_EHIST); }, \
+                            [&](int b) __attribute__((always_inline)) { atomicAdd(&JD_HIST[b], 1); });                             \
+            }                                                                                                                      \
+            const unsigned so = f2o(nw[j].score);                                                                                  \
+            mo = so > mo ? so : mo;                                                                                                \
+        }                                                                                                                          \
+    };
+
+// The HMM update of one instance: tk[0 .. NE] (entry token + last frame's tokens) -> nw[1 .. NE], ex.  LR: one comparison per state;
+// else the general, branch-free form; the exit state either way.  Uses: LR, NE, MN, n, tm, tk, nw, ex, emit, live_mask, sh.trP (LR),
+// trP_all / se_all (general); DEFER_HIST with itv, outp, h1 (see JD_A_ENTRY_TOKEN).
+#define JD_A_HMM_UPDATE                                                                                                                    \
+    if (LR) {                                                                                                                              \
+        constexpr int LRW = (NE == 3) ? 8 : 16;                    /* a_1 .. a_{NE+1}, s_1 .. s_NE */                                      \
+        const float4 *lt = (const float4 *)(sh.trP + tm * LRW);                                                                            \
+        float tw[LRW];                                                                                                                     \
+        _Pragma("unroll")                                                                                                                  \
+        for (int q = 0; q < LRW / 4; ++q) {                                                                                                \
+            const float4 v = lt[q];                                                                                                        \
+            tw[4 * q] = v.x; tw[4 * q + 1] = v.y; tw[4 * q + 2] = v.z; tw[4 * q + 3] = v.w;                                                \
+        }                                                                                                                                  \
+        bool entry_won = false;                                                                                                            \
+        _Pragma("unroll")                                                                                                                  \
+        for (int j = 1; j <= NE; ++j) {                            /* :387-424 emitting state j: predecessors j-1 and j */                 \
+            nw[j] = null_tok();                                                                                                            \
+            const float a = tw[j - 1], sf = tw[NE + j];                                                                                    \
+            const float c0 = tk[j - 1].score + a, c1 = tk[j].score + sf;                                                                   \
+            const bool self = c1 > c0;                             /* the lower predecessor wins ties (:401) */                            \
+            Tok src;                                                                                                                       \
+            src.score = 0.0f; src.ac = self ? tk[j].ac : tk[j - 1].ac; src.lm = self ? tk[j].lm : tk[j - 1].lm;                            \
+            src.path = self ? tk[j].path : tk[j - 1].path;                                                                                 \
+            if (j < n - 1) emit(j, self ? c1 : c0, self ? sf : a, src);                                                                    \
+            if (j == 1) entry_won = !self;                                                                                                 \
+        }                                                                                                                                  \
+        if (DEFER_HIST && (live_mask & 2) && entry_won) {        /* state 1 took the entry token: its history, from the item (:562-566) */ \
+            const Tok it = as_tok(itv);                                                                                                    \
+            nw[1].ac = (it.ac + tw[0]) + outp[0];                                                                                          \
+            nw[1].lm = it.lm + __int_as_float(h1.w);                                                                                       \
+            nw[1].path = it.path;                                                                                                          \
+        }                                                                                                                                  \
+        /* exit state (:443-483): entered from the last emitting state only */                                                             \
+        Tok le = null_tok();                                                                                                               \
+        float ax = 0.0f;                                                                                                                   \
+        _Pragma("unroll")                                                                                                                  \
+        for (int i = 1; i <= NE; ++i) if (i == n - 2) { le = nw[i]; ax = tw[i]; }                                                          \
+        if (le.score > LZ) { ex = le; ex.score = le.score + ax; ex.ac = le.ac + ax; if (!(ex.score > LZ)) ex = null_tok(); }               \
+    } else {                                                                                                                               \
+        /* general topologies, branch-free: every (predecessor, state) pair is evaluated and selected */                                   \
+        const float *trP = trP_all + (size_t)tm * MN * MN;                                                                                 \
+        const int *se = se_all + (size_t)tm * MN;                                                                                          \
+        _Pragma("unroll")                                                                                                                  \
+        for (int j = 1; j <= NE; ++j) {                            /* :387-424 emitting state j */                                         \
+            nw[j] = null_tok();                                                                                                            \
+            const int sev = se[j < MN ? j : 0];                                                                                            \
+            const int st = sev & 0xffff, en = sev >> 16;                                                                                   \
+            float best = 0.0f, btp = 0.0f;                                                                                                 \
+            Tok src = null_tok();                                                                                                          \
+            bool have = false;                                                                                                             \
+            _Pragma("unroll")                                                                                                              \
+            for (int i = 0; i <= NE; ++i) {                        /* predecessors in ascending order, the first wins ties */              \
+                const bool v = (i == st) | ((i > st) & (i < en));                                                                          \
+                const float tp = trP[(i < MN ? i : 0) * MN + (j < MN ? j : 0)];                                                            \
+                const float tmp = tk[i].score + tp;                                                                                        \
+                const bool take = v & (!have | (tmp > best));                                                                              \
+                best = take ? tmp : best; btp = take ? tp : btp;                                                                           \
+                src.ac = take ? tk[i].ac : src.ac; src.lm = take ? tk[i].lm : src.lm; src.path = take ? tk[i].path : src.path;             \
+                have |= v;                                                                                                                 \
+            }                                                                                                                              \
+            if (have & (j < n - 1)) emit(j, best, btp, src);                                                                               \
+        }                                                                                                                                  \
+        /* exit state (:443-483) from the NEW tokens */                                                                                    \
+        {                                                                                                                                  \
+            const int sev = se[n >= 2 ? n - 1 : 0];                                                                                        \
+            const int st = sev & 0xffff, en = sev >> 16;                                                                                   \
+            bool have = false;                                                                                                             \
+            _Pragma("unroll")                                                                                                              \
+            for (int i = 1; i <= NE; ++i) {                                                                                                \
+                const bool v = (i == st) | ((i > st) & (i < en));                                                                          \
+                const float tp = trP[(i < MN ? i : 0) * MN + (n >= 2 ? n - 1 : 0)];                                                        \
+                const float tmp = nw[i].score + tp;                                                                                        \
+                const bool take = v & (!have | (tmp > ex.score));                                                                          \
+                ex.score = take ? tmp : ex.score; ex.ac = take ? nw[i].ac + tp : ex.ac;                                                    \
+                ex.lm = take ? nw[i].lm : ex.lm; ex.path = take ? nw[i].path : ex.path;                                                    \
+                have |= v;                                                                                                                 \
+            }                                                                                                                              \
+            if (!(have & (n >= 2)) || !(ex.score > LZ)) ex = null_tok();                                                                   \
+        }                                                                                                                                  \
+    }
+
+// What a pass leaves behind: survivors to the wave's segment gw of the next record list, exit tokens to its item segment with their bid.
+// Uses: live_mask, ex, nw, h0 .. h2, arc, valid, is_new, kv, out_cnt, exit_cnt, c_emit, c_insts, c_surv, c_end,
+// rnext, icur, item_base; JD_GOUT, JD_GW, JD_FAIL, JD_COUNT_PASS.
+#define JD_A_WRITE_OUT                                                                                                                                             \
+    c_emit += __popc(live_mask);                                                                                                                                   \
+    const bool has_exit = ex.score > LZ;                                                                                                                           \
+    const bool slot_live = live_mask != 0;                                                                                                                         \
+    const unsigned long long bl = __ballot(slot_live), be = __ballot(has_exit);                                                                                    \
+    if (!is_new) c_insts += __popcll(__ballot(valid));             /* (new arcs are counted when they are entered) */                                              \
+    JD_COUNT(JD_COUNT_PASS);                                                                                                                                       \
+    /* survivors: header + new tokens to this wave's segment of the next list */                                                                                   \
+    {                                                                                                                                                              \
+        const int nsurv = __popcll(bl);                                                                                                                            \
+        if (out_cnt + nsurv > (int)JD_GOUT.seg_rec) { if (lane == 0) JD_FAIL((int)JDE_SLOTS); }                                                                    \
+        else {                                                                                                                                                     \
+            const int pos = out_cnt + rank_in(bl);                                                                                                                 \
+            const unsigned doff = slot_live ? rnext + rec_chunk_off<NE>(JD_GOUT.seg_rec, JD_GW, pos >> 6) + (unsigned)(pos & 63) * 16u : OOB_OFF;                  \
+            st16(V.rec, doff, h0); st16(V.rec, doff + 1024u, h1);                                                                                                  \
+            if (NE == 6) st16(V.rec, doff + 2048u, h2);                                                                                                            \
+            _Pragma("unroll")                                                                                                                                      \
+            for (int j = 1; j <= NE; ++j) st16(V.rec, doff + (unsigned)(HF + j - 1) * 1024u, as_v4(nw[j]));                                                        \
+            out_cnt += nsurv;                                                                                                                                      \
+            c_surv += nsurv;                                                                                                                                       \
+        }                                                                                                                                                          \
+        /* the arc's "has an instance" flag changes at birth and death only (returnNetInst :777-797) */                                                            \
+        if (valid && is_new && slot_live) CS(&V.live[arc], (unsigned char)1);                                                                                      \
+        if (valid && !slot_live && !is_new) CS(&V.live[arc], (unsigned char)0);                                                                                    \
+    }                                                                                                                                                              \
+    /* exit tokens: frontier items of round 0 in this wave's item segment, bidding for their */                                                                    \
+    /* destination state (state-level recombination, see phase X); tokens leaving word-labelled */                                                                 \
+    /* arcs face their own threshold (:952-962) -> own key class */                                                                                                \
+    {                                                                                                                                                              \
+        const int nex = __popcll(be);                                                                                                                              \
+        if (exit_cnt + nex > (int)JD_GOUT.seg_item) { if (lane == 0) JD_FAIL((int)JDE_ITEMS); }                                                                    \
+        else {                                                                                                                                                     \
+            const unsigned k = item_base + (unsigned)(exit_cnt + rank_in(be));                                                                                     \
+            const unsigned ioff = has_exit ? icur + k * 32u : OOB_OFF;                                                                                             \
+            st16(V.items, ioff, as_v4(ex));                                                                                                                        \
+            const int lab = (h0.y & REC_LABELLED) ? 1 : 0;         /* (the label itself is read from the arc when a Path record is written) */                     \
+            const int sole = (h0.y & REC_SOLE) ? ITEM_SOLE : 0;                                                                                                    \
+            st16(V.items, ioff + 16u, (v4i){arc, lab, h0.w, sole});                                                                                                \
+            if (has_exit && !sole) GMAX((lab ? &SREC_BID(V.srec, C, h0.w).keyL : &SREC_BID(V.srec, C, h0.w).key0), ((unsigned long long)f2o(ex.score) << 32) | k); \
+            JD_COUNT(const int nbid_ = __popcll(__ballot(has_exit && !sole)); if (lane == 0 && nbid_) atomicAdd(&sh.stat[ST_BIDS], nbid_));                        \
+            exit_cnt += nex;                                                                                                                                       \
+            c_end += nex;                                                                                                                                          \
+        }                                                                                                                                                          \
+    }
+
+// phase X, one item per lane: what kind of item it is.  Uses: valid, exit_kind, ii, info, slice_no, icur; JD_TALLY.
+#define JD_X_ITEM_HEAD                                                                                                                     \
+    const unsigned ioff = valid ? icur + ii * 32u : OOB_OFF;                                                                               \
+    const bool start_tok = valid && exit_kind && info.x < 0;       /* recognitionStart's token: it has traversed no arc */                 \
+    JD_COUNT(JD_TALLY(xitems, __popcll(__ballot(valid))));                                                                                 \
+    const bool real = valid && !start_tok && slice_no == 0;        /* an item that traversed an arc (a slice has been through all this) */ \
+    const int state = !valid ? 0 : start_tok ? C.init_state : info.z;
+
+// The threshold class test (:952-962), the reference's Path count, who reserves a Path record.  Uses: valid, exit_kind, t, info, init, endTh, wordTh, real, start_tok, state, c_pend, c_ref, C, MDL.
+#define JD_X_THRESHOLDS                                                                                                  \
+    bool have = valid;                                                                                                   \
+    if (real && exit_kind && !init) {                              /* :952-962 */                                        \
+        have = t.score > ((info.y != 0) ? wordTh : endTh);                                                               \
+        if (have) ++c_pend;                                                                                              \
+    }                                                                                                                    \
+    /* the reference's own Path count (collectPaths' trigger, :360-362): propagateToken makes one for the arc's label */ \
+    /* and one for every labelled epsilon / tee arc of the closure behind it, for EVERY token it is called with - */     \
+    /* recombination happens at the entry states only (:560) - where this build expands a state's best arrival alone */  \
+    if (C.pcount != nullptr && ((real && exit_kind && have) || start_tok))                                               \
+        c_ref += (start_tok ? 0 : (info.y != 0 ? 1 : 0)) + C.pcount[state];                                              \
+    /* Path records (:497-509) are reserved for every labelled item that passed its threshold, winner or not, so that */ \
+    /* the reservation is in flight together with the loads below: it is issued BEHIND them (the compiler waits */       \
+    /* for a returning atomic where it stands, and that wait then is the wait for the loads as well) */                  \
+    /* (MDL: behind the winner test, below) */                                                                           \
+    const bool labelled = !MDL && real && have && info.y != 0;                                                           \
+    const unsigned long long blab = __ballot(labelled);                                                                  \
+    int pbase = 0;                                                                                                       \
+    int amdl = 0;                                                  /* MDL: an exit token's model (its arc's in-label) */
+
+// Winner test and bid reset, Path records (word mode and MDL), final state, what the arrival will need.
+// Uses: C, V, real, exit_kind, sole, kv, ii, info, state, have, t, label, amdl, cmdl, pbase, blab, ioff, pframe, last_frame, LZY / fin_lazy (cluster kernel: the
+// final weight of a lazily composed state comes with its row), INF, c_paths, words; JD_BID_FINAL, JD_FAIL.
+#define JD_X_WINNER                                                                                                                    \
+    if (real) {                                                                                                                        \
+        /* (a closure item was the best arrival at its state when it was produced - else it was never listed for a */                  \
+        /* later round - and that makes it responsible for the arcs its score was the first to make hopeful, see */                    \
+        /* above: it is expanded even if a better arrival has come since) */                                                           \
+        const bool winner = !exit_kind || sole || ((unsigned)(kv & 0xffffffffULL) == ii && kv != 0ULL);                                \
+        /* every state that received exit-token bids is cleaned up by its winner, expanded or not (an */                               \
+        /* item below its threshold still holds the key of its state if it was the best one there) */                                  \
+        if (winner && exit_kind && !sole) CS(info.y != 0 ? &SREC_BID(V.srec, C, state).keyL : &SREC_BID(V.srec, C, state).key0, 0ULL); \
+        have = have && winner;                                                                                                         \
+    }                                                                                                                                  \
+    if constexpr (MDL) {                                           /* a record for every winner that passed a model or a word label */ \
+        const int mdl = exit_kind ? amdl : cmdl;                                                                                       \
+        const bool rec = have && real && (label != 0 || mdl != 0);                                                                     \
+        const unsigned long long brec = __ballot(rec);                                                                                 \
+        pbase = jd_reserve_paths(words, brec, lane);                                                                                   \
+        if (rec) {                                                                                                                     \
+            const int pp = pbase + rank_in(brec);                                                                                      \
+            if (pp < C.cap_paths) {                                                                                                    \
+                /* PathRec {prev, frame, label, model; score, ac, lm, -} */                                                            \
+                V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, mdl};                                                           \
+                V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};           \
+                t.path = pp;                                                                                                           \
+                st16(V.items, ioff, as_v4(t));                                                                                         \
+                if (label != 0) ++c_paths;                                                                                             \
+            } else JD_FAIL((int)JDE_PATHS);                                                                                            \
+        }                                                                                                                              \
+    }                                                                                                                                  \
+    if (have && real) {                                                                                                                \
+        if (!MDL && info.y != 0) {                                                                                                     \
+            const int pp = pbase + rank_in(blab);                                                                                      \
+            if (pp < C.cap_paths) {                                                                                                    \
+                /* PathRec {prev, frame, label, -; score, ac, lm, -}: two plain 16-byte stores (read by later launches only) */        \
+                V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, 0};                                                             \
+                V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};           \
+                t.path = pp;                                                                                                           \
+                st16(V.items, ioff, as_v4(t));                     /* the tokens pulled from this item carry the new history */        \
+                ++c_paths;                                                                                                             \
+            } else JD_FAIL((int)JDE_PATHS);                                                                                            \
+        }                                                                                                                              \
+        /* :513-520 final state.  bestFinalToken is reset every frame (:316) and only read by */                                       \
+        /* finish(), so it only has to be evaluated on the last frame that is available. */                                            \
+        if (last_frame) {                                                                                                              \
+            const float fw = LZY ? fin_lazy : C.fin_w[info.z];                                                                         \
+            if (fw < INF) {                                                                                                            \
+                const float cs = t.score + fw;                                                                                         \
+                if (cs > LZ) JD_BID_FINAL(((unsigned long long)f2o(cs) << 32) | ii);                                                   \
+            }                                                                                                                          \
+        }                                                                                                                              \
+    }                                                                                                                                  \
+    /* ---- arrival of an exit token (and of the start token) at its state: the atomic's old value is the best */                      \
+    /* arrival before it.  (Closure items arrived when they were produced and carry that value; a slice carries */                     \
+    /* its item's.)  The answer is first needed by the arc passes: its round trip runs beside the first arcs'. */                      \
+    unsigned eo = exit_kind ? 0u : (unsigned)info.x;               /* ordered score of the best arrival before this one (0: none) */   \
+    unsigned long long eold = 0ULL;                                                                                                    \
+    const bool arrive = have && exit_kind;                         /* (the atomic itself: behind the first arcs' loads, below) */
+
+// Slices of a long row, the pooled arc walk's prefix, the first arcs' loads.  Uses: rs, rs1, slice_no, have, lane, wpfx; JD_ARC_AT_DEF, JD_ARC_AT.
+#define JD_X_POOL                                                                                                          \
+    /* ---- A state with thousands of out-arcs (a history with 10^4 successors) would keep this wave busy */               \
+    /* for hundreds of passes while the cluster waits at the barrier: the wave walks the first X_SLICE */                  \
+    /* arcs itself and hands the rest on as SLICES - items of the next round (flag 2 + slice number) */                    \
+    /* that carry the token as it stands now and skip everything above; the cluster shares them out. */                    \
+    int alo = rs, ahi = rs1;                                                                                               \
+    if (slice_no > 0) { alo = rs + slice_no * X_SLICE; ahi = min(rs1, alo + X_SLICE); }                                    \
+    int n_slices = 0;                                                                                                      \
+    if (have && slice_no == 0 && rs1 - rs > X_SLICE) { n_slices = (rs1 - rs - 1) / X_SLICE; ahi = rs + X_SLICE; }          \
+    /* ---- pooled arc walk: exclusive prefix of the items' out-degrees */                                                 \
+    const int deg = have ? ahi - alo : 0;                                                                                  \
+    int incl = deg;                                                                                                        \
+    _Pragma("unroll")                                                                                                      \
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (lane >= o) incl += y; }                       \
+    const int tot = __shfl(incl, 63);                                                                                      \
+    wpfx[lane] = incl - deg;                                       /* wave-private: a wave's LDS operations are ordered */ \
+    /* owner of pooled arc a = largest gg with wpfx[gg] <= a; its arc record is fetched one pass ahead */                  \
+    auto owner_of = [&](int a) __attribute__((always_inline)) { int gg = 0;                                                \
+        _Pragma("unroll")                                                                                                  \
+        for (int stp = 32; stp > 0; stp >>= 1) if (wpfx[gg + stp] <= a) gg += stp;                                         \
+        return gg; };                                                                                                      \
+    int g_nx = owner_of(lane);                                                                                             \
+    int b_nx = __shfl(alo, g_nx) + (lane - wpfx[g_nx]);                                                                    \
+    JdArc Bk_nx = {0, 0.0f, 0, 0};                                                                                         \
+    JD_ARC_AT_DEF                                                                                                          \
+    /* ... and so is its "has an instance" flag (a byte per arc: the arcs of a state share a sector).  These loads are */  \
+    /* UNCONDITIONAL (lanes without an arc read arc 0): a load inside a branch reaches the loop-carried registers */       \
+    /* through a copy at the join, and the compiler waits for it right there - the "pass ahead" was a pass behind. */      \
+    int lv_nx = 0;                                                                                                         \
+    { const int bq = lane < tot ? b_nx : 0; Bk_nx = JD_ARC_AT(bq); lv_nx = CL(V.live + bq); }
+
+// The arrival, the slices handed on.  Uses: arrive, t, ii, state, eo, eold, x_new, c_new, n_slices, label, out, deferred, item_base, icur, list_dirty; JD_X_ARRIVAL (sole), JD_GOUT, JD_FAIL.
+#define JD_X_ARRIVE                                                                                                                              \
+    /* the arrival (see above), issued behind the first arcs' loads: the compiler waits for a returning atomic where it */                       \
+    /* stands, so this way the two round trips are one */                                                                                        \
+    if (arrive) {                                                                                                                                \
+        JD_X_ARRIVAL                                                                                                                             \
+    }                                                                                                                                            \
+    jd_list_dirty<XL_>(words, out.dirty_cnt, JD_GOUT.seg_new, dirty_seg, lane, arrive && eold == 0ULL, state);                                                                                                   \
+    if (eo == 0u) c_new += x_new;                                  /* (the first arrival at the state in this frame: :899-935 tries them all) */ \
+    if (__ballot(n_slices > 0)) {                                                                                                                \
+        for (unsigned long long bs = __ballot(n_slices > 0); bs; bs &= bs - 1) {                                                                 \
+            const int src = __ffsll((long long)bs) - 1;                                                                                          \
+            const int ns = __shfl(n_slices, src);                                                                                                \
+            const v4i tv = {__shfl(__float_as_int(t.score), src), __shfl(__float_as_int(t.ac), src),                                             \
+                            __shfl(__float_as_int(t.lm), src), __shfl(t.path, src)};                                                             \
+            const int sx = __shfl((int)eo, src), sy = __shfl(label, src), sz = __shfl(state, src);                                               \
+            for (int j0 = 0; j0 < ns; j0 += 64) {                                                                                                \
+                const int nj = min(64, ns - j0);                                                                                                 \
+                if (out.item_cnt + nj > (int)JD_GOUT.seg_item) { if (lane == 0) JD_FAIL((int)JDE_ITEMS); break; }                                \
+                if (lane < nj) {                                                                                                                 \
+                    const unsigned k = item_base + (unsigned)(out.item_cnt + lane);                                                              \
+                    st16(V.items, icur + k * 32u, tv);                                                                                           \
+                    st16(V.items, icur + k * 32u + 16u, (v4i){sx, sy, sz, 2 | ((j0 + lane + 1) << 2)});                                          \
+                }                                                                                                                                \
+                out.item_cnt += nj; deferred += nj;                                                                                              \
+            }                                                                                                                                    \
+        }                                                                                                                                        \
+    }
+
+// One pass of the pooled arc walk: lane l takes arc a0 + l (classification, epsilon / tee token, touch rule, closure push).
+// Uses: a0, tot, alo, wpfx, owner_of, g_nx, b_nx, Bk_nx, lv_nx, t, eo, state, xitem, p, endTh, wordTh, bestA, can_filter, tee_lds, LZY, MDL, mo, c_arcs, c_new, out, q_n, qtok, qinfo, qrow, qmdl, deferred, item_base, new_base, icur, list_dirty;
+// JD_ARC_AT, JD_TMAX, JD_TALLY, JD_GOUT, JD_FAIL.
+#define JD_X_ARC_STEP                                                                                                                                  \
+    const int a = a0 + lane;                                                                                                                           \
+    const int gg = g_nx, b = b_nx;                                                                                                                     \
+    const JdArc Bk = Bk_nx;                                                                                                                            \
+    const int lv = lv_nx;                                                                                                                              \
+    /* the next pass's arcs (LDS look-ups only; the loads are issued BEHIND this pass's own, see below) */                                             \
+    g_nx = owner_of(a + 64);                                                                                                                           \
+    const int alo_nx = __shfl(alo, g_nx);                      /* (every lane takes part: its owner may be a lane that has no next arc itself) */      \
+    b_nx = (a + 64 < tot) ? alo_nx + (a + 64 - wpfx[g_nx]) : 0;                                                                                        \
+    Tok tg;                                                                                                                                            \
+    tg.score = __shfl(t.score, gg); tg.ac = __shfl(t.ac, gg);                                                                                          \
+    tg.lm = __shfl(t.lm, gg); tg.path = __shfl(t.path, gg);                                                                                            \
+    const unsigned eog = (unsigned)__shfl((int)eo, gg);         /* best arrival at the owner's state before it (ordered; 0: none) */                   \
+    const int sgx = __shfl(state | (xitem ? (int)0x80000000 : 0), gg);   /* (+ the owner's "counted per state" flag) */                                \
+    const int sg = sgx & 0x7fffffff;                                                                                                                   \
+    bool mk = false, touch = false;                                                                                                                    \
+    Tok un = null_tok();                                                                                                                               \
+    /* Everything a pass READS is requested before anything is waited for - one memory round trip: the */                                              \
+    /* model's constant of an entry arc, and the state record of the destination of every arc that can */                                              \
+    /* produce a closure item (its arrival key as a pre-filter: hot history states receive many arrivals, */                                           \
+    /* and an atomic on a contended key costs far more than this load; its row for the item to carry). */                                              \
+    const bool on = a < tot;                                                                                                                           \
+    const int inl = Bk.in & ~ARC_FLAGS;                                                                                                                \
+    const bool entry = on && inl != 0;                                                                                                                 \
+    const bool is_tee = entry && (Bk.in & TEE_FLAG) != 0;                                                                                              \
+    const float ns = tg.score + Bk.w;                          /* (:535 / :562: the same sum either way) */                                            \
+    const unsigned so = f2o(ns);                                                                                                                       \
+    unsigned long long skc = 0ULL;                                                                                                                     \
+    const float tmax = JD_TMAX(entry ? inl - 1 : 0);       /* (used for entry arcs without an instance; unconditional, see above) */                   \
+    int2 nrow = make_int2(0, 0);                                                                                                                       \
+    {                                                                                                                                                  \
+        const unsigned doff = ((on && inl == 0) || is_tee) ? SREC_E_OFF(C, Bk.to, p) : OOB_OFF;                                                        \
+        const unsigned long long se = ld8(V.srec_r, doff);                                                                                             \
+        if (!LZY) { const int ti = doff != OOB_OFF ? Bk.to : 0; const int r0 = C.row_ptr[ti]; nrow = make_int2(r0, C.row_ptr[ti + 1] - r0); }          \
+        /* the next pass's arc records and flags: in flight during this pass, and - issued behind the loads this */                                    \
+        /* pass waits for (loads return in order) - not waited for before the next one */                                                              \
+        Bk_nx = JD_ARC_AT(b_nx); lv_nx = CL(V.live + b_nx);                                                                                            \
+        skc = se;                                                                                                                                      \
+    }                                                                                                                                                  \
+    if (on) ++c_arcs;                                                                                                                                  \
+    JD_COUNT(JD_TALLY(walk, __popcll(__ballot(on))));                                                                                                  \
+    if (on && inl == 0) {                                      /* :533-540 epsilon input */                                                            \
+        un = tg;                                                                                                                                       \
+        un.score = ns;                                                                                                                                 \
+        un.lm = tg.lm + Bk.w;                                                                                                                          \
+        mk = un.score > endTh;                                                                                                                         \
+    } else if (is_tee) {                                       /* :584-600 tee model */                                                                \
+        /* (an atomic load: never merged with the LDS one into a flat load) */                                                                         \
+        const float tee = tee_lds ? sh.tee[inl - 1] : CL(C.hmm_tee + (inl - 1));                                                                       \
+        const float ns2 = ns + tee;                                                                                                                    \
+        un.score = ns2;                                                                                                                                \
+        un.ac = tg.ac + tee;                                                                                                                           \
+        un.lm = tg.lm + Bk.w;                                                                                                                          \
+        un.path = tg.path;                                                                                                                             \
+        mk = ns2 > ((Bk.out != 0) ? wordTh : endTh);                                                                                                   \
+    }                                                                                                                                                  \
+    if (entry) {                                               /* :560-582 entry-token recombination: pulled by the next phase A */                    \
+        mo = so > mo ? so : mo;                                /* :572-573 */                                                                          \
+        if (lv == 0) {                                         /* no instance: attachNetInst :751-774 */                                               \
+            if (sgx >= 0 && eog == 0u) ++c_new;                /* (counted once, by the first arrival at the state; prefix walks: per state, above) */ \
+            if (can_filter) {                                                                                                                          \
+                const bool mine = (ns + tmax) - bestA > -C.emit_win;                                                                                   \
+                const bool before = eog != 0u && ((o2f(eog) + Bk.w) + tmax) - bestA > -C.emit_win;                                                     \
+                touch = mine && !before;                       /* the first arrival whose candidate may survive */                                     \
+            } else touch = eog == 0u;                                                                                                                  \
+        }                                                                                                                                              \
+    }                                                                                                                                                  \
+    /* arcs to be tried in the next phase A -> this wave's segment of the new list */                                                                  \
+    const unsigned long long bt = __ballot(touch);                                                                                                     \
+    if (bt) {                                                                                                                                          \
+        const int nt = __popcll(bt);                                                                                                                   \
+        if (out.new_cnt + nt > (int)JD_GOUT.seg_new) { if (lane == 0) JD_FAIL((int)JDE_NEW); }                                                         \
+        else {                                                                                                                                         \
+            if (touch) CS(V.newl + (size_t)new_base + (unsigned)(out.new_cnt + rank_in(bt)),                                                           \
+                          ((unsigned long long)(unsigned)sg << 32) | (unsigned)b);                                                                     \
+            out.new_cnt += nt;                                                                                                                         \
+        }                                                                                                                                              \
+    }                                                                                                                                                  \
+    /* closure items: the best arrival at its state so far is kept (running maximum), written to */                                                    \
+    /* this wave's item segment and - if the wave's queue has room - expanded by this wave itself */                                                   \
+    if (__ballot(mk)) {                                                                                                                                \
+        const unsigned sou = f2o(un.score);                                                                                                            \
+        const bool pass = mk && sou > (unsigned)(skc >> 32);   /* cheap pre-filter before an index is spent */                                         \
+        const unsigned long long bp = __ballot(pass);                                                                                                  \
+        const int np = __popcll(bp);                                                                                                                   \
+        JD_COUNT(JD_TALLY(clos, np));                                                                                                                  \
+        if (out.item_cnt + np > (int)JD_GOUT.seg_item) { if (lane == 0) JD_FAIL((int)JDE_ITEMS); }                                                     \
+        else if (np) {                                                                                                                                 \
+            const unsigned k = item_base + (unsigned)(out.item_cnt + rank_in(bp));                                                                     \
+            bool keep = false, first = false;                                                                                                          \
+            unsigned ceo = 0u;                                                                                                                         \
+            if (pass) {                                                                                                                                \
+                const unsigned long long key = ((unsigned long long)sou << 32) | k;                                                                    \
+                const unsigned long long cold = GMAX(&SREC_E(V.srec, C, Bk.to, p), key);                                                               \
+                keep = key > cold; first = cold == 0ULL; ceo = (unsigned)(cold >> 32);                                                                 \
+            }                                                                                                                                          \
+            const unsigned long long bk = __ballot(keep);                                                                                              \
+            const int room = QCAP - q_n;                                                                                                               \
+            const bool inq = keep && rank_in(bk) < room;       /* expanded by this wave, right after this batch */                                     \
+            if (pass) {                                                                                                                                \
+                st16(V.items, icur + k * 32u, as_v4(un));                                                                                              \
+                st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, ((keep && !inq) ? 0 : 1) | (MDL && is_tee ? inl << 2 : 0)});        \
+            }                                                                                                                                          \
+            if (inq) {                                                                                                                                 \
+                const int qi = q_n + rank_in(bk);                                                                                                      \
+                qtok[qi] = as_v4(un); qinfo[qi] = (v4i){(int)ceo, Bk.out, Bk.to, (int)k}; qrow[qi] = nrow;                                             \
+                if constexpr (MDL) qmdl[qi] = is_tee ? inl : 0;                                                                                        \
+            }                                                                                                                                          \
+            const int nk = __popcll(bk);                                                                                                               \
+            const int n_inq = nk < room ? nk : room;                                                                                                   \
+            q_n += n_inq; deferred += nk - n_inq;                                                                                                      \
+            out.item_cnt += np;                                                                                                                        \
+            jd_list_dirty<XL_>(words, out.dirty_cnt, JD_GOUT.seg_new, dirty_seg, lane, first, Bk.to);                                                                                                                  \
+        }                                                                                                                                              \
+    }
+
+// ---- the cluster kernel's side of the shared units (k_search, k_resident; the slot kernel's: jd_slot.h)
+#define JD_GOUT gout                                   // the geometry this launch writes its lists with
+#define JD_GW gw                                       // this wave's segment of them
+#define JD_FAIL(code) CS(&c.err[p], code)              // per-frame words: the stream's control block in HBM
+#define JD_BID_FINAL(key) GMAX(&c.final_key, key)
+#define JD_HIST sh.hist                                // the workgroup's share of the frame's bins, published behind the phase
+#define JD_TMAX(i) C.hmm_tmax0[i]
+#define JD_TALLY(what, n) c_##what += (n)              // JD_COUNT counters: registers, added up at the end of the phase
+#define JD_COUNT_PASS if (is_new) c_recs += __popcll(__ballot(valid)); c_keys += __popcll(__ballot(valid && kv != 0ULL))
+#define JD_X_ARRIVAL                                   /* REC_SOLE: the frame's only arrival at the state - a store, nothing to read back: +1-2 % on the heavy graphs */ \
+    const unsigned long long akey = ((unsigned long long)f2o(t.score) << 32) | ii;                                                                          \
+    if (sole) CS(&SREC_E(V.srec, C, state, p), akey);                                                                                                       \
+    else { eold = GMAX(&SREC_E(V.srec, C, state, p), akey); eo = (unsigned)(eold >> 32); }
+#define JD_ARC_AT_DEF                                  /* the arc record: lazily composed networks keep theirs in the arena */ \
+    auto arc_at = [&](int b) __attribute__((always_inline)) -> JdArc {                                                        \
+        if (LZY) { const v4i r = ld16(V.larcs, (unsigned)b * 16u); return JdArc{r.x, __int_as_float(r.y), r.z, r.w}; }        \
+        return C.arcs[b];                                                                                                     \
+    };
+#define JD_ARC_AT(b) arc_at(b)
+#define JD_NOTE_CELL(j)                                /* (diagnostics: this cell of the table is read, :411) */ \
+    if (cells) {                                                                                                  \
+        const int gj = (j == 1) ? h1.x : (j == 2) ? h1.y : (j == 3) ? h1.z : (j == 4) ? h2.x : (j == 5) ? h2.y : h2.z; \
+        const long long cell = cell0 + gj;                                                                        \
+        atomicOr(cells + (cell >> 5), 1u << (cell & 31));                                                         \
+    }
+
+// ------------------------------------------------------------------ phase A
+//
+// doHMMInternalPropagation (:899-935) + HMMInternalPropagation (:376-484).  One lane owns one
+// instance and updates its emitting states in turn, so a wave has 64 instances in flight and all
+// loads of a pass are issued back to back (no divergent load branches: lanes without work read
+// out of range and get zeros).  Waves take chunks of 64 (of ONE writer segment); survivors and exit
+// tokens go to the wave's own output segments - no atomics, no barriers.  Work items, in this
+// order: chunks of instance records (list 0), of newly entered arcs (1), of states whose arrival keys
+// of the frame before the previous one need zeroing (2).  An instance PULLS its entry token: the best
+// arrival at its arc's source state in the previous frame (StateRec::e) plus the arc's weight.
+//
+// LR: every transition matrix of the model set is plain left-to-right (state j is entered from j-1 and
+// itself, the exit state from the last emitting state; no skips): the predecessor loops become one
+// comparison per state, on a compact table a_k = log P(k-1 -> k), s_k = log P(k -> k) in LDS.
 template <int NE, bool TRPL, bool LR, bool XL, bool LZY>
 __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, StreamCtl &c, const StreamView &V,
                                         const Geo &gin, const Geo &gd, const Geo &gout, const int (&Q)[3], const int (&LN)[3], const int (&NS)[3],
@@ -744,6 +1387,7 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
     const int Q01 = Q[0] + Q[1], Qall = Q01 + Q[2];
     int c_insts = 0, c_pemit = 0, c_emit = 0, c_end = 0, c_surv = 0, c_recs = 0, c_keys = 0;
     unsigned mo = 0u;
+    constexpr bool DEFER_HIST = false;                                 // (the pipeline below has the item by the time the arithmetic starts)
     // The pass loop is software-pipelined two deep.  A pass is a chain of dependent memory round trips
     // (record -> source state's arrival key + likelihoods -> winning item) followed by arithmetic and stores, and with
     // two waves per SIMD nothing else hides them; the memory counter is in-order, so a wait for a
@@ -778,7 +1422,7 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
     };
     auto stage_k = [&](bool is_new, bool valid, int2 nb, v4i &h0, v4i &h1, v4i &h2, Tok (&tk)[NE + 1],
                        unsigned long long &kv, float (&outp)[NE]) __attribute__((always_inline)) {
-        if (is_new) {                                                  // attachNetInst :751-774, from the arc's template
+        if (is_new) {                                                  // attachNetInst :751-774, from the arc's template (the twin of jd_slot.h: slot_phase_a's new-arc branch)
             JdArc Bk;
             int4 a0, a1 = make_int4(0, 0, 0, 0);
             if (LZY) {                                                 // the arena, and the template by HMM
@@ -834,154 +1478,18 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
         Tok ntk[NE + 1];
         stage_r(un, n_is_new, n_valid, n_nb, nh0, nh1, nh2, ntk);
         FINE(1);                                                       // the winning item (+ the next record)
-        tk[0] = null_tok();
-        if (kv != 0ULL) {
-            const Tok it = as_tok(itv);
-            tk[0].score = o2f((unsigned)(kv >> 32)) + __int_as_float(h1.w);   // :562 newScore = tok.score + weight
-            tk[0].ac = it.ac; tk[0].lm = it.lm + __int_as_float(h1.w); tk[0].path = it.path;
-            if (tk[0].score < startTh) tk[0] = null_tok();            // :915-918 (a candidate is never LOG_ZERO)
-        }
+        JD_A_ENTRY_TOKEN
         Tok nw[NE + 1];
         int live_mask = 0;
         Tok ex = null_tok();
-        auto emit = [&](int j, float best, float btp, const Tok &src) __attribute__((always_inline)) {   // :408-424
-            const float sc = best - normalise;                         // :408
-            if (sc > emitTh) {                                         // :409
-                ++c_pemit;
-                if (cells) {                                           // (diagnostics: this cell of the table is read, :411)
-                    const int gj = (j == 1) ? h1.x : (j == 2) ? h1.y : (j == 3) ? h1.z : (j == 4) ? h2.x : (j == 5) ? h2.y : h2.z;
-                    const long long cell = cell0 + gj;
-                    atomicOr(cells + (cell >> 5), 1u << (cell & 31));
-                }
-                nw[j].score = sc + outp[j - 1];
-                nw[j].ac = (src.ac + btp) + outp[j - 1];
-                nw[j].lm = src.lm;
-                nw[j].path = src.path;
-                live_mask |= 1 << j;
-                if (use_hist) {                                        // Histogram::addScore, Histogram.cpp:64-100
-                    jd_hist_add(nw[j].score, C.hist_min, C.hist_max, [&]() __attribute__((always_inline)) { CS(&c.err[p], (int)JD_EHIST); },
-                                [&](int b) __attribute__((always_inline)) { atomicAdd(&sh.hist[b], 1); });
-                }
-                const unsigned so = f2o(nw[j].score);
-                mo = so > mo ? so : mo;
-            }
-        };
-        if (LR) {
-            constexpr int LRW = (NE == 3) ? 8 : 16;                    // a_1 .. a_{NE+1}, s_1 .. s_NE
-            const float4 *lt = (const float4 *)(sh.trP + tm * LRW);
-            float tw[LRW];
-#pragma unroll
-            for (int q = 0; q < LRW / 4; ++q) {
-                const float4 v = lt[q];
-                tw[4 * q] = v.x; tw[4 * q + 1] = v.y; tw[4 * q + 2] = v.z; tw[4 * q + 3] = v.w;
-            }
-#pragma unroll
-            for (int j = 1; j <= NE; ++j) {                            // :387-424 emitting state j: predecessors j-1 and j
-                nw[j] = null_tok();
-                const float a = tw[j - 1], sf = tw[NE + j];
-                const float c0 = tk[j - 1].score + a, c1 = tk[j].score + sf;
-                const bool self = c1 > c0;                             // the lower predecessor wins ties (:401)
-                Tok src;
-                src.score = 0.0f; src.ac = self ? tk[j].ac : tk[j - 1].ac; src.lm = self ? tk[j].lm : tk[j - 1].lm;
-                src.path = self ? tk[j].path : tk[j - 1].path;
-                if (j < n - 1) emit(j, self ? c1 : c0, self ? sf : a, src);
-            }
-            // exit state (:443-483): entered from the last emitting state only
-            Tok le = null_tok();
-            float ax = 0.0f;
-#pragma unroll
-            for (int i = 1; i <= NE; ++i) if (i == n - 2) { le = nw[i]; ax = tw[i]; }
-            if (le.score > LZ) { ex = le; ex.score = le.score + ax; ex.ac = le.ac + ax; if (!(ex.score > LZ)) ex = null_tok(); }
-        } else {
-            // general topologies, branch-free: every (predecessor, state) pair is evaluated and selected
-            const float *trP = trP_all + (size_t)tm * MN * MN;
-            const int *se = se_all + (size_t)tm * MN;
-#pragma unroll
-            for (int j = 1; j <= NE; ++j) {                            // :387-424 emitting state j
-                nw[j] = null_tok();
-                const int sev = se[j < MN ? j : 0];
-                const int st = sev & 0xffff, en = sev >> 16;
-                float best = 0.0f, btp = 0.0f;
-                Tok src = null_tok();
-                bool have = false;
-#pragma unroll
-                for (int i = 0; i <= NE; ++i) {                        // predecessors in ascending order, the first wins ties
-                    const bool v = (i == st) | ((i > st) & (i < en));
-                    const float tp = trP[(i < MN ? i : 0) * MN + (j < MN ? j : 0)];
-                    const float tmp = tk[i].score + tp;
-                    const bool take = v & (!have | (tmp > best));
-                    best = take ? tmp : best; btp = take ? tp : btp;
-                    src.ac = take ? tk[i].ac : src.ac; src.lm = take ? tk[i].lm : src.lm; src.path = take ? tk[i].path : src.path;
-                    have |= v;
-                }
-                if (have & (j < n - 1)) emit(j, best, btp, src);
-            }
-            // exit state (:443-483) from the NEW tokens
-            {
-                const int sev = se[n >= 2 ? n - 1 : 0];
-                const int st = sev & 0xffff, en = sev >> 16;
-                bool have = false;
-#pragma unroll
-                for (int i = 1; i <= NE; ++i) {
-                    const bool v = (i == st) | ((i > st) & (i < en));
-                    const float tp = trP[(i < MN ? i : 0) * MN + (n >= 2 ? n - 1 : 0)];
-                    const float tmp = nw[i].score + tp;
-                    const bool take = v & (!have | (tmp > ex.score));
-                    ex.score = take ? tmp : ex.score; ex.ac = take ? nw[i].ac + tp : ex.ac;
-                    ex.lm = take ? nw[i].lm : ex.lm; ex.path = take ? nw[i].path : ex.path;
-                    have |= v;
-                }
-                if (!(have & (n >= 2)) || !(ex.score > LZ)) ex = null_tok();
-            }
-        }
+        JD_A_EMIT
+        JD_A_HMM_UPDATE
         FINE(2);                                                       // arithmetic
         // stage K of the next chunk: its record has arrived during the arithmetic
         unsigned long long nkv = 0ULL;
         float noutp[NE];
         stage_k(n_is_new, n_valid, n_nb, nh0, nh1, nh2, ntk, nkv, noutp);
-        c_emit += __popc(live_mask);
-        const bool has_exit = ex.score > LZ;
-        const bool slot_live = live_mask != 0;
-        const unsigned long long bl = __ballot(slot_live), be = __ballot(has_exit);
-        if (!is_new) c_insts += __popcll(__ballot(valid));             // (new arcs are counted when they are entered)
-        JD_COUNT(if (is_new) c_recs += __popcll(__ballot(valid)); c_keys += __popcll(__ballot(valid && kv != 0ULL)));
-        // survivors: header + new tokens to this wave's segment of the next list
-        {
-            const int nsurv = __popcll(bl);
-            if (out_cnt + nsurv > (int)gout.seg_rec) { if (lane == 0) CS(&c.err[p], (int)JDE_SLOTS); }
-            else {
-                const int pos = out_cnt + rank_in(bl);
-                const unsigned doff = slot_live ? rnext + rec_chunk_off<NE>(gout.seg_rec, gw, pos >> 6) + (unsigned)(pos & 63) * 16u : OOB_OFF;
-                st16(V.rec, doff, h0); st16(V.rec, doff + 1024u, h1);
-                if (NE == 6) st16(V.rec, doff + 2048u, h2);
-#pragma unroll
-                for (int j = 1; j <= NE; ++j) st16(V.rec, doff + (unsigned)(HF + j - 1) * 1024u, as_v4(nw[j]));
-                out_cnt += nsurv;
-                c_surv += nsurv;
-            }
-            // the arc's "has an instance" flag changes at birth and death only (returnNetInst :777-797)
-            if (valid && is_new && slot_live) CS(&V.live[arc], (unsigned char)1);
-            if (valid && !slot_live && !is_new) CS(&V.live[arc], (unsigned char)0);
-        }
-        // exit tokens: frontier items of round 0 in this wave's item segment, bidding for their
-        // destination state (state-level recombination, see phase X); tokens leaving word-labelled
-        // arcs face their own threshold (:952-962) -> own key class
-        {
-            const int nex = __popcll(be);
-            if (exit_cnt + nex > (int)gout.seg_item) { if (lane == 0) CS(&c.err[p], (int)JDE_ITEMS); }
-            else {
-                const unsigned k = item_base + (unsigned)(exit_cnt + rank_in(be));
-                const unsigned ioff = has_exit ? icur + k * 32u : OOB_OFF;
-                st16(V.items, ioff, as_v4(ex));
-                const int lab = (h0.y & REC_LABELLED) ? 1 : 0;         // (the label itself is read from the arc when a Path record is written)
-                const int sole = (h0.y & REC_SOLE) ? ITEM_SOLE : 0;
-                st16(V.items, ioff + 16u, (v4i){arc, lab, h0.w, sole});
-                if (has_exit && !sole) GMAX((lab ? &SREC_BID(V.srec, C, h0.w).keyL : &SREC_BID(V.srec, C, h0.w).key0), ((unsigned long long)f2o(ex.score) << 32) | k);
-                JD_COUNT(const int nbid_ = __popcll(__ballot(has_exit && !sole)); if (lane == 0 && nbid_) atomicAdd(&sh.stat[ST_BIDS], nbid_));
-                exit_cnt += nex;
-                c_end += nex;
-            }
-        }
+        JD_A_WRITE_OUT
 #if defined(JD_FINE) && JD_FINE == 1
         // issue of stage K + stores (not drained)
         if (threadIdx.x == 0) { const long long tn_ = wall_clock64(); sh.fclk[3] += tn_ - ft_; sh.fclk[4] += 1; }
@@ -1005,19 +1513,7 @@ __device__ __forceinline__ void phase_a(const DecConst &C, SearchShared &sh, Str
             CS(&SREC_E(V.srec, C, b, p), 0ULL);
         }
     }
-    // per-wave totals -> workgroup counters (LDS)
-    mo = wave_umax(mo);
-    c_pemit = wave_sum(c_pemit); c_emit = wave_sum(c_emit);
-    if (lane == 0) {
-        if (mo) atomicMax(&sh.best, mo);
-        if (c_insts) { atomicAdd(&sh.stat[ST_INSTS], c_insts); atomicAdd(&sh.stat[ST_RECS], c_insts); }
-        if (c_pemit) atomicAdd(&sh.stat[ST_PEMIT], c_pemit);
-        if (c_emit) atomicAdd(&sh.stat[ST_EMIT], c_emit);
-        if (c_end) atomicAdd(&sh.stat[ST_END], c_end);
-        if (c_surv) { atomicAdd(&sh.stat[ST_MODELS], c_surv); atomicAdd(&sh.stat[ST_SURV], c_surv); }
-        if (c_recs) atomicAdd(&sh.stat[ST_NEWL], c_recs);
-        if (c_keys) atomicAdd(&sh.stat[ST_KEYS], c_keys);
-    }
+    jd_a_totals(sh, &sh.best, lane, mo, c_insts, c_pemit, c_emit, c_end, c_surv, c_recs, c_keys);
 }
 
 // ------------------------------------------------------------------ phase X
@@ -1090,18 +1586,7 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
     int c_arcs = 0, c_paths = 0, c_pend = 0, c_new = 0, c_xitems = 0, c_walk = 0, c_clos = 0;
     int c_ref = 0;                                                     // Path objects the reference creates for this wave's exit tokens
     unsigned mo = 0u;
-    // states whose arrival key became non-zero: zeroed by the phase A of the frame after the next one
-    auto list_dirty = [&](bool first, int state) __attribute__((always_inline)) {
-        const unsigned long long bf = __ballot(first);
-        if (bf) {
-            const int nf = __popcll(bf);
-            if (out.dirty_cnt + nf > (int)gout.seg_new) { if (lane == 0) CS(&c.err[p], (int)JDE_NEW); }
-            else {
-                if (first) CS(dirty_seg + (unsigned)(out.dirty_cnt + rank_in(bf)), state);
-                out.dirty_cnt += nf;
-            }
-        }
-    };
+    const CtlWords<XL> words{c, p};
 #pragma nounroll
     for (;;) {
         // ---- a batch of up to 64 items: the wave's own closure queue first, else the next chunk
@@ -1141,11 +1626,7 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
             if constexpr (MDL) cmdl = exit_kind ? 0 : info.w >> 2;
         }
         XFINE(0);                                                      // hop 1: the items
-        const unsigned ioff = valid ? icur + ii * 32u : OOB_OFF;
-        const bool start_tok = valid && exit_kind && info.x < 0;       // recognitionStart's token: it has traversed no arc
-        JD_COUNT(c_xitems += __popcll(__ballot(valid)));
-        const bool real = valid && !start_tok && slice_no == 0;        // an item that traversed an arc (a slice has been through all this)
-        const int state = !valid ? 0 : start_tok ? C.init_state : info.z;
+        JD_X_ITEM_HEAD
         // (the state's static record, XState: requested here, used when the item is known to go on; graphs of long rows - C.xcut
         // off - ask for state 0's every time: no branch around the loads, one cached line)
         const bool xcut = !LZY && C.xcut != 0;
@@ -1155,31 +1636,8 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
         // of an exit token's arc, the Path reservation.  A closure item this wave queued for itself brought its row
         // along - the record was read when it arrived - and has just been found the best arrival at its state: it
         // needs no load at all.
-        bool have = valid;
-        if (real && exit_kind && !init) {                              // :952-962
-            have = t.score > ((info.y != 0) ? wordTh : endTh);
-            if (have) ++c_pend;
-        }
-        // the reference's own Path count (collectPaths' trigger, :360-362): propagateToken makes one for the arc's label
-        // and one for every labelled epsilon / tee arc of the closure behind it, for EVERY token it is called with -
-        // recombination happens at the entry states only (:560) - where this build expands a state's best arrival alone
-        if (C.pcount != nullptr && ((real && exit_kind && have) || start_tok))
-            c_ref += (start_tok ? 0 : (info.y != 0 ? 1 : 0)) + C.pcount[state];
-        // Path records (:497-509) are reserved for every labelled item that passed its threshold, winner or not, so that
-        // the reservation is in flight together with the loads below: it is issued BEHIND them (the compiler waits
-        // for a returning atomic where it stands, and that wait then is the wait for the loads as well)
-        // (MDL: behind the winner test, below)
-        const bool labelled = !MDL && real && have && info.y != 0;
-        const unsigned long long blab = __ballot(labelled);
-        int pbase = 0;
-        int amdl = 0;                                                  // MDL: an exit token's model (its arc's in-label)
-        auto reserve = [&]() __attribute__((always_inline)) {
-            if (blab) {
-                const int first = __ffsll((long long)blab) - 1;
-                if (lane == first) pbase = GADD(&c.n_paths, __popcll(blab));
-                pbase = __shfl(pbase, first);
-            }
-        };
+        JD_X_THRESHOLDS
+        auto reserve = [&]() __attribute__((always_inline)) { pbase = jd_reserve_paths(words, blab, lane); };   // (called behind the loads below, see JD_X_THRESHOLDS)
         int rs, rs1;
         float fin_lazy = 0.0f;
         unsigned long long kv = 0ULL;
@@ -1210,313 +1668,27 @@ __device__ __forceinline__ void phase_x(const DecConst &C, SearchShared &sh, Str
             label = lab_on ? lb : label;
             if (LZY) {
                 rs = lr.x; rs1 = lr.x + lr.y; fin_lazy = __int_as_float(lr.w);
-                if (valid && lr.z < LZ_EXPANDED) CS(&c.err[p], (int)JDE_LAZY_INV);   // (cannot happen: the invariant of jd_lazy.h)
+                if (valid && lr.z < LZ_EXPANDED) JD_FAIL((int)JDE_LAZY_INV);   // (cannot happen: the invariant of jd_lazy.h)
             } else { rs = srow.x; rs1 = srow.y; }
             kv = ((unsigned long long)(unsigned)(info.y != 0 ? sk.w : sk.y) << 32) | (unsigned)(info.y != 0 ? sk.z : sk.x);
         }
         XFINE(1);                                                      // hop 2: state record, label, Path reservation
-        if (real) {
-            // (a closure item was the best arrival at its state when it was produced - else it was never listed for a
-            // later round - and that makes it responsible for the arcs its score was the first to make hopeful, see
-            // above: it is expanded even if a better arrival has come since)
-            const bool winner = !exit_kind || sole || ((unsigned)(kv & 0xffffffffULL) == ii && kv != 0ULL);
-            // every state that received exit-token bids is cleaned up by its winner, expanded or not (an
-            // item below its threshold still holds the key of its state if it was the best one there)
-            if (winner && exit_kind && !sole) CS(info.y != 0 ? &SREC_BID(V.srec, C, state).keyL : &SREC_BID(V.srec, C, state).key0, 0ULL);
-            have = have && winner;
-        }
-        if constexpr (MDL) {                                           // a record for every winner that passed a model or a word label
-            const int mdl = exit_kind ? amdl : cmdl;
-            const bool rec = have && real && (label != 0 || mdl != 0);
-            const unsigned long long brec = __ballot(rec);
-            if (brec) {
-                const int first = __ffsll((long long)brec) - 1;
-                if (lane == first) pbase = GADD(&c.n_paths, __popcll(brec));
-                pbase = __shfl(pbase, first);
-            }
-            if (rec) {
-                const int pp = pbase + rank_in(brec);
-                if (pp < C.cap_paths) {
-                    // PathRec {prev, frame, label, model; score, ac, lm, -}
-                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, mdl};
-                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
-                    t.path = pp;
-                    st16(V.items, ioff, as_v4(t));
-                    if (label != 0) ++c_paths;
-                } else CS(&c.err[p], (int)JDE_PATHS);
-            }
-        }
-        if (have && real) {
-            if (!MDL && info.y != 0) {
-                const int pp = pbase + rank_in(blab);
-                if (pp < C.cap_paths) {
-                    // PathRec {prev, frame, label, -; score, ac, lm, -}: two plain 16-byte stores (read by later launches only)
-                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, 0};
-                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
-                    t.path = pp;
-                    st16(V.items, ioff, as_v4(t));                     // the tokens pulled from this item carry the new history
-                    ++c_paths;
-                } else CS(&c.err[p], (int)JDE_PATHS);
-            }
-            // :513-520 final state.  bestFinalToken is reset every frame (:316) and only read by
-            // finish(), so it only has to be evaluated on the last frame that is available.
-            if (last_frame) {
-                const float fw = LZY ? fin_lazy : C.fin_w[info.z];
-                if (fw < INF) {
-                    const float cs = t.score + fw;
-                    if (cs > LZ) GMAX(&c.final_key, ((unsigned long long)f2o(cs) << 32) | ii);
-                }
-            }
-        }
-        // ---- arrival of an exit token (and of the start token) at its state: the atomic's old value is the best
-        // arrival before it.  (Closure items arrived when they were produced and carry that value; a slice carries
-        // its item's.)  The answer is first needed by the arc passes: its round trip runs beside the first arcs'.
-        unsigned eo = exit_kind ? 0u : (unsigned)info.x;               // ordered score of the best arrival before this one (0: none)
-        unsigned long long eold = 0ULL;
-        const bool arrive = have && exit_kind;                         // (the atomic itself: behind the first arcs' loads, below)
+        JD_X_WINNER
         XFINE(2);                                                      // winners: key reset, Path record, final state
-        // ---- The prefix walk of jd_slot.h's phase X (see there): a row of up to 57 arcs has its model arcs in descending order of
-        // w + tmax behind the arcs every arrival walks; the item walks the prefix it can enter, by the samples of the state's XState,
-        // and accounts for the rest from that record and the row's instance flags.
         int x_new = 0;
-        const bool xitem = xcut && have && slice_no == 0 && rs1 - (rs & ~7) <= 64;
-        if (xitem) {
-            const int n_entry = x0.y, n_model = x0.w;
-            if (n_model > 0) { const unsigned sw = f2o(t.score + __int_as_float(x0.z)); mo = sw > mo ? sw : mo; }
-            const int a8 = rs & ~7;
-            const GAS unsigned long long *lw = (const GAS unsigned long long *)(V.live + a8);
-            auto in_row = [&](int base) __attribute__((always_inline)) {   // the bytes of the word at `base` that belong to the row
-                const int lo = max(rs - base, 0), hi = min(rs1 - base, 8);
-                const unsigned long long mh = hi >= 8 ? ~0ULL : ((1ULL << (8 * max(hi, 0))) - 1ULL);
-                const unsigned long long ml = (1ULL << (8 * lo)) - 1ULL;
-                return 0x0101010101010101ULL & mh & ~ml;
-            };
-            int lv_row = 0;
-            {
-                unsigned long long w8[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w8[i] = (n_model > 0 && a8 + 8 * i < rs1) ? CL(lw + i) : 0ULL;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * i));
-            }
-            if (__ballot(n_model > 0 && a8 + 32 < rs1)) {               // (some lane's row goes on: the second batch)
-                unsigned long long w8[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w8[i] = (n_model > 0 && a8 + 8 * (4 + i) < rs1) ? CL(lw + 4 + i) : 0ULL;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * (4 + i)));
-            }
-            x_new = n_model - lv_row;
-            if (can_filter && n_entry > 0) {
-                const float lim = (bestA - C.emit_win) - (1.0f + 1e-5f * (fabsf(bestA) + fabsf(t.score)));
-                const int kx[XNCAND] = {x1.x, x1.y, x1.z, x1.w, x2.x, x2.y, x2.z, x2.w, x3.x, x3.y, x3.z, x3.w};
-                int P = n_entry;
-#pragma unroll
-                for (int i = XNCAND - 1; i >= 0; --i)
-                    if (xcand(i) < n_entry && t.score + __int_as_float(kx[i]) <= lim) P = xcand(i);
-                c_arcs += n_entry - P;
-                rs1 -= n_entry - P;
-            }
-        }
-        // ---- A state with thousands of out-arcs (a history with 10^4 successors) would keep this wave busy
-        // for hundreds of passes while the cluster waits at the barrier: the wave walks the first X_SLICE
-        // arcs itself and hands the rest on as SLICES - items of the next round (flag 2 + slice number)
-        // that carry the token as it stands now and skip everything above; the cluster shares them out.
-        int alo = rs, ahi = rs1;
-        if (slice_no > 0) { alo = rs + slice_no * X_SLICE; ahi = min(rs1, alo + X_SLICE); }
-        int n_slices = 0;
-        if (have && slice_no == 0 && rs1 - rs > X_SLICE) { n_slices = (rs1 - rs - 1) / X_SLICE; ahi = rs + X_SLICE; }
-        // ---- pooled arc walk: exclusive prefix of the items' out-degrees
-        const int deg = have ? ahi - alo : 0;
-        int incl = deg;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (lane >= o) incl += y; }
-        const int tot = __shfl(incl, 63);
-        wpfx[lane] = incl - deg;                                       // wave-private: a wave's LDS operations are ordered
-        // owner of pooled arc a = largest g with wpfx[g] <= a; its arc record is fetched one pass ahead
-        auto owner_of = [&](int a) __attribute__((always_inline)) { int g = 0;
-#pragma unroll
-            for (int stp = 32; stp > 0; stp >>= 1) if (wpfx[g + stp] <= a) g += stp;
-            return g; };
-        int g_nx = owner_of(lane);
-        int b_nx = __shfl(alo, g_nx) + (lane - wpfx[g_nx]);
-        JdArc Bk_nx = {0, 0.0f, 0, 0};
-        auto arc_at = [&](int b) __attribute__((always_inline)) -> JdArc {
-            if (LZY) { const v4i r = ld16(V.larcs, (unsigned)b * 16u); return JdArc{r.x, __int_as_float(r.y), r.z, r.w}; }
-            return C.arcs[b];
-        };
-        // ... and so is its "has an instance" flag (a byte per arc: the arcs of a state share a sector).  These loads are
-        // UNCONDITIONAL (lanes without an arc read arc 0): a load inside a branch reaches the loop-carried registers
-        // through a copy at the join, and the compiler waits for it right there - the "pass ahead" was a pass behind.
-        int lv_nx = 0;
-        { const int bq = lane < tot ? b_nx : 0; Bk_nx = arc_at(bq); lv_nx = CL(V.live + bq); }
-        // the arrival (see above), issued behind the first arcs' loads: the compiler waits for a returning atomic where it
-        // stands, so this way the two round trips are one
-        if (arrive) {
-            const unsigned long long akey = ((unsigned long long)f2o(t.score) << 32) | ii;
-            if (sole) CS(&SREC_E(V.srec, C, state, p), akey);          // (REC_SOLE: the frame's only arrival at the state - a store, nothing to read back: +1-2 % on
-                                                                       // the heavy graphs; the slot kernel keeps the atomic - the branch cost its headline 1.5 %)
-            else { eold = GMAX(&SREC_E(V.srec, C, state, p), akey); eo = (unsigned)(eold >> 32); }
-        }
-        list_dirty(arrive && eold == 0ULL, state);
-        if (eo == 0u) c_new += x_new;                                  // (the first arrival at the state in this frame: :899-935 tries them all)
-        if (__ballot(n_slices > 0)) {
-            for (unsigned long long bs = __ballot(n_slices > 0); bs; bs &= bs - 1) {
-                const int src = __ffsll((long long)bs) - 1;
-                const int ns = __shfl(n_slices, src);
-                const v4i tv = {__shfl(__float_as_int(t.score), src), __shfl(__float_as_int(t.ac), src),
-                                __shfl(__float_as_int(t.lm), src), __shfl(t.path, src)};
-                const int sx = __shfl((int)eo, src), sy = __shfl(label, src), sz = __shfl(state, src);
-                for (int j0 = 0; j0 < ns; j0 += 64) {
-                    const int nj = min(64, ns - j0);
-                    if (out.item_cnt + nj > (int)gout.seg_item) { if (lane == 0) CS(&c.err[p], (int)JDE_ITEMS); break; }
-                    if (lane < nj) {
-                        const unsigned k = item_base + (unsigned)(out.item_cnt + lane);
-                        st16(V.items, icur + k * 32u, tv);
-                        st16(V.items, icur + k * 32u + 16u, (v4i){sx, sy, sz, 2 | ((j0 + lane + 1) << 2)});
-                    }
-                    out.item_cnt += nj; deferred += nj;
-                }
-            }
-        }
+        const bool xitem = jd_prefix_walk(C, V, xcut, have, slice_no, rs, rs1, x0, x1, x2, x3, t.score, bestA, can_filter, mo, c_arcs, x_new);
+        JD_X_POOL
+        JD_X_ARRIVE
 
         XFINE(3);                                                      // prefix + hop 3: the first 64 arcs (+ the arrival's answer)
 #pragma nounroll
         for (int a0 = 0; a0 < tot; a0 += 64) {
             XFINE_COUNT(6);
-            const int a = a0 + lane;
-            const int g = g_nx, b = b_nx;
-            const JdArc Bk = Bk_nx;
-            const int lv = lv_nx;
-            // the next pass's arcs (LDS look-ups only; the loads are issued BEHIND this pass's own, see below)
-            g_nx = owner_of(a + 64);
-            const int alo_nx = __shfl(alo, g_nx);                      // (every lane takes part: its owner may be a lane that has no next arc itself)
-            b_nx = (a + 64 < tot) ? alo_nx + (a + 64 - wpfx[g_nx]) : 0;
-            Tok tg;
-            tg.score = __shfl(t.score, g); tg.ac = __shfl(t.ac, g);
-            tg.lm = __shfl(t.lm, g); tg.path = __shfl(t.path, g);
-            const unsigned eog = (unsigned)__shfl((int)eo, g);         // best arrival at the owner's state before it (ordered; 0: none)
-            const int sgx = __shfl(state | (xitem ? (int)0x80000000 : 0), g);   // (+ the owner's "counted per state" flag)
-            const int sg = sgx & 0x7fffffff;
-            bool mk = false, touch = false;
-            Tok un = null_tok();
-            // Everything a pass READS is requested before anything is waited for - one memory round trip: the
-            // model's constant of an entry arc, and the state record of the destination of every arc that can
-            // produce a closure item (its arrival key as a pre-filter: hot history states receive many arrivals,
-            // and an atomic on a contended key costs far more than this load; its row for the item to carry).
-            const bool on = a < tot;
-            const int inl = Bk.in & ~ARC_FLAGS;
-            const bool entry = on && inl != 0;
-            const bool is_tee = entry && (Bk.in & TEE_FLAG) != 0;
-            const float ns = tg.score + Bk.w;                          // (:535 / :562: the same sum either way)
-            const unsigned so = f2o(ns);
-            unsigned long long skc = 0ULL;
-            const float tmax = C.hmm_tmax0[entry ? inl - 1 : 0];       // (used for entry arcs without an instance; unconditional, see above)
-            int2 nrow = make_int2(0, 0);
-            {
-                const unsigned doff = ((on && inl == 0) || is_tee) ? SREC_E_OFF(C, Bk.to, p) : OOB_OFF;
-                const unsigned long long se = ld8(V.srec_r, doff);
-                if (!LZY) { const int ti = doff != OOB_OFF ? Bk.to : 0; const int r0 = C.row_ptr[ti]; nrow = make_int2(r0, C.row_ptr[ti + 1] - r0); }
-                // the next pass's arc records and flags: in flight during this pass, and - issued behind the loads this
-                // pass waits for (loads return in order) - not waited for before the next one
-                Bk_nx = arc_at(b_nx); lv_nx = CL(V.live + b_nx);
-                skc = se;
-            }
-            if (on) ++c_arcs;
-            JD_COUNT(c_walk += __popcll(__ballot(on)));
-            if (on && inl == 0) {                                      // :533-540 epsilon input
-                un = tg;
-                un.score = ns;
-                un.lm = tg.lm + Bk.w;
-                mk = un.score > endTh;
-            } else if (is_tee) {                                       // :584-600 tee model
-                // (an atomic load: never merged with the LDS one into a flat load)
-                const float tee = tee_lds ? sh.tee[inl - 1] : CL(C.hmm_tee + (inl - 1));
-                const float ns2 = ns + tee;
-                un.score = ns2;
-                un.ac = tg.ac + tee;
-                un.lm = tg.lm + Bk.w;
-                un.path = tg.path;
-                mk = ns2 > ((Bk.out != 0) ? wordTh : endTh);
-            }
-            if (entry) {                                               // :560-582 entry-token recombination: pulled by the next phase A
-                mo = so > mo ? so : mo;                                // :572-573
-                if (lv == 0) {                                         // no instance: attachNetInst :751-774
-                    if (sgx >= 0 && eog == 0u) ++c_new;                // (counted once, by the first arrival at the state; prefix walks: per state, above)
-                    if (can_filter) {
-                        const bool mine = (ns + tmax) - bestA > -C.emit_win;
-                        const bool before = eog != 0u && ((o2f(eog) + Bk.w) + tmax) - bestA > -C.emit_win;
-                        touch = mine && !before;                       // the first arrival whose candidate may survive
-                    } else touch = eog == 0u;
-                }
-            }
-            // arcs to be tried in the next phase A -> this wave's segment of the new list
-            const unsigned long long bt = __ballot(touch);
-            if (bt) {
-                const int nt = __popcll(bt);
-                if (out.new_cnt + nt > (int)gout.seg_new) { if (lane == 0) CS(&c.err[p], (int)JDE_NEW); }
-                else {
-                    if (touch) CS(V.newl + (size_t)new_base + (unsigned)(out.new_cnt + rank_in(bt)),
-                                  ((unsigned long long)(unsigned)sg << 32) | (unsigned)b);
-                    out.new_cnt += nt;
-                }
-            }
-            // closure items: the best arrival at its state so far is kept (running maximum), written to
-            // this wave's item segment and - if the wave's queue has room - expanded by this wave itself
-            if (__ballot(mk)) {
-                const unsigned sou = f2o(un.score);
-                const bool pass = mk && sou > (unsigned)(skc >> 32);   // cheap pre-filter before an index is spent
-                const unsigned long long bp = __ballot(pass);
-                const int np = __popcll(bp);
-                JD_COUNT(c_clos += np);
-                if (out.item_cnt + np > (int)gout.seg_item) { if (lane == 0) CS(&c.err[p], (int)JDE_ITEMS); }
-                else if (np) {
-                    const unsigned k = item_base + (unsigned)(out.item_cnt + rank_in(bp));
-                    bool keep = false, first = false;
-                    unsigned ceo = 0u;
-                    if (pass) {
-                        const unsigned long long key = ((unsigned long long)sou << 32) | k;
-                        const unsigned long long cold = GMAX(&SREC_E(V.srec, C, Bk.to, p), key);
-                        keep = key > cold; first = cold == 0ULL; ceo = (unsigned)(cold >> 32);
-                    }
-                    const unsigned long long bk = __ballot(keep);
-                    const int room = QCAP - q_n;
-                    const bool inq = keep && rank_in(bk) < room;       // expanded by this wave, right after this batch
-                    if (pass) {
-                        st16(V.items, icur + k * 32u, as_v4(un));
-                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, ((keep && !inq) ? 0 : 1) | (MDL && is_tee ? inl << 2 : 0)});
-                    }
-                    if (inq) {
-                        const int qi = q_n + rank_in(bk);
-                        qtok[qi] = as_v4(un); qinfo[qi] = (v4i){(int)ceo, Bk.out, Bk.to, (int)k}; qrow[qi] = nrow;
-                        if constexpr (MDL) qmdl[qi] = is_tee ? inl : 0;
-                    }
-                    const int nk = __popcll(bk);
-                    const int n_inq = nk < room ? nk : room;
-                    q_n += n_inq; deferred += nk - n_inq;
-                    out.item_cnt += np;
-                    list_dirty(first, Bk.to);
-                }
-            }
+            JD_X_ARC_STEP
         }
         XFINE(4);                                                      // the arc passes of this batch
     }
-    mo = wave_umax(mo);
-    c_arcs = wave_sum(c_arcs); c_paths = wave_sum(c_paths); c_pend = wave_sum(c_pend); c_new = wave_sum(c_new);
-    if (C.pcount != nullptr) {
-        c_ref = wave_sum(c_ref);
-        if (lane == 0 && c_ref) (void)GADD(&c.n_paths_ref, c_ref);
-    }
-    if (lane == 0) {
-        if (mo) atomicMax(&sh.best, mo);
-        if (c_arcs) atomicAdd(&sh.stat[ST_ARCS], c_arcs);
-        if (c_paths) atomicAdd(&sh.stat[ST_PATHS], c_paths);
-        if (c_pend) atomicAdd(&sh.stat[ST_PEND], c_pend);
-        if (c_xitems) atomicAdd(&sh.stat[ST_XITEMS], c_xitems);
-        if (c_walk) atomicAdd(&sh.stat[ST_WALK], c_walk);
-        if (c_clos) atomicAdd(&sh.stat[ST_CLOS], c_clos);
-        if (c_new) { atomicAdd(&sh.stat[ST_MODELS], c_new); atomicAdd(&sh.new_all, c_new); }   // attached instances are active models (:981)
-    }
+    jd_x_totals(sh, words, &sh.best, C.pcount != nullptr, lane, mo, c_arcs, c_paths, c_pend, c_new, c_ref, c_xitems, c_walk, c_clos);
 }
 
 // ------------------------------------------------------------------ one stream, one launch

@@ -7,6 +7,13 @@
 // HBM (instance records, frontier items, StateRec, wave-segmented lists, StreamCtl) are those of jd_search.h: a stream
 // may be served by either kernel, the collection / finish / init kernels do not know the difference.
 //
+// What is shared and what is this file's.  The arithmetic is not copied: what one lane does with an instance, an item or an arc is
+// the text of jd_search.h's section "the token-passing arithmetic" (JD_A_* / JD_X_*), expanded in slot_phase_a / slot_phase_x below
+// with this kernel's side of the differences (the macro block in front of slot_phase_a: per-frame words in LDS, counters as LDS
+// atomics, eight segments).  This file's own: the loop structure of the two phases (slot_grab + locate, no pipeline), the loads that
+// bring a pass or an item its data, slot_run (a frame as workgroup barriers), the kernels, their mailbox.  One piece of arithmetic
+// is still here beside its twin: the record header of a new instance (slot_phase_a; jd_search.h says why).
+//
 // Why a second kernel.  run_stream (jd_search.h) serves a stream with a CLUSTER of workgroups: its lists are sized for
 // 512 writer waves, its counters live in HBM behind agent-scope atomics, a frame is a chain of cluster barriers and
 // work-list round trips, and inlined it needs 256 VGPRs and 86 KB of LDS - one workgroup per CU, two waves per SIMD,
@@ -25,7 +32,6 @@
 //     descending order of the bound the pruning test runs on (XState, jd_search.h).
 #pragma once
 
-#define XLW 4                        // phase X: 8-byte words of a row's instance flags requested at once (XState)
 #ifndef SLOT_WPE
 #define SLOT_WPE 4                   // waves per SIMD the kernel is compiled for (2 workgroups of SW = 8 waves per CU)
 #endif
@@ -66,6 +72,12 @@ struct SlotShared {
 };
 
 __device__ __forceinline__ void slot_err(SlotShared &sh, int code) { atomicCAS(&sh.err, 0, code); }
+struct SlotWords {                                                     // (jd_search.h: CtlWords - this kernel's are in LDS)
+    SlotShared &sh;
+    __device__ __forceinline__ void fail(int code) const { slot_err(sh, code); }
+    __device__ __forceinline__ int take_paths(int n) const { return atomicAdd(&sh.n_paths, n); }
+    __device__ __forceinline__ void add_paths_ref(int n) const { atomicAdd(&sh.n_paths_ref, n); }
+};
 // The thread's number, opaque to the optimiser.  Under the mailbox loop of k_slot everything a command computes once from the kernel's
 // arguments and the thread's number - loop bounds, list offsets, table addresses - is invariant ACROSS commands, and the compiler hoists
 // it out of that loop and keeps it in registers over everything (53 VGPRs spilled where the plain launch, the same code without a loop
@@ -92,7 +104,41 @@ __device__ __forceinline__ int slot_prefix8(int v, int &total)
     return lane == 0 ? 0 : ex;                                         // (lane SW holds the total)
 }
 
-// ------------------------------------------------------------------ phase A (see jd_search.h: phase_a)
+// ---- this kernel's side of the shared units (jd_search.h: "the token-passing arithmetic" says what each of these is; the cluster
+// kernel's side stands there, behind the units)
+#undef JD_GOUT
+#undef JD_GW
+#undef JD_FAIL
+#undef JD_BID_FINAL
+#undef JD_HIST
+#undef JD_TMAX
+#undef JD_TALLY
+#undef JD_COUNT_PASS
+#undef JD_NOTE_CELL
+#undef JD_ARC_AT_DEF
+#undef JD_X_ARRIVAL
+#undef JD_ARC_AT
+#define JD_GOUT g                                      // eight wave segments, always
+#define JD_GW wid
+#define JD_FAIL(code) slot_err(sh, code)               // per-frame words: LDS
+#define JD_BID_FINAL(key) atomicMax(&sh.final_key, key)
+#define JD_HIST hist                                   // the stream's bins of this frame's parity
+#define JD_TMAX(i) (tee_lds ? sh.tmax[i] : C.hmm_tmax0[i])
+// JD_COUNT counters: LDS atomics at once (no registers to spare).  (The ballots are the whole wave's: taken outside the one-lane branch.)
+#define JD_TALLY(what, n) JD_TALLY_##what(n)
+#define JD_TALLY_xitems(n) const int cnt_i_ = (n); if (lane == 0) atomicAdd(&sh.stat[ST_XITEMS], cnt_i_)
+#define JD_TALLY_walk(n) const unsigned long long cnt_w_ = (unsigned long long)(n); if (lane == 0) atomicAdd(&sh.cntX, cnt_w_)
+#define JD_TALLY_clos(n) if (lane == 0 && (n)) atomicAdd(&sh.cntX, (unsigned long long)(n) << 32)
+#define JD_COUNT_PASS const unsigned long long cnt_a_ = (unsigned long long)(is_new ? __popcll(__ballot(valid)) : 0) | ((unsigned long long)__popcll(__ballot(valid && kv != 0ULL)) << 32); \
+                      if (lane == 0) atomicAdd(&sh.cntA, cnt_a_)
+#define JD_ARC_AT_DEF
+// (REC_SOLE arrivals keep the atomic here: the branch of the cluster kernel's plain store cost the headline 1.5 %)
+#define JD_X_ARRIVAL eold = GMAX(&SREC_E(V.srec, C, state, p), ((unsigned long long)f2o(t.score) << 32) | ii); eo = (unsigned)(eold >> 32);
+#define JD_ARC_AT(b) C.arcs[b]
+#define JD_NOTE_CELL(j)                                // (the `cells` diagnostic is the cluster kernel's)
+
+// ------------------------------------------------------------------ phase A (the algorithm: jd_search.h, "phase A"; the
+// arithmetic: its JD_A_* units.  Here: how a wave gets its chunk, and an unpipelined pass)
 template <int NE, bool TRPL, bool LR, bool LLL>
 __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, const StreamView &V, const Geo &g, int Q0, int Q1, int Q2,
                                              int n0, int n1, int n2, int p, float normalise, float emitTh, float startTh,
@@ -114,6 +160,7 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
     int *const hist = sh.hist[p];
     int c_insts = 0, c_pemit = 0, c_emit = 0, c_end = 0, c_surv = 0;
     unsigned mo = 0u;
+    constexpr bool DEFER_HIST = LR;                                    // (see below: "the item is a third round trip")
     // entry `lane` of chunk ru of packed list k: its writer segment and its index there (eight segments: seven compares)
     auto locate = [&](int k, int ru, int total, bool &valid, int &w, int &idx) __attribute__((always_inline)) {
         const int gi = (ru << 6) + lane;
@@ -157,7 +204,7 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
                 for (int j = 1; j <= NE; ++j) tk[j] = ptk[j];
                 if (un < Q0) load_rec(un, pvalid, ph0, ph1, ph2, ptk);
             } else load_rec(u, valid, h0, h1, h2, tk);
-        } else {                                                       // attachNetInst :751-774, from the arc's template
+        } else {                                                       // attachNetInst :751-774, from the arc's template (the twin of jd_search.h: stage_k - see there)
             locate(1, u - Q0, n1, valid, w, idx);
             const unsigned long long e = CL(V.newl + (valid ? (size_t)w * g.seg_new + (unsigned)idx : (size_t)0));
             const int2 nb = valid ? make_int2((int)(unsigned)e, (int)(unsigned)(e >> 32)) : make_int2(0, 0);   // {arc, source state}
@@ -191,153 +238,13 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
         // path): its score is in the key.  Everything that decides - maxima, thresholds, the histogram - runs on scores; with plain
         // left-to-right models only state 1 can take the entry token, so the item is taken up BEHIND the arithmetic (below), its
         // round trip running beside it.  (General topologies: any state may take it - they wait for it here.)
-        tk[0] = null_tok();
-        if (kv != 0ULL) {
-            tk[0].score = o2f((unsigned)(kv >> 32)) + __int_as_float(h1.w);   // :562 newScore = tok.score + weight
-            if (!LR) {
-                const Tok it = as_tok(itv);
-                tk[0].ac = it.ac; tk[0].lm = it.lm + __int_as_float(h1.w); tk[0].path = it.path;
-            }
-            if (tk[0].score < startTh) tk[0] = null_tok();            // :915-918 (a candidate is never LOG_ZERO)
-        }
+        JD_A_ENTRY_TOKEN
         Tok nw[NE + 1];
         int live_mask = 0;
         Tok ex = null_tok();
-        auto emit = [&](int j, float best, float btp, const Tok &src) __attribute__((always_inline)) {   // :408-424
-            const float sc = best - normalise;                         // :408
-            if (sc > emitTh) {                                         // :409
-                ++c_pemit;
-                nw[j].score = sc + outp[j - 1];
-                nw[j].ac = (src.ac + btp) + outp[j - 1];
-                nw[j].lm = src.lm;
-                nw[j].path = src.path;
-                live_mask |= 1 << j;
-                if (use_hist) {                                        // Histogram::addScore, Histogram.cpp:64-100
-                    jd_hist_add(nw[j].score, C.hist_min, C.hist_max, [&]() __attribute__((always_inline)) { slot_err(sh, (int)JD_EHIST); },
-                                [&](int b) __attribute__((always_inline)) { atomicAdd(&hist[b], 1); });
-                }
-                const unsigned so = f2o(nw[j].score);
-                mo = so > mo ? so : mo;
-            }
-        };
-        if (LR) {
-            constexpr int LRW = (NE == 3) ? 8 : 16;                    // a_1 .. a_{NE+1}, s_1 .. s_NE
-            const float4 *lt = (const float4 *)(sh.trP + tm * LRW);
-            float tw[LRW];
-#pragma unroll
-            for (int q = 0; q < LRW / 4; ++q) {
-                const float4 v = lt[q];
-                tw[4 * q] = v.x; tw[4 * q + 1] = v.y; tw[4 * q + 2] = v.z; tw[4 * q + 3] = v.w;
-            }
-            bool entry_won = false;
-#pragma unroll
-            for (int j = 1; j <= NE; ++j) {                            // :387-424 emitting state j: predecessors j-1 and j
-                nw[j] = null_tok();
-                const float a = tw[j - 1], sf = tw[NE + j];
-                const float c0 = tk[j - 1].score + a, c1 = tk[j].score + sf;
-                const bool self = c1 > c0;                             // the lower predecessor wins ties (:401)
-                Tok src;
-                src.score = 0.0f; src.ac = self ? tk[j].ac : tk[j - 1].ac; src.lm = self ? tk[j].lm : tk[j - 1].lm;
-                src.path = self ? tk[j].path : tk[j - 1].path;
-                if (j < n - 1) emit(j, self ? c1 : c0, self ? sf : a, src);
-                if (j == 1) entry_won = !self;
-            }
-            if ((live_mask & 2) && entry_won) {                        // state 1 took the entry token: its history, from the item (:562-566)
-                const Tok it = as_tok(itv);
-                nw[1].ac = (it.ac + tw[0]) + outp[0];
-                nw[1].lm = it.lm + __int_as_float(h1.w);
-                nw[1].path = it.path;
-            }
-            // exit state (:443-483): entered from the last emitting state only
-            Tok le = null_tok();
-            float ax = 0.0f;
-#pragma unroll
-            for (int i = 1; i <= NE; ++i) if (i == n - 2) { le = nw[i]; ax = tw[i]; }
-            if (le.score > LZ) { ex = le; ex.score = le.score + ax; ex.ac = le.ac + ax; if (!(ex.score > LZ)) ex = null_tok(); }
-        } else {
-            // general topologies, branch-free: every (predecessor, state) pair is evaluated and selected
-            const float *trP = trP_all + (size_t)tm * MN * MN;
-            const int *se = se_all + (size_t)tm * MN;
-#pragma unroll
-            for (int j = 1; j <= NE; ++j) {                            // :387-424 emitting state j
-                nw[j] = null_tok();
-                const int sev = se[j < MN ? j : 0];
-                const int st = sev & 0xffff, en = sev >> 16;
-                float best = 0.0f, btp = 0.0f;
-                Tok src = null_tok();
-                bool have = false;
-#pragma unroll
-                for (int i = 0; i <= NE; ++i) {                        // predecessors in ascending order, the first wins ties
-                    const bool v = (i == st) | ((i > st) & (i < en));
-                    const float tp = trP[(i < MN ? i : 0) * MN + (j < MN ? j : 0)];
-                    const float tmp = tk[i].score + tp;
-                    const bool take = v & (!have | (tmp > best));
-                    best = take ? tmp : best; btp = take ? tp : btp;
-                    src.ac = take ? tk[i].ac : src.ac; src.lm = take ? tk[i].lm : src.lm; src.path = take ? tk[i].path : src.path;
-                    have |= v;
-                }
-                if (have & (j < n - 1)) emit(j, best, btp, src);
-            }
-            // exit state (:443-483) from the NEW tokens
-            {
-                const int sev = se[n >= 2 ? n - 1 : 0];
-                const int st = sev & 0xffff, en = sev >> 16;
-                bool have = false;
-#pragma unroll
-                for (int i = 1; i <= NE; ++i) {
-                    const bool v = (i == st) | ((i > st) & (i < en));
-                    const float tp = trP[(i < MN ? i : 0) * MN + (n >= 2 ? n - 1 : 0)];
-                    const float tmp = nw[i].score + tp;
-                    const bool take = v & (!have | (tmp > ex.score));
-                    ex.score = take ? tmp : ex.score; ex.ac = take ? nw[i].ac + tp : ex.ac;
-                    ex.lm = take ? nw[i].lm : ex.lm; ex.path = take ? nw[i].path : ex.path;
-                    have |= v;
-                }
-                if (!(have & (n >= 2)) || !(ex.score > LZ)) ex = null_tok();
-            }
-        }
-        c_emit += __popc(live_mask);
-        const bool has_exit = ex.score > LZ;
-        const bool slot_live = live_mask != 0;
-        const unsigned long long bl = __ballot(slot_live), be = __ballot(has_exit);
-        if (!is_new) c_insts += __popcll(__ballot(valid));             // (new arcs are counted when they are entered)
-        JD_COUNT(const unsigned long long cnt_a_ = (unsigned long long)(is_new ? __popcll(__ballot(valid)) : 0) | ((unsigned long long)__popcll(__ballot(valid && kv != 0ULL)) << 32);
-                 if (lane == 0) atomicAdd(&sh.cntA, cnt_a_));         // (the ballots are the whole wave's: taken outside the one-lane branch)
-        // survivors: header + new tokens to this wave's segment of the next list
-        {
-            const int nsurv = __popcll(bl);
-            if (out_cnt + nsurv > (int)g.seg_rec) { if (lane == 0) slot_err(sh, (int)JDE_SLOTS); }
-            else {
-                const int pos = out_cnt + rank_in(bl);
-                const unsigned doff = slot_live ? rnext + rec_chunk_off<NE>(g.seg_rec, wid, pos >> 6) + (unsigned)(pos & 63) * 16u : OOB_OFF;
-                st16(V.rec, doff, h0); st16(V.rec, doff + 1024u, h1);
-                if (NE == 6) st16(V.rec, doff + 2048u, h2);
-#pragma unroll
-                for (int j = 1; j <= NE; ++j) st16(V.rec, doff + (unsigned)(HF + j - 1) * 1024u, as_v4(nw[j]));
-                out_cnt += nsurv;
-                c_surv += nsurv;
-            }
-            // the arc's "has an instance" flag changes at birth and death only (returnNetInst :777-797)
-            if (valid && is_new && slot_live) CS(&V.live[arc], (unsigned char)1);
-            if (valid && !slot_live && !is_new) CS(&V.live[arc], (unsigned char)0);
-        }
-        // exit tokens: frontier items of round 0 in this wave's item segment, bidding for their destination state
-        {
-            const int nex = __popcll(be);
-            if (exit_cnt + nex > (int)g.seg_item) { if (lane == 0) slot_err(sh, (int)JDE_ITEMS); }
-            else {
-                const unsigned k = item_base + (unsigned)(exit_cnt + rank_in(be));
-                const unsigned ioff = has_exit ? icur + k * 32u : OOB_OFF;
-                st16(V.items, ioff, as_v4(ex));
-                const int lab = (h0.y & REC_LABELLED) ? 1 : 0;
-                const int sole = (h0.y & REC_SOLE) ? ITEM_SOLE : 0;      // (jd_search.h: REC_SOLE - nobody to recombine with, no bid)
-                st16(V.items, ioff + 16u, (v4i){arc, lab, h0.w, sole});
-                if (has_exit && !sole) GMAX((lab ? &SREC_BID(V.srec, C, h0.w).keyL : &SREC_BID(V.srec, C, h0.w).key0), ((unsigned long long)f2o(ex.score) << 32) | k);
-                JD_COUNT(const int nbid_ = __popcll(__ballot(has_exit && !sole)); if (lane == 0 && nbid_) atomicAdd(&sh.stat[ST_BIDS], nbid_));
-                exit_cnt += nex;
-                c_end += nex;
-            }
-        }
+        JD_A_EMIT
+        JD_A_HMM_UPDATE
+        JD_A_WRITE_OUT
         u = un;
     }
     // key clean-up: the arrival keys e[p] of the frame before the previous one (see jd_search.h)
@@ -351,19 +258,11 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
             CS(&SREC_E(V.srec, C, b, p), 0ULL);
         }
     }
-    mo = wave_umax(mo);
-    c_pemit = wave_sum(c_pemit); c_emit = wave_sum(c_emit);
-    if (lane == 0) {
-        if (mo) atomicMax(&sh.bestA[p], mo);
-        if (c_insts) { atomicAdd(&sh.stat[ST_INSTS], c_insts); atomicAdd(&sh.stat[ST_RECS], c_insts); }
-        if (c_pemit) atomicAdd(&sh.stat[ST_PEMIT], c_pemit);
-        if (c_emit) atomicAdd(&sh.stat[ST_EMIT], c_emit);
-        if (c_end) atomicAdd(&sh.stat[ST_END], c_end);
-        if (c_surv) { atomicAdd(&sh.stat[ST_MODELS], c_surv); atomicAdd(&sh.stat[ST_SURV], c_surv); }
-    }
+    jd_a_totals(sh, &sh.bestA[p], lane, mo, c_insts, c_pemit, c_emit, c_end, c_surv, 0, 0);
 }
 
-// ------------------------------------------------------------------ phase X (see jd_search.h: phase_x)
+// ------------------------------------------------------------------ phase X (the algorithm: jd_search.h, "phase X"; the
+// arithmetic: its JD_X_* units.  Here: how a wave gets its items, and the loads of an item)
 // xp / xc / xs: lanes 0 .. SW-1 of the calling wave hold, per writer segment, the chunks before it, its items and where
 // they start (built by the caller from the counts in LDS: every wave has its own copy - no barrier, no shared table).
 // MDL: model-level output, as in phase_x.
@@ -390,17 +289,9 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
     int *qmdl = qmdl_[MDL ? wid : 0];
     int c_arcs = 0, c_paths = 0, c_pend = 0, c_new = 0, c_ref = 0;
     unsigned mo = 0u;
-    auto list_dirty = [&](bool first, int state) __attribute__((always_inline)) {
-        const unsigned long long bf = __ballot(first);
-        if (bf) {
-            const int nf = __popcll(bf);
-            if (out.dirty_cnt + nf > (int)g.seg_new) { if (lane == 0) slot_err(sh, (int)JDE_NEW); }
-            else {
-                if (first) CS(dirty_seg + (unsigned)(out.dirty_cnt + rank_in(bf)), state);
-                out.dirty_cnt += nf;
-            }
-        }
-    };
+    const SlotWords words{sh};
+    constexpr bool LZY = false;                                        // (lazily composed networks: cluster kernel only)
+    const float fin_lazy = 0.0f;
 #pragma nounroll
     for (;;) {
         bool valid, exit_kind;
@@ -438,31 +329,12 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
             if (!exit_kind && (info.w & 3) == 2) slice_no = info.w >> 2;
             if constexpr (MDL) cmdl = exit_kind ? 0 : info.w >> 2;
         }
-        const unsigned ioff = valid ? icur + ii * 32u : OOB_OFF;
-        const bool start_tok = valid && exit_kind && info.x < 0;       // recognitionStart's token: it has traversed no arc
-        JD_COUNT(const int cnt_i_ = __popcll(__ballot(valid)); if (lane == 0) atomicAdd(&sh.stat[ST_XITEMS], cnt_i_));
-        const bool real = valid && !start_tok && slice_no == 0;
-        const int state = !valid ? 0 : start_tok ? C.init_state : info.z;
+        JD_X_ITEM_HEAD
         // the state's static record (XState): requested here, used when the item is known to go on
         const int4 *xq = (const int4 *)(C.xst + state);
         const int4 x0 = xq[0], x1 = xq[1], x2 = xq[2], x3 = xq[3];
-        bool have = valid;
-        if (real && exit_kind && !init) {                              // :952-962
-            have = t.score > ((info.y != 0) ? wordTh : endTh);
-            if (have) ++c_pend;
-        }
-        if (C.pcount != nullptr && ((real && exit_kind && have) || start_tok))
-            c_ref += (start_tok ? 0 : (info.y != 0 ? 1 : 0)) + C.pcount[state];
-        // Path records (:497-509) are reserved for every labelled item that passed its threshold, winner or not: the cursor is in LDS
-        const bool labelled = !MDL && real && have && info.y != 0;    // (MDL: behind the winner test, below)
-        const unsigned long long blab = __ballot(labelled);
-        int pbase = 0;
-        int amdl = 0;                                                  // MDL: an exit token's model (its arc's in-label)
-        if (blab) {
-            const int first = __ffsll((long long)blab) - 1;
-            if (lane == first) pbase = atomicAdd(&sh.n_paths, __popcll(blab));
-            pbase = __shfl(pbase, first);
-        }
+        JD_X_THRESHOLDS
+        pbase = jd_reserve_paths(words, blab, lane);                                             // (the cursor is in LDS: nothing to issue it behind)
         int rs, rs1;
         unsigned long long kv = 0ULL;
         int label = exit_kind ? 0 : info.y;
@@ -481,266 +353,35 @@ __device__ __forceinline__ void slot_phase_x(const DecConst &C, SlotShared &sh, 
             rs = srow.x; rs1 = srow.y;
             kv = ((unsigned long long)(unsigned)(info.y != 0 ? sk.w : sk.y) << 32) | (unsigned)(info.y != 0 ? sk.z : sk.x);
         }
-        if (real) {
-            const bool winner = !exit_kind || sole || ((unsigned)(kv & 0xffffffffULL) == ii && kv != 0ULL);
-            if (winner && exit_kind && !sole) CS(info.y != 0 ? &SREC_BID(V.srec, C, state).keyL : &SREC_BID(V.srec, C, state).key0, 0ULL);
-            have = have && winner;
-        }
-        if constexpr (MDL) {                                           // a record for every winner that passed a model or a word label
-            const int mdl = exit_kind ? amdl : cmdl;
-            const bool rec = have && real && (label != 0 || mdl != 0);
-            const unsigned long long brec = __ballot(rec);
-            if (brec) {
-                const int first = __ffsll((long long)brec) - 1;
-                if (lane == first) pbase = atomicAdd(&sh.n_paths, __popcll(brec));
-                pbase = __shfl(pbase, first);
-            }
-            if (rec) {
-                const int pp = pbase + rank_in(brec);
-                if (pp < C.cap_paths) {
-                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, mdl};
-                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
-                    t.path = pp;
-                    st16(V.items, ioff, as_v4(t));
-                    if (label != 0) ++c_paths;
-                } else slot_err(sh, (int)JDE_PATHS);
-            }
-        }
-        if (have && real) {
-            if (!MDL && info.y != 0) {
-                const int pp = pbase + rank_in(blab);
-                if (pp < C.cap_paths) {
-                    V.paths[2 * (size_t)pp] = (v4i){t.path, pframe, label, 0};
-                    V.paths[2 * (size_t)pp + 1] = (v4i){__float_as_int(t.score), __float_as_int(t.ac), __float_as_int(t.lm), 0};
-                    t.path = pp;
-                    st16(V.items, ioff, as_v4(t));                     // the tokens pulled from this item carry the new history
-                    ++c_paths;
-                } else slot_err(sh, (int)JDE_PATHS);
-            }
-            if (last_frame) {                                          // :513-520 final state
-                const float fw = C.fin_w[info.z];
-                if (fw < INF) {
-                    const float cs = t.score + fw;
-                    if (cs > LZ) atomicMax(&sh.final_key, ((unsigned long long)f2o(cs) << 32) | ii);
-                }
-            }
-        }
-        unsigned eo = exit_kind ? 0u : (unsigned)info.x;               // ordered score of the best arrival before this one (0: none)
-        unsigned long long eold = 0ULL;
-        const bool arrive = have && exit_kind;
-        // The arcs of the state that enter a model stand in descending order of w + tmax behind the ones every arrival walks (XState):
-        // this item can only enter a PREFIX of them - the rest fails the "hopeless candidate" test below whatever its flag says - and
-        // the prefix's upper bound comes from the samples in the state's record.  (Conservative by a margin far above the rounding of
-        // the sums: the test itself still decides inside the prefix.)  What the walk did for the arcs left out: they count as visited,
-        // the best entry-token candidate of the WHOLE row is score + wmax (float addition is monotone), and the arcs entered without
-        // an instance are the row's model arcs less the instance flags set in it - one byte per arc, the row's side by side -
-        // counted behind the arrival below.
+        JD_X_WINNER
         int x_new = 0;
-        // (rows of up to 8 * 2 * XLW - 7 arcs: their flags are one or two batches of loads; a longer row is walked whole and counted arc by arc)
-        const bool xitem = have && slice_no == 0 && rs1 - (rs & ~7) <= 16 * XLW;
-        if (xitem) {
-            const int n_entry = x0.y, n_model = x0.w;
-            if (n_model > 0) {
-                const unsigned sw = f2o(t.score + __int_as_float(x0.z));
-                mo = sw > mo ? sw : mo;
-            }
-            const int a8 = rs & ~7;
-            const GAS unsigned long long *lw = (const GAS unsigned long long *)(V.live + a8);
-            auto in_row = [&](int base) __attribute__((always_inline)) {   // the bytes of the word at `base` that belong to the row
-                const int lo = max(rs - base, 0), hi = min(rs1 - base, 8);
-                const unsigned long long mh = hi >= 8 ? ~0ULL : ((1ULL << (8 * max(hi, 0))) - 1ULL);
-                const unsigned long long ml = (1ULL << (8 * lo)) - 1ULL;
-                return 0x0101010101010101ULL & mh & ~ml;
-            };
-            int lv_row = 0;
-            {
-                unsigned long long w8[XLW];
-#pragma unroll
-                for (int i = 0; i < XLW; ++i) w8[i] = (n_model > 0 && a8 + 8 * i < rs1) ? CL(lw + i) : 0ULL;
-#pragma unroll
-                for (int i = 0; i < XLW; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * i));
-            }
-            if (__ballot(n_model > 0 && a8 + 8 * XLW < rs1)) {          // (some lane's row goes on: the second batch)
-                unsigned long long w8[XLW];
-#pragma unroll
-                for (int i = 0; i < XLW; ++i) w8[i] = (n_model > 0 && a8 + 8 * (XLW + i) < rs1) ? CL(lw + XLW + i) : 0ULL;
-#pragma unroll
-                for (int i = 0; i < XLW; ++i) lv_row += __popcll(w8[i] & in_row(a8 + 8 * (XLW + i)));
-            }
-            x_new = n_model - lv_row;
-            if (can_filter && n_entry > 0) {
-                const float lim = (bestA - C.emit_win) - (1.0f + 1e-5f * (fabsf(bestA) + fabsf(t.score)));
-                const int kx[XNCAND] = {x1.x, x1.y, x1.z, x1.w, x2.x, x2.y, x2.z, x2.w, x3.x, x3.y, x3.z, x3.w};
-                int P = n_entry;
-#pragma unroll
-                for (int i = XNCAND - 1; i >= 0; --i)
-                    if (xcand(i) < n_entry && t.score + __int_as_float(kx[i]) <= lim) P = xcand(i);
-                c_arcs += n_entry - P;
-                rs1 -= n_entry - P;
-            }
-        }
-        int alo = rs, ahi = rs1;
-        if (slice_no > 0) { alo = rs + slice_no * X_SLICE; ahi = min(rs1, alo + X_SLICE); }
-        int n_slices = 0;
-        if (have && slice_no == 0 && rs1 - rs > X_SLICE) { n_slices = (rs1 - rs - 1) / X_SLICE; ahi = rs + X_SLICE; }
-        const int deg = have ? ahi - alo : 0;
-        int incl = deg;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (lane >= o) incl += y; }
-        const int tot = __shfl(incl, 63);
-        wpfx[lane] = incl - deg;
-        auto owner_of = [&](int a) __attribute__((always_inline)) { int gg = 0;
-#pragma unroll
-            for (int stp = 32; stp > 0; stp >>= 1) if (wpfx[gg + stp] <= a) gg += stp;
-            return gg; };
-        int g_nx = owner_of(lane);
-        int b_nx = __shfl(alo, g_nx) + (lane - wpfx[g_nx]);
-        JdArc Bk_nx = {0, 0.0f, 0, 0};
-        int lv_nx = 0;
-        { const int bq = lane < tot ? b_nx : 0; Bk_nx = C.arcs[bq]; lv_nx = CL(V.live + bq); }
-if (arrive) { eold = GMAX(&SREC_E(V.srec, C, state, p), ((unsigned long long)f2o(t.score) << 32) | ii); eo = (unsigned)(eold >> 32); }
-        list_dirty(arrive && eold == 0ULL, state);
-        if (eo == 0u) c_new += x_new;                                  // (the first arrival at the state in this frame: :899-935 tries them all)
-        if (__ballot(n_slices > 0)) {
-            for (unsigned long long bs = __ballot(n_slices > 0); bs; bs &= bs - 1) {
-                const int src = __ffsll((long long)bs) - 1;
-                const int ns = __shfl(n_slices, src);
-                const v4i tv = {__shfl(__float_as_int(t.score), src), __shfl(__float_as_int(t.ac), src),
-                                __shfl(__float_as_int(t.lm), src), __shfl(t.path, src)};
-                const int sx = __shfl((int)eo, src), sy = __shfl(label, src), sz = __shfl(state, src);
-                for (int j0 = 0; j0 < ns; j0 += 64) {
-                    const int nj = min(64, ns - j0);
-                    if (out.item_cnt + nj > (int)g.seg_item) { if (lane == 0) slot_err(sh, (int)JDE_ITEMS); break; }
-                    if (lane < nj) {
-                        const unsigned k = item_base + (unsigned)(out.item_cnt + lane);
-                        st16(V.items, icur + k * 32u, tv);
-                        st16(V.items, icur + k * 32u + 16u, (v4i){sx, sy, sz, 2 | ((j0 + lane + 1) << 2)});
-                    }
-                    out.item_cnt += nj; deferred += nj;
-                }
-            }
-        }
+        const bool xitem = jd_prefix_walk(C, V, true, have, slice_no, rs, rs1, x0, x1, x2, x3, t.score, bestA, can_filter, mo, c_arcs, x_new);
+        JD_X_POOL
+        JD_X_ARRIVE
 #pragma nounroll
         for (int a0 = 0; a0 < tot; a0 += 64) {
-            const int a = a0 + lane;
-            const int gg = g_nx, b = b_nx;
-            const JdArc Bk = Bk_nx;
-            const int lv = lv_nx;
-            g_nx = owner_of(a + 64);
-            const int alo_nx = __shfl(alo, g_nx);
-            b_nx = (a + 64 < tot) ? alo_nx + (a + 64 - wpfx[g_nx]) : 0;
-            Tok tg;
-            tg.score = __shfl(t.score, gg); tg.ac = __shfl(t.ac, gg);
-            tg.lm = __shfl(t.lm, gg); tg.path = __shfl(t.path, gg);
-            const unsigned eog = (unsigned)__shfl((int)eo, gg);
-            const int sgx = __shfl(state | (xitem ? (int)0x80000000 : 0), gg);   // (+ the owner's "counted per state" flag)
-            const int sg = sgx & 0x7fffffff;
-            bool mk = false, touch = false;
-            Tok un = null_tok();
-            const bool on = a < tot;
-            const int inl = Bk.in & ~ARC_FLAGS;
-            const bool entry = on && inl != 0;
-            const bool is_tee = entry && (Bk.in & TEE_FLAG) != 0;
-            const float ns = tg.score + Bk.w;                          // (:535 / :562: the same sum either way)
-            const unsigned so = f2o(ns);
-            unsigned long long skc = 0ULL;
-            const float tmax = tee_lds ? sh.tmax[entry ? inl - 1 : 0] : C.hmm_tmax0[entry ? inl - 1 : 0];
-            int2 nrow = make_int2(0, 0);
-            {
-                const unsigned doff = ((on && inl == 0) || is_tee) ? SREC_E_OFF(C, Bk.to, p) : OOB_OFF;
-                const unsigned long long se = ld8(V.srec_r, doff);
-                { const int ti = doff != OOB_OFF ? Bk.to : 0; const int r0 = C.row_ptr[ti]; nrow = make_int2(r0, C.row_ptr[ti + 1] - r0); }
-                Bk_nx = C.arcs[b_nx]; lv_nx = CL(V.live + b_nx);
-                skc = se;
-            }
-            if (on) ++c_arcs;
-            JD_COUNT(const unsigned long long cnt_w_ = (unsigned long long)__popcll(__ballot(on)); if (lane == 0) atomicAdd(&sh.cntX, cnt_w_));
-            if (on && inl == 0) {                                      // :533-540 epsilon input
-                un = tg;
-                un.score = ns;
-                un.lm = tg.lm + Bk.w;
-                mk = un.score > endTh;
-            } else if (is_tee) {                                       // :584-600 tee model
-                const float tee = tee_lds ? sh.tee[inl - 1] : CL(C.hmm_tee + (inl - 1));
-                const float ns2 = ns + tee;
-                un.score = ns2;
-                un.ac = tg.ac + tee;
-                un.lm = tg.lm + Bk.w;
-                un.path = tg.path;
-                mk = ns2 > ((Bk.out != 0) ? wordTh : endTh);
-            }
-            if (entry) {                                               // :560-582 entry-token recombination: pulled by the next phase A
-                mo = so > mo ? so : mo;                                // :572-573
-                if (lv == 0) {                                         // no instance: attachNetInst :751-774
-                    if (sgx >= 0 && eog == 0u) ++c_new;                // (long rows: counted arc by arc; else per state, above)
-                    if (can_filter) {
-                        const bool mine = (ns + tmax) - bestA > -C.emit_win;
-                        const bool before = eog != 0u && ((o2f(eog) + Bk.w) + tmax) - bestA > -C.emit_win;
-                        touch = mine && !before;
-                    } else touch = eog == 0u;
-                }
-            }
-            const unsigned long long bt = __ballot(touch);
-            if (bt) {
-                const int nt = __popcll(bt);
-                if (out.new_cnt + nt > (int)g.seg_new) { if (lane == 0) slot_err(sh, (int)JDE_NEW); }
-                else {
-                    if (touch) CS(V.newl + (size_t)new_base + (unsigned)(out.new_cnt + rank_in(bt)),
-                                  ((unsigned long long)(unsigned)sg << 32) | (unsigned)b);
-                    out.new_cnt += nt;
-                }
-            }
-            if (__ballot(mk)) {
-                const unsigned sou = f2o(un.score);
-                const bool pass = mk && sou > (unsigned)(skc >> 32);
-                const unsigned long long bp = __ballot(pass);
-                const int np = __popcll(bp);
-                JD_COUNT(if (lane == 0 && np) atomicAdd(&sh.cntX, (unsigned long long)np << 32));
-                if (out.item_cnt + np > (int)g.seg_item) { if (lane == 0) slot_err(sh, (int)JDE_ITEMS); }
-                else if (np) {
-                    const unsigned k = item_base + (unsigned)(out.item_cnt + rank_in(bp));
-                    bool keep = false, first = false;
-                    unsigned ceo = 0u;
-                    if (pass) {
-                        const unsigned long long key = ((unsigned long long)sou << 32) | k;
-                        const unsigned long long cold = GMAX(&SREC_E(V.srec, C, Bk.to, p), key);
-                        keep = key > cold; first = cold == 0ULL; ceo = (unsigned)(cold >> 32);
-                    }
-                    const unsigned long long bk = __ballot(keep);
-                    const int room = QCAP - q_n;
-                    const bool inq = keep && rank_in(bk) < room;
-                    if (pass) {
-                        st16(V.items, icur + k * 32u, as_v4(un));
-                        st16(V.items, icur + k * 32u + 16u, (v4i){(int)ceo, Bk.out, Bk.to, ((keep && !inq) ? 0 : 1) | (MDL && is_tee ? inl << 2 : 0)});
-                    }
-                    if (inq) {
-                        const int qi = q_n + rank_in(bk);
-                        qtok[qi] = as_v4(un); qinfo[qi] = (v4i){(int)ceo, Bk.out, Bk.to, (int)k}; qrow[qi] = nrow;
-                        if constexpr (MDL) qmdl[qi] = is_tee ? inl : 0;
-                    }
-                    const int nk = __popcll(bk);
-                    const int n_inq = nk < room ? nk : room;
-                    q_n += n_inq; deferred += nk - n_inq;
-                    out.item_cnt += np;
-                    list_dirty(first, Bk.to);
-                }
-            }
+            JD_X_ARC_STEP
         }
     }
-    mo = wave_umax(mo);
-    c_arcs = wave_sum(c_arcs); c_paths = wave_sum(c_paths); c_pend = wave_sum(c_pend); c_new = wave_sum(c_new);
-    if (C.pcount != nullptr) {
-        c_ref = wave_sum(c_ref);
-        if (lane == 0 && c_ref) atomicAdd(&sh.n_paths_ref, c_ref);
-    }
-    if (lane == 0) {
-        if (mo) atomicMax(&sh.bestX[p], mo);
-        if (c_arcs) atomicAdd(&sh.stat[ST_ARCS], c_arcs);
-        if (c_paths) atomicAdd(&sh.stat[ST_PATHS], c_paths);
-        if (c_pend) atomicAdd(&sh.stat[ST_PEND], c_pend);
-        if (c_new) { atomicAdd(&sh.stat[ST_MODELS], c_new); atomicAdd(&sh.new_all, c_new); }
-    }
+    jd_x_totals(sh, words, &sh.bestX[p], C.pcount != nullptr, lane, mo, c_arcs, c_paths, c_pend, c_new, c_ref, 0, 0, 0);
 }
+
+// (the policy macros end with the functions that expand the shared units: nothing behind this line sees either kernel's set)
+#undef JD_GOUT
+#undef JD_GW
+#undef JD_FAIL
+#undef JD_BID_FINAL
+#undef JD_HIST
+#undef JD_TMAX
+#undef JD_TALLY
+#undef JD_TALLY_xitems
+#undef JD_TALLY_walk
+#undef JD_TALLY_clos
+#undef JD_COUNT_PASS
+#undef JD_ARC_AT_DEF
+#undef JD_X_ARRIVAL
+#undef JD_ARC_AT
+#undef JD_NOTE_CELL
 
 // ------------------------------------------------------------------ one stream, one command (see jd_search.h: run_stream)
 template <int NE, bool MDL>

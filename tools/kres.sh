@@ -1,9 +1,12 @@
 #!/bin/bash
-# Register / LDS / spill numbers of the search kernels, compile only (no GPU): tools/kres.sh [extra hipcc flags] 
+# Register / LDS / spill numbers of the search kernels, compile only (no GPU): tools/kres.sh [extra hipcc flags]
 # e.g. tools/kres.sh -DJD_SLOT_WPE=4
+# (the object goes to a temporary file of this run's own: two trees - a parent and a branch - can be measured side by side)
 cd "$(dirname "$0")/.."
+obj=$(mktemp --suffix=.o) || exit 1
+trap 'rm -f "$obj"' EXIT
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --offload-device-only -c \
-  -Rpass-analysis=kernel-resource-usage -I include -I juicer_amd/csrc "$@" -o /tmp/jd_device_res.o juicer_amd/csrc/jd_device.hip 2>&1 | \
+  -Rpass-analysis=kernel-resource-usage -I include -I juicer_amd/csrc "$@" -o "$obj" juicer_amd/csrc/jd_device.hip 2>&1 | \
   python3 -c "
 import re,sys
 txt=sys.stdin.read()
