@@ -539,7 +539,9 @@ int jd_dec_set_pipeline(jd_dec *d, int32_t mode, int32_t depth, int32_t slots);
  *   JD_SCORE_FAST   fused multiply-add distance on pre-scaled parameters and an fp32 logAdd on the hardware's exp / log: a log-likelihood
  *                   moves by ~1e-5 of its magnitude; hypotheses keep their words and times on every fixture of the test suite and their
  *                   scores stay within 1e-4 relative (what BASELINE.json's north_star asks of the path; tests/test_gpu_fastscore.py).
- *                   The table costs 0.4 of the exact one (csrc/jd_gmm.h: jd_gmm_fast39).  39-dimensional GMM models only.
+ *                   GMM models of every vector size (hybrid models: refused).  At D = 39 the table costs 0.4 of the exact one
+ *                   (csrc/jd_gmm.h: jd_gmm_fast39); every other D is scored by jd_gmm_fast (the same arithmetic, D at run time; DESIGN.md
+ *                   3.5 has its measured cost and deviation per D; tests/test_gpu_fastscore_anyd.py).
  * Call it between two decodes; whatever was scored or announced ahead is dropped.  jd_am_score_frames_mode: jd_am_score_frames with the option.
  */
 #define JD_SCORE_EXACT 0

@@ -595,7 +595,8 @@ class Decoder:
 
     def set_scoring(self, mode: int):
         """How the likelihood tables are scored (jd_dec_set_scoring): SCORE_EXACT (default: the reference's roundings, bit-identical
-        log-likelihoods) or SCORE_FAST (fused multiply-add distance, fp32 logAdd: scores within 1e-4, the table at 0.4 of the cost)."""
+        log-likelihoods) or SCORE_FAST (fused multiply-add distance, fp32 logAdd: scores within 1e-4, the table at 0.4 of the cost at D = 39; GMM models of
+        every vector size)."""
         _check(lib().jd_dec_set_scoring(self.h, C.c_int32(mode)))
 
     def pipeline_stats(self) -> dict:

@@ -547,3 +547,106 @@ __global__ __launch_bounds__(256, 4) void jd_gmm_fast39(const float *__restrict_
         }
     }
 }
+
+
+// ---- JD_SCORE_FAST for every other vector size (D != 39): jd_gmm_fast39's arithmetic term for term - u = fma(x, s, t), sum = fma(u, u, sum)
+// packed over a lane's frame pair, the dimensions in ascending order, c = fma(-0.5, sum, det), jd_log_add_fast over the mixtures - with D at
+// run time.  The same 128-row tiles (rows r and r + 64 per lane), state groups of GT (a quarter per wave), row_src, skip_unused and tile list.
+//   parameters  par_fast is [g][m][DP][2], DP = D rounded up to GMM_FAST_DC (upload_am_fast); the padding is s = t = 0 and the staged feature
+//               tile is 0 there: u = 0 and sum = fma(0, 0, sum) = sum bit for bit.  A chunk of a mixture is 16 dwords through the scalar cache.
+//   features    a slab of GMM_FAST_DS dimensions of the tile in LDS (33 KB: four workgroups share a CU), read a chunk of GMM_FAST_DC dimensions
+//               at a time into registers (odd row stride: conflict-free) and used by up to GMM_FAST_MB mixtures of the wave's state, whose
+//               running sums sit in registers.  D <= GMM_FAST_DS: the slab is the tile, staged once.  Above: the slabs are staged in turn
+//               for every state and block of mixtures (the loops are then workgroup-uniform: bound by M, not n_mix) - 32 loads a lane
+//               against 512 packed FMAs at 8 mixtures.
+//   output      straight to the table (two dwords per lane and state): the LDS is the slab's, there is no room for a tile to transpose.
+#define GMM_FAST_DC 8
+#define GMM_FAST_DS 64
+#define GMM_FAST_MB 8               // (16: the compiler keeps scalar registers in vector lanes across the chunk loop)
+template <int GT>
+__global__ __launch_bounds__(256, 4) void jd_gmm_fast(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
+                                                    const float *__restrict__ par_fast, const float *__restrict__ det,
+                                                    const int *__restrict__ n_mix, int G, int M, int D, int DP, float *__restrict__ ll,
+                                                    int skip_unused, const int *__restrict__ rt_base, int n_rt_list)
+{
+    constexpr int DC = GMM_FAST_DC, DS = GMM_FAST_DS, MB = GMM_FAST_MB, LS = DS + 1;
+    extern __shared__ __align__(16) char smem[];
+    float *sx = (float *)smem;                        // [128][LS]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_slabs = (DP + DS - 1) / DS;
+    const int n_rt = rt_base ? n_rt_list : (n_rows + GMM_ROWS2 - 1) / GMM_ROWS2, n_gt = (G + GT - 1) / GT;
+    for (int tile = blockIdx.x; tile < n_rt * n_gt; tile += gridDim.x) {
+        const int gt = tile / n_rt;                   // row tile skewed by the state group (see jd_gmm_kernel)
+        const int r0 = rt_base ? rt_base[(tile + gt) % n_rt] : ((tile + gt) % n_rt) * GMM_ROWS2;
+        const int g0 = gt * GT;
+        if (skip_unused && row_src[r0] < 0) continue;
+        // dimensions [slab DS, slab DS + w) of the tile's rows into sx (coalesced along the dimension; 0 for an unused row and the padding)
+        auto stage = [&](int slab) {
+            const int j0 = slab * DS, w = min(DS, DP - j0);
+            __syncthreads();                          // the readers of what sx held are done
+            for (int e = tid; e < GMM_ROWS2 * w; e += 256) {
+                const int r = e / w, k = e - r * w;
+                const int src = (r0 + r < n_rows) ? row_src[r0 + r] : -1;
+                sx[r * LS + k] = (src >= 0 && j0 + k < D) ? feats[(size_t)src * D + j0 + k] : 0.0f;
+            }
+            __syncthreads();
+        };
+        if (n_slabs == 1) stage(0);
+        const float *x0 = sx + lane * LS, *x1 = sx + (lane + 64) * LS;
+        constexpr int GPW = GT / 4;
+        for (int gi = 0; gi < GPW; ++gi) {
+            const int g = g0 + wid * GPW + gi;        // wave-uniform
+            const int nm = (g < G) ? n_mix[g] : 0;
+            const float *pg = par_fast + (size_t)(g < G ? g : 0) * M * DP * 2;
+            const float *dg = det + (size_t)(g < G ? g : 0) * M;
+            float acc0 = LZ, acc1 = LZ;
+            const int m_end = (n_slabs == 1) ? nm : M;    // (staging inside: every wave takes every turn)
+            for (int m0 = 0; m0 < m_end; m0 += MB) {
+                const int nb = min(MB, nm - m0);      // this wave's mixtures of the block (<= 0: none)
+                jd_f2 sum[MB];
+#pragma unroll
+                for (int mi = 0; mi < MB; ++mi) sum[mi] = jd_f2{0.0f, 0.0f};
+                for (int slab = 0; slab < n_slabs; ++slab) {
+                    if (n_slabs > 1) stage(slab);
+                    if (nb <= 0) continue;
+                    const int j0 = slab * DS, w = min(DS, DP - j0);
+                    for (int jc = 0; jc < w; jc += DC) {
+                        jd_f2 x[DC];
+#pragma unroll
+                        for (int k = 0; k < DC; ++k) { x[k].x = x0[jc + k]; x[k].y = x1[jc + k]; }
+                        // (one pointer for the chunk and a 32-bit stride between mixtures: a pointer per mixture kept over the loop costs
+                        // more scalar registers than there are)
+                        const float *pc = pg + ((size_t)m0 * DP + j0 + jc) * 2;
+                        const unsigned ms = (unsigned)DP * 2u;
+#pragma unroll
+                        for (int mi = 0; mi < MB; ++mi) {
+                            if (mi < nb) {
+                                const float *pm = pc + (unsigned)mi * ms;
+#pragma unroll
+                                for (int k = 0; k < DC; ++k) {
+                                    const jd_f2 sj = {pm[2 * k], pm[2 * k]}, tj = {pm[2 * k + 1], pm[2 * k + 1]};
+                                    const jd_f2 u = __builtin_elementwise_fma(x[k], sj, tj);
+                                    sum[mi] = __builtin_elementwise_fma(u, u, sum[mi]);
+                                }
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int mi = 0; mi < MB; ++mi) {
+                    if (mi < nb) {
+                        const float dm = dg[m0 + mi];
+                        const float c0 = __builtin_fmaf(-0.5f, sum[mi].x, dm), c1 = __builtin_fmaf(-0.5f, sum[mi].y, dm);
+                        if (m0 + mi == 0) { acc0 = LZ < c0 ? c0 : LZ; acc1 = LZ < c1 ? c1 : LZ; }
+                        else { acc0 = jd_log_add_fast(acc0, c0); acc1 = jd_log_add_fast(acc1, c1); }
+                    }
+                }
+            }
+            if (g < G) {
+                if (r0 + lane < n_rows) ll[(size_t)(r0 + lane) * G + g] = acc0;
+                if (r0 + lane + 64 < n_rows) ll[(size_t)(r0 + lane + 64) * G + g] = acc1;
+            }
+        }
+    }
+}

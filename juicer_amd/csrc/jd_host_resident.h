@@ -790,9 +790,9 @@ extern "C" int jd_dec_set_scoring(jd_dec *d, int32_t mode)
 {
     if (!d) return jd_fail(JD_EINVAL, "jd_dec_set_scoring: null");
     if (mode != JD_SCORE_EXACT && mode != JD_SCORE_FAST) return jd_fail(JD_EINVAL, "jd_dec_set_scoring: mode %d (JD_SCORE_EXACT or JD_SCORE_FAST)", mode);
-    if (mode == JD_SCORE_FAST && (d->am->D != 39 || d->am->hybrid))
+    if (mode == JD_SCORE_FAST && d->am->hybrid)                        // (today's text: GMM models of every D are served since)
         return jd_fail(JD_EINVAL, "jd_dec_set_scoring: JD_SCORE_FAST serves 39-dimensional GMM models (this decoder's: D = %d%s)", d->am->D,
-                       d->am->hybrid ? ", hybrid" : "");
+                       ", hybrid");
     if (d->res && d->res->on && !d->pipe_on) return jd_fail(JD_ESTATE, "jd_dec_set_scoring: a broker drives this decoder's resident kernel");
     int rc = check_device(d->device);
     if (rc) return rc;

@@ -1,5 +1,5 @@
 // jd_host_scoring.h - the host side of the companion scoring kernels (included by jd_device.hip): the model parameters on the device,
-// launch_gmm (jd_gmm_kernel39, the default; jd_gmm_fast39, jd_dec_set_scoring's option; the generic and the hybrid kernel),
+// launch_gmm (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast, jd_dec_set_scoring's option; the generic and the hybrid kernel),
 // jd_am_score_frames.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
 #pragma once
 
@@ -16,8 +16,9 @@ __global__ void jd_hybrid_kernel(const float *__restrict__ feats, const int *__r
 
 struct AmDevBuf {
     float *par = nullptr, *det = nullptr; int *n_mix = nullptr;
-    float *par_fast = nullptr;      // jd_dec_set_scoring(JD_SCORE_FAST): [g][m][D][2] = (sqrt(ivar), -mean sqrt(ivar)), made when first asked for
-    int fast = 0;                   // launch_gmm scores with jd_gmm_fast39
+    float *par_fast = nullptr;      // jd_dec_set_scoring(JD_SCORE_FAST): [g][m][DP][2] = (sqrt(ivar), -mean sqrt(ivar)), made when first asked for
+                                    // (DP = jd_fast_dp(D): D = 39 as it is, every other D padded with (0, 0) to jd_gmm_fast's chunk)
+    int fast = 0;                   // launch_gmm scores with jd_gmm_fast39 (D = 39) / jd_gmm_fast
     float *log_prior = nullptr;
     JdLogTab *logtab = nullptr;
     int device = -1;
@@ -51,18 +52,24 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
     return JD_OK;
 }
 
-// the parameters of the scoring option (jd_gmm.h: jd_gmm_fast39)
+// the parameters of the scoring option (jd_gmm.h: jd_gmm_fast39, jd_gmm_fast): par is [gm][jd_fast_dp(D)][2], zero behind dimension D
+static int jd_fast_dp(int D) { return D == 39 ? 39 : (D + GMM_FAST_DC - 1) / GMM_FAST_DC * GMM_FAST_DC; }
+static void prep_par_fast(const float *mean, const float *ivar, size_t gm, size_t D, std::vector<float> &par)
+{
+    const size_t DP = (size_t)jd_fast_dp((int)D);
+    par.assign(gm * DP * 2, 0.0f);
+    for (size_t i = 0; i < gm; ++i)
+        for (size_t j = 0; j < D; ++j) {
+            const double s = sqrt((double)ivar[i * D + j]);
+            par[(i * DP + j) * 2] = (float)s;
+            par[(i * DP + j) * 2 + 1] = (float)(-(double)mean[i * D + j] * s);
+        }
+}
 static int upload_am_fast(const jd_am *a, AmDevBuf &b)
 {
     if (b.par_fast) return JD_OK;
-    const size_t gm = (size_t)a->n_gmm * a->max_mix, D = (size_t)a->D;
-    std::vector<float> par(gm * D * 2);
-    for (size_t i = 0; i < gm; ++i)
-        for (size_t j = 0; j < D; ++j) {
-            const double s = sqrt((double)a->ivar[i * D + j]);
-            par[(i * D + j) * 2] = (float)s;
-            par[(i * D + j) * 2 + 1] = (float)(-(double)a->mean[i * D + j] * s);
-        }
+    std::vector<float> par;
+    prep_par_fast(a->mean.data(), a->ivar.data(), (size_t)a->n_gmm * a->max_mix, (size_t)a->D, par);
     HIPCHK(hipMalloc(&b.par_fast, par.size() * sizeof(float)));
     HIPCHK(hipMemcpy(b.par_fast, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice));
     return JD_OK;
@@ -85,7 +92,7 @@ static void free_am_gmm(AmDevBuf &b)
 // scoring cost the search 20 ms).  A bounded grid scores in the background instead.
 // skip_unused: row_src marks unused rows with -1 in whole-tile runs (decode_wave's stream slots).
 // used_row_tiles >= 0: the row tiles that are not skipped (else: all of them)
-// rt_base (device, or null) / n_rt_list: score these row tiles (first rows) only - D = 39
+// rt_base (device, or null) / n_rt_list: score these row tiles (first rows) only - the kernels of 128-row tiles (D = 39; jd_gmm_fast)
 static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows,
                       float *d_ll, hipStream_t st, int max_blocks = 0, int skip_unused = 0, int used_row_tiles = -1,
                       const int *rt_base = nullptr, int n_rt_list = 0)
@@ -98,12 +105,14 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
         HIPCHK(hipGetLastError());
         return JD_OK;
     }
-    const int rows_per_tile = (a->D == 39) ? GMM_ROWS2 : GMM_ROWS;
-    if (rt_base && a->D != 39) return jd_fail(JD_EINVAL, "launch_gmm: tile lists are the D = 39 kernel's");
+    const bool fast_any = a->D != 39 && b.fast && b.par_fast;           // jd_gmm_fast: the D = 39 kernels' tiles
+    const bool tiles128 = a->D == 39 || fast_any;
+    const int rows_per_tile = tiles128 ? GMM_ROWS2 : GMM_ROWS;
+    if (rt_base && !tiles128) return jd_fail(JD_EINVAL, "launch_gmm: tile lists are the D = 39 kernel's");
     const long long row_tiles = rt_base ? n_rt_list : (n_rows + rows_per_tile - 1) / rows_per_tile;
     long long tiles = row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT);
     // few rows (a streaming push, a tick of the broker): tiles of 16 states, four times as many and a quarter as long
-    const bool small_tiles = a->D == 39 && (used_row_tiles >= 0 ? (long long)used_row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT) : tiles) < 1024;
+    const bool small_tiles = tiles128 && (used_row_tiles >= 0 ? (long long)used_row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT) : tiles) < 1024;
     if (small_tiles) tiles = row_tiles * ((a->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL);
     dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
     if (a->D == 39 && b.fast && b.par_fast) {
@@ -114,6 +123,15 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
         else
             hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
+    } else if (fast_any) {
+        const size_t sm = (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * sizeof(float);
+        const int DP = jd_fast_dp(a->D);
+        if (small_tiles)
+            hipLaunchKernelGGL(jd_gmm_fast<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
+                               b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
+        else
+            hipLaunchKernelGGL(jd_gmm_fast<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
+                               b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
     } else if (a->D == 39) {
         const size_t sm = 130 * sizeof(JdLogTab) + 32 * sizeof(unsigned long long) + (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float);
         if (small_tiles)
@@ -159,7 +177,8 @@ static int score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const
 {
     if (!a || !frames || !out || n_frames < 0) return jd_fail(JD_EINVAL, "jd_am_score_frames: bad argument");
     if (mode != JD_SCORE_EXACT && mode != JD_SCORE_FAST) return jd_fail(JD_EINVAL, "jd_am_score_frames_mode: mode %d (JD_SCORE_EXACT or JD_SCORE_FAST)", mode);
-    if (mode == JD_SCORE_FAST && (a->D != 39 || a->hybrid)) return jd_fail(JD_EINVAL, "JD_SCORE_FAST: 39-dimensional GMM models only");
+    // (the text of the days when the option served D = 39 alone, kept for its callers: GMM models of every D are served, hybrid ones are not)
+    if (mode == JD_SCORE_FAST && a->hybrid) return jd_fail(JD_EINVAL, "JD_SCORE_FAST: 39-dimensional GMM models only");
     int rc = check_device(device);
     if (rc) return rc;
     if (n_frames == 0) return JD_OK;
