@@ -1355,9 +1355,9 @@ static int pf_announce(jd_dec *d, int nb, const float *d_feats, const int64_t *u
 // afterwards).  Nothing changes for a caller who does not announce, announces one ahead, or fills more than half of
 // the streams with one batch; results cannot depend on any of it (streams never interact).
 // The batch behind the running one, if its table is there: its unfinished streams as work items for the launch that is
-// being planned (started - initialised, frame counts set - the first time round).  heads: {frame, T, error, needs_init} of
-// every stream, as of now (only read for a batch that has been started before).
-static int pf_background(jd_dec *d, int fg_bank, const std::vector<int> *heads, hipStream_t st, std::vector<int2> *work, std::vector<double> *left)
+// being planned (started - initialised, frame counts set - the first time round).  heads: those of every stream (read_heads),
+// as of now (only read for a batch that has been started before).
+static int pf_background(jd_dec *d, int fg_bank, const std::vector<StreamHead> *heads, hipStream_t st, std::vector<int2> *work, std::vector<double> *left)
 {
     work->clear(); left->clear();
     if (d->pf_q.empty() || !d->pipeline || d->C.lazy) return JD_OK;
@@ -1395,10 +1395,10 @@ static int pf_background(jd_dec *d, int fg_bank, const std::vector<int> *heads, 
     if (!heads) return JD_OK;
     const int s0 = F.bank * B;
     for (int u = 0; u < F.nb; ++u) {
-        const int *h = heads->data() + (size_t)(s0 + u) * 4;
-        if (h[2] == 0 && h[0] < F.plan.T[(size_t)u]) {
+        const StreamHead &h = (*heads)[(size_t)(s0 + u)];
+        if (h.error == 0 && h.frame < F.plan.T[(size_t)u]) {
             work->push_back(make_int2(s0 + u, (int)(table_row0(d, F.buf) + F.plan.row_off[(size_t)u])));
-            left->push_back((double)(F.plan.T[(size_t)u] - h[0]));
+            left->push_back((double)(F.plan.T[(size_t)u] - h.frame));
         }
     }
     return JD_OK;
@@ -1496,9 +1496,10 @@ static int decode_wave(jd_dec *d, int nb, const float *d_feats, const int64_t *u
         hipLaunchKernelGGL(jd_set_T_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, s0, nb, d->d_T + s0);
         HIPCHK(hipGetLastError());
     } else {
-        std::vector<int> head((size_t)nb * 4);
-        HIPCHK(hipMemcpy2D(head.data(), 16, d->d_ctl + s0, sizeof(StreamCtl), 16, (size_t)nb, hipMemcpyDeviceToHost));
-        for (int u = 0; u < nb; ++u) { frame0[(size_t)u] = head[(size_t)u * 4]; d->timing.ahead_frames += head[(size_t)u * 4]; }
+        std::vector<StreamHead> head;
+        rc = read_heads(d, s0, nb, &head, nullptr);
+        if (rc) return rc;
+        for (int u = 0; u < nb; ++u) { frame0[(size_t)u] = head[(size_t)u].frame; d->timing.ahead_frames += head[(size_t)u].frame; }
     }
 
     struct Events {                                                    // (destroyed on every way out, error paths included)
