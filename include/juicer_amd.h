@@ -116,9 +116,21 @@ void    jd_net_destroy(jd_net *n);
  * JD_PUSH_LABELS.  JD_PUSH_WEIGHTS: the best grammar weight reachable below a lexicon-tree node is paid on the way
  * into it, so the beam prunes on it; path totals are the same up to float association.  JD_PUSH_LABELS: C.L is
  * composed with its output labels pushed towards the initial state (jd_net_push_labels).
+ * JD_LOOKAHEAD_SETS (a third bit of `pushing`, free to combine with the other two; off by default, and without it
+ * every result is what it was before the bit existed): the look-ahead works on label SETS, as the reference's does,
+ * instead of intervals of the caller's word numbers.  S(c) is the set of output labels on the first label-carrying
+ * arcs reachable from C.L state c through arcs without an output label.  With the bit, a label-less arc
+ * c -i:eps-> c' is followed at grammar state g iff g has an arc whose input label is in S(c') (or a final C.L state
+ * is reachable from c' without a label and g is final - unchanged), and JD_PUSH_WEIGHTS pays the best weight among
+ * g's arcs with a label in S(c), 0 if there is none.  States on a cycle of label-less arcs, and their ancestors, keep
+ * "every label".  The composed network then does not depend on how the words are numbered: vocabularies numbered by
+ * spelling and words with several pronunciations get the graph a depth-first numbering of a pure tree gets from the
+ * intervals.  Costs host time (the sets) and device memory for the label lists of the states whose set is no interval
+ * under the internal renumbering; those lists hold at most 2^28 labels in all (JD_ENOMEM names the bound).
  */
 #define JD_PUSH_WEIGHTS 1
 #define JD_PUSH_LABELS 2
+#define JD_LOOKAHEAD_SETS 4
 int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, int32_t device,
                    int64_t max_states, int64_t max_arcs, int32_t pushing);
 
@@ -131,6 +143,15 @@ int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, int32_t devi
  * Host code (no device needed); exact rule: csrc/jd_compose.hip, cl_push_labels.  n_moved (may be NULL): labels moved.
  */
 int jd_net_push_labels(jd_net **out, const jd_net *cl, int64_t *n_moved);
+
+/*
+ * Diagnostics / tests (host code, no device): the label sets S(c) of JD_LOOKAHEAD_SETS for every state of a C.L
+ * transducer, as CSR - row_ptr[n_states + 1], labels[cap] - sorted, in the caller's label numbering; a state with
+ * "every label" gets the single entry -1.  mayfin[n_states] (may be NULL): a final state is reachable from c through
+ * label-less arcs.  *n_total = the number of entries; JD_ENOMEM (with *n_total set) when cap is too small, or when
+ * the sets that are no interval under the internal renumbering hold more than 2^28 labels (the bound of the option).
+ */
+int jd_debug_cl_label_sets(const jd_net *cl, int64_t *row_ptr, int32_t *labels, int64_t cap, int64_t *n_total, uint8_t *mayfin);
 
 /*
  * Dynamic composition proper (WFSTOnTheFlyDecoder: C.L o G expanded where the search goes, never as a

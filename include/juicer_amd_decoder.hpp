@@ -384,15 +384,17 @@ private:
 // apart and are composed where the search goes (jd_net_create_lazy).  The composed network is owned here and
 // keeps what has been expanded from one utterance to the next.  modelLevelOutput: setModelLevelOutput (as in
 // GpuWFSTDecoder); latticeGeneration is not offered; doPushing: JD_PUSH_WEIGHTS | JD_PUSH_LABELS is the reference's doLabelAndWeightPushing
-// = true; maxStates / maxArcs: the room the network may grow into (0 = defaults; when it fills up the arena starts
+// = true, and JD_LOOKAHEAD_SETS may be or-ed into the mask (lookAheadSets in the bool form; off by default): the look-ahead
+// then works on exact label sets, so that the composed graph does not depend on how the vocabulary is numbered (juicer_amd.h,
+// jd_net_compose); maxStates / maxArcs: the room the network may grow into (0 = defaults; when it fills up the arena starts
 // again between utterances, jd_net_lazy_set_high_water).
 struct LazyNetHolder_ {
     jd_net *lazyNet_;
     LazyNetHolder_(const jd_net *cl, const jd_net *g, const jd_am *models, int device, long long maxStates, long long maxArcs, int pushing)
         : lazyNet_(0)
     {
-        if (pushing < 0 || pushing > (JD_PUSH_WEIGHTS | JD_PUSH_LABELS)) {
-            fprintf(stderr, "juicer_amd: doPushing is a mask of JD_PUSH_WEIGHTS | JD_PUSH_LABELS (got %d)\n", pushing);
+        if (pushing < 0 || pushing > (JD_PUSH_WEIGHTS | JD_PUSH_LABELS | JD_LOOKAHEAD_SETS)) {
+            fprintf(stderr, "juicer_amd: doPushing is a mask of JD_PUSH_WEIGHTS | JD_PUSH_LABELS | JD_LOOKAHEAD_SETS (got %d)\n", pushing);
             exit(1);
         }
         if (jd_net_create_lazy(&lazyNet_, cl, g, models, device, maxStates, maxArcs, pushing) != JD_OK) {
@@ -413,9 +415,10 @@ public:
     // mask above would silently mean JD_PUSH_WEIGHTS alone)
     GpuWFSTOnTheFlyDecoder(const jd_net *clNetwork, const jd_net *gNetwork, const jd_am *models, float emitPruneWin,
                            float phoneEndPruneWin, int maxEmitHyps, bool doLabelAndWeightPushing, int device = 0,
-                           long long maxStates = 0, long long maxArcs = 0, int blockSize = 5, int flushFrames = 64)
+                           long long maxStates = 0, long long maxArcs = 0, int blockSize = 5, int flushFrames = 64,
+                           bool lookAheadSets = false)
         : LazyNetHolder_(clNetwork, gNetwork, models, device, maxStates, maxArcs,
-                         doLabelAndWeightPushing ? (JD_PUSH_WEIGHTS | JD_PUSH_LABELS) : 0),
+                         (doLabelAndWeightPushing ? (JD_PUSH_WEIGHTS | JD_PUSH_LABELS) : 0) | (lookAheadSets ? JD_LOOKAHEAD_SETS : 0)),
           GpuWFSTDecoder(lazyNet_, models, 0.0f, emitPruneWin, phoneEndPruneWin, 0.0f, maxEmitHyps, device, blockSize, flushFrames) {}
     // composed states / arcs materialised so far
     void composedSize(long long &states, long long &arcs) const

@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libjuicer_amd.so")
 
 JD_OK, JD_EINVAL, JD_ENODEV, JD_EHIP, JD_ENOMEM, JD_EHIST, JD_ESTATE, JD_EFORMAT = 0, -1, -2, -3, -4, -5, -6, -7
+# bits of the `pushing` argument of jd_net_compose / jd_net_create_lazy / jd_multi_create_lazy
+JD_PUSH_WEIGHTS, JD_PUSH_LABELS, JD_LOOKAHEAD_SETS = 1, 2, 4
 LOG_ZERO = float(np.float32(-3.402823466e+38))
 
 
@@ -118,7 +120,7 @@ EXPORTS = [
     "jd_am_score_frames", "jd_last_error", "jd_version", "jd_dec_debug_trace", "jd_debug_expf",
     "jd_multi_create", "jd_multi_create_lazy", "jd_multi_decode_batch", "jd_multi_destroy",
     "jd_dec_set_partial_interval", "jd_stream_partial", "jd_stream_collect_info", "jd_stream_path_counts", "jd_dec_quiesce", "jd_debug_closure_path_counts", "jd_dec_set_max_alloc_models", "jd_net_compose", "jd_am_create_hybrid", "jd_net_create_lazy", "jd_net_lazy_size", "jd_net_lazy_reset",
-    "jd_net_lazy_set_high_water", "jd_net_lazy_generation", "jd_release_cached_memory", "jd_net_push_labels",
+    "jd_net_lazy_set_high_water", "jd_net_lazy_generation", "jd_release_cached_memory", "jd_net_push_labels", "jd_debug_cl_label_sets",
     "jd_dec_prefetch_scores", "jd_streams_push", "jd_dec_info",
     "jd_broker_create", "jd_broker_destroy", "jd_broker_open", "jd_broker_close", "jd_broker_init", "jd_broker_push",
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
@@ -192,6 +194,10 @@ def _model_hyp_from_c(h: CModelHyp) -> ModelHyp:
                     tot_score=float(h.tot_score), tot_ac=float(h.tot_ac), tot_lm=float(h.tot_lm))
 
 
+def _pushing_mask(pushing, push_labels, lookahead_sets) -> int:
+    return (JD_PUSH_WEIGHTS if pushing else 0) | (JD_PUSH_LABELS if push_labels else 0) | (JD_LOOKAHEAD_SETS if lookahead_sets else 0)
+
+
 class Network:
     """WFSTNetwork counterpart: CSR arc table (16-byte arc records) for HBM."""
 
@@ -244,21 +250,38 @@ class Network:
 
     @classmethod
     def compose(cls, cl: "Network", g: "Network", device: int = 0, max_states: int = 0, max_arcs: int = 0, pushing: bool = False,
-                push_labels: bool = False):
+                push_labels: bool = False, lookahead_sets: bool = False):
         """C.L o G on the device (jd_net_compose): the dynamic-composition row's first step."""
         h = C.c_void_p()
         _check(lib().jd_net_compose(C.byref(h), cl.h, g.h, C.c_int32(device), C.c_int64(max_states), C.c_int64(max_arcs),
-                                    C.c_int32((1 if pushing else 0) | (2 if push_labels else 0))))
+                                    C.c_int32(_pushing_mask(pushing, push_labels, lookahead_sets))))
         return cls(h)
 
     @classmethod
     def lazy(cls, cl: "Network", g: "Network", am: "Models", device: int = 0, max_states: int = 0, max_arcs: int = 0, pushing: bool = False,
-             push_labels: bool = False):
+             push_labels: bool = False, lookahead_sets: bool = False):
         """C.L o G expanded by the search, where it goes (jd_net_create_lazy)."""
         h = C.c_void_p()
         _check(lib().jd_net_create_lazy(C.byref(h), cl.h, g.h, am.h, C.c_int32(device), C.c_int64(max_states), C.c_int64(max_arcs),
-                                        C.c_int32((1 if pushing else 0) | (2 if push_labels else 0))))
+                                        C.c_int32(_pushing_mask(pushing, push_labels, lookahead_sets))))
         return cls(h)
+
+    def label_sets(self, cap: int = -1):
+        """The label sets of JD_LOOKAHEAD_SETS for every state of this C.L transducer (jd_debug_cl_label_sets, host only):
+        (row_ptr int64 [n_states + 1], labels int32 - sorted per state, -1 alone for "every label" -, mayfin bool [n_states]).
+        cap: room for the labels (default: as many as there are)."""
+        L = lib()
+        ns = self.n_states
+        rp, mf, n = np.zeros(ns + 1, np.int64), np.zeros(ns, np.uint8), C.c_int64(0)
+        if cap < 0:
+            dummy = np.zeros(1, np.int32)
+            rc = L.jd_debug_cl_label_sets(self.h, _p(rp, C.c_int64), _p(dummy, C.c_int32), C.c_int64(0), C.byref(n), _p(mf, C.c_uint8))
+            if rc != 0 and not (rc == JD_ENOMEM and n.value > 0):
+                _check(rc)
+            cap = n.value
+        labels = np.zeros(max(cap, 1), np.int32)
+        _check(L.jd_debug_cl_label_sets(self.h, _p(rp, C.c_int64), _p(labels, C.c_int32), C.c_int64(cap), C.byref(n), _p(mf, C.c_uint8)))
+        return rp, labels[:n.value], mf.astype(bool)
 
     def push_labels(self):
         """C.L with its output labels pushed towards the initial state (jd_net_push_labels): (network, labels moved)."""

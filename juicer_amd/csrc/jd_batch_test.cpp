@@ -172,7 +172,7 @@ int main(int argc, char **argv)
     const char *fsm = 0, *insyms = 0, *outsyms = 0, *amf = 0, *mmf = 0, *list = 0;
     const char *gramFsm = 0, *gramInSyms = 0, *gramOutSyms = 0;              // juicer.cpp:128-130: separate C.L and G
     float mainBeam = 0, startBeam = 0, endBeam = 0, wordBeam = 0, lmScale = 1.0f, insPen = 0.0f;
-    int maxHyps = 0, framesPerSec = 100, device = 0, batch = 64, useAdapter = 0, writeBinaryFiles = 0, nDevices = 0, pushing = 0, lazy = 0, nThreads = 0;
+    int maxHyps = 0, framesPerSec = 100, device = 0, batch = 64, useAdapter = 0, writeBinaryFiles = 0, nDevices = 0, pushing = 0, lazy = 0, nThreads = 0, lookaheadSets = 0;
     std::string outputFormat = "ref";          // -outputFormat ref|trans|mlf|xmlf|verbose (juicer.cpp:263-264)
     const char *refFName = 0;                  // -refFName: expected results, MLF or one line per file (juicer.cpp:267)
     const char *outputFName = 0;               // -outputFName: "", "stdout", "stderr" or a file (DecoderBatchTest.cpp:216-230)
@@ -188,6 +188,7 @@ int main(int argc, char **argv)
         // juicer.cpp:240 doLabelAndWeightPushing
         else if (a == "-gramOutSymsFName") gramOutSyms = nxt(); else if (a == "-pushing") pushing = JD_PUSH_WEIGHTS | JD_PUSH_LABELS;
         else if (a == "-weightPushing") pushing = JD_PUSH_WEIGHTS;
+        else if (a == "-lookaheadSets") lookaheadSets = 1;                       // look-ahead on exact label sets (JD_LOOKAHEAD_SETS)
         else if (a == "-lazy") lazy = 1;                                         // compose where the search goes (jd_net_create_lazy)
         else if (a == "-outSymsFName") outsyms = nxt(); else if (a == "-modelsFName") amf = nxt();
         else if (a == "-htkModelsFName") mmf = nxt();
@@ -221,14 +222,17 @@ int main(int argc, char **argv)
                         "       [-threads N   (N serial harness threads - the reference's loop each - through one decoder: the broker)]\n"
                         "       [-residentSlots N   (a list longer than N goes through N one-workgroup slots of a search kernel that stays: a slot takes the\n"
                         "        next utterance the moment its own is through - jd_dec_set_pipeline, JD_FLOW_RESIDENT; -batch is then at least N)]\n"
-                        "       [-gramFsmFName G [-gramInSymsFName S] [-gramOutSymsFName S] [-pushing | -weightPushing] [-lazy]   (-fsmFName is then C.L: composed with G on the\n"
-                        "        device, as a whole before the search or - with -lazy - by the search, where it goes)]\n"
+                        "       [-gramFsmFName G [-gramInSymsFName S] [-gramOutSymsFName S] [-pushing | -weightPushing] [-lookaheadSets] [-lazy]   (-fsmFName is then\n"
+                        "        C.L: composed with G on the device, as a whole before the search or - with -lazy - by the search, where it goes;\n"
+                        "        -lookaheadSets: look-ahead on exact label sets, for vocabularies not numbered in the lexicon tree's order)]\n"
                         "       [-modelLevelOutput   (phones: the HMMs the best path passed, by the models' names, words beside them in mlf / xmlf;\n"
                         "        not with -threads, -devices or -refFName)]\n"
                         "       [-monoListFName F] [-tiedListFName F] [-cdSepChars C] [-silMonophone P] [-pauseMonophone P]   (accepted, no effect:\n"
                         "        phones are printed by the HMM names of the models file)\n");
         return 2;
     }
+    if (lookaheadSets && !gramFsm) { fprintf(stderr, "jd_batch_test: -lookaheadSets needs -gramFsmFName (it is an option of the composition)\n"); return 1; }
+    if (lookaheadSets) pushing |= JD_LOOKAHEAD_SETS;
     if (modelLevel) {                          // what cannot give models: refused before anything is loaded
         const char *why = nThreads > 0 ? "-threads (a broker serves word output only)"
                         : nDevices > 0 ? "-devices (jd_multi decodes words only)"

@@ -31,6 +31,13 @@
 //   - P(source) (a matched arc: - P(source) only; a final weight likewise), so the grammar's weight is
 //   paid as early as the tree allows and the beam sees it: (w + P(c',g)) - P(c,g), resp. (w + v) - P(c,g).
 //   Path totals are unchanged up to float association.
+//   label sets (JD_LOOKAHEAD_SETS): the interval [lo(c), hi(c)] is replaced, in both places above, by the SET S(c) of
+//   the first labels reachable from c through label-less arcs: the arc c -i:eps-> c' is kept if g has an arc whose
+//   input label is in S(c') (the final-state clause is unchanged), and P(c,g) is the best weight among the arcs of g
+//   with a label in S(c), 0 if there is none.  States on a cycle of label-less arcs, and their ancestors, keep
+//   "every label".  Intervals are exact only when the words are numbered in the lexicon tree's depth-first order;
+//   sets make the result independent of the word numbering (representation: jd_labelsets.h, jd_lazy.h LA_LIST).
+//   Numbering, arc order and the back-off rule are the same.
 //
 // All weights are the ones the two networks carry after loading (each with its own scale, as
 // juicer.cpp:933-970 loads them), i.e. log-domain scores that add, in float32.  States are numbered by
@@ -47,6 +54,7 @@
 
 #include "jd_internal.h"
 #include "jd_lazy.h"        // LazyDev and the expansion step shared with the search kernel
+#include "jd_labelsets.h"   // JD_LOOKAHEAD_SETS: the label sets of C.L (host code)
 
 #define CHK(expr)                                                                                  \
     do {                                                                                           \
@@ -65,6 +73,7 @@ struct ComposeArgs {
     long long *arc_start; int *arc_cnt; JdArc *arcs; unsigned long long *n_arcs; long long max_arcs;
     float *fin; int *err;
     int push;                                                            // weight look-ahead pushing (see jd_net_compose)
+    const int *set_row, *set_lab;                                        // label lists (JD_LOOKAHEAD_SETS; jd_lazy.h LA_LIST), else null
 };
 
 __device__ __forceinline__ unsigned long long jc_hash(unsigned long long k)
@@ -162,7 +171,10 @@ __device__ __forceinline__ int jc_arc_kind(const ComposeArgs &A, const JdArc &ca
     return *ga >= 0;
 }
 
-// one wave per state of the current BFS level
+// one wave per state of the current BFS level.  SETS: label-set look-ahead (jc_any_in_set / jc_potential_set are
+// la_set_lane and, for long lists, la_set_wave of jd_lazy.h, reached through la_arc_kind); the instantiation without
+// it is the kernel as it was.
+template <bool SETS>
 __global__ __launch_bounds__(256) void jc_expand(ComposeArgs A, int begin, int end)
 {
     const int lane = threadIdx.x & 63;
@@ -178,10 +190,20 @@ __global__ __launch_bounds__(256) void jc_expand(ComposeArgs A, int begin, int e
     const int a0 = A.cl_row[c], a1 = A.cl_row[c + 1];
     // pushing: what this state's incoming arcs have already paid of the word that is under way
     float p_src = 0.0f;
-    if (A.push && !flag) { const int2 la = A.cl_la[c]; p_src = jc_potential(A, g, la.x, la_hi(la)); }
+    if (A.push && !flag) {
+        if (SETS) p_src = la_wave_potential(A, g, c);
+        else { const int2 la = A.cl_la[c]; p_src = jc_potential(A, g, la.x, la_hi(la)); }
+    }
     // pass 1: how many arcs this state gets
     int mine = 0, ga;
-    for (int a = a0 + lane; a < a1; a += 64) mine += jc_arc_kind(A, A.cl_arcs[a], g, &ga);
+    float pot = 0.0f;
+    if (SETS)
+        for (int a = a0; a < a1; a += 64) {                            // (every lane goes round: the wave shares long list tests)
+            const bool on = a + lane < a1;
+            mine += la_arc_kind(A, on, on ? A.cl_arcs[a + lane] : JdArc{0, 0.0f, 0, 0}, g, false, &ga, &pot);
+        }
+    else
+        for (int a = a0 + lane; a < a1; a += 64) mine += jc_arc_kind(A, A.cl_arcs[a], g, &ga);
     int total = mine;
 #pragma unroll
     for (int o = 32; o; o >>= 1) total += __shfl_xor(total, o);
@@ -208,7 +230,8 @@ __global__ __launch_bounds__(256) void jc_expand(ComposeArgs A, int begin, int e
         JdArc ca = {0, 0.0f, 0, 0};
         int cnt = 0;
         ga = -1;
-        if (on) { ca = A.cl_arcs[a + lane]; cnt = jc_arc_kind(A, ca, g, &ga); }
+        if (SETS) { if (on) ca = A.cl_arcs[a + lane]; cnt = la_arc_kind(A, on, ca, g, A.push != 0, &ga, &pot); }
+        else if (on) { ca = A.cl_arcs[a + lane]; cnt = jc_arc_kind(A, ca, g, &ga); }
         int pre = cnt;                                                 // inclusive scan over the lanes
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(pre, o); if (lane >= o) pre += y; }
@@ -217,7 +240,10 @@ __global__ __launch_bounds__(256) void jc_expand(ComposeArgs A, int begin, int e
             const long long pos = run + pre - 1;
             if (ca.out == 0) {
                 float w = ca.w;
-                if (A.push) { const int2 la = A.cl_la[ca.to]; w = (ca.w + jc_potential(A, g, la.x, la_hi(la))) - p_src; }
+                if (A.push) {
+                    if (!SETS) { const int2 la = A.cl_la[ca.to]; pot = jc_potential(A, g, la.x, la_hi(la)); }
+                    w = (ca.w + pot) - p_src;
+                }
                 A.arcs[pos] = JdArc{jc_state_id(A, (unsigned)ca.to, g), w, ca.in, 0};
             } else {
                 const JdArc m = A.g_arcs[ga];
@@ -329,6 +355,48 @@ static void cl_lookahead(const jd_net *cl, std::vector<int2> &la)
         if (mf[(size_t)c]) la[(size_t)c].y = (int)((unsigned)la[(size_t)c].y | LA_MAYFIN);
 }
 
+// JD_LOOKAHEAD_SETS: the look-ahead entries and label lists of C.L (jd_labelsets.h), C.L's arcs with their output labels
+// renumbered and G's sorted arcs with their INPUT labels renumbered the same way and sorted again (the epsilon, label 0,
+// stays first; matching is by label and the composed arc takes G's output label, so G's order within a state does not show)
+static int cl_label_sets(const char *who, const jd_net *cl, const jd_net *g, std::vector<int2> &la, std::vector<JdArc> &cl_arcs,
+                         std::vector<JdArc> &g_sorted, std::vector<int32_t> &set_row, std::vector<int32_t> &set_lab)
+{
+    int32_t max_label = 0;
+    for (const JdArc &a : g_sorted) {
+        if (a.in < 0) return jd_fail(JD_EINVAL, "%s: negative input label %d in G", who, a.in);
+        max_label = std::max(max_label, a.in);
+    }
+    JdLabelSets R;
+    const int rc = jd_label_sets(cl, max_label, jd_label_sets_bound(), R);
+    if (rc) return rc;
+    const size_t S = (size_t)cl->n_states;
+    la.resize(S);
+    for (size_t c = 0; c < S; ++c) {
+        const bool list = R.set_row[c + 1] > R.set_row[c];
+        la[c] = make_int2((int)((unsigned)R.lo[c] | (list ? LA_LIST : 0u)), (int)((unsigned)R.hi[c] | (R.mayfin[c] ? LA_MAYFIN : 0u)));
+    }
+    cl_arcs = cl->arcs;
+    for (JdArc &a : cl_arcs) a.out = R.fwd[(size_t)a.out];
+    for (JdArc &a : g_sorted) a.in = R.fwd[(size_t)a.in];
+    for (int32_t s = 0; s < g->n_states; ++s)
+        std::sort(g_sorted.begin() + g->row_ptr[(size_t)s], g_sorted.begin() + g->row_ptr[(size_t)s + 1],
+                  [](const JdArc &x, const JdArc &y) { return x.in < y.in; });
+    set_row.swap(R.set_row);
+    set_lab.swap(R.set_lab);
+    if (getenv("JD_VERBOSE")) {
+        int64_t lists = 0;
+        for (size_t c = 0; c < S; ++c) lists += set_row[c + 1] > set_row[c];
+        fprintf(stderr, "%s: label-set look-ahead: %lld of %zu C.L states carry a list, %zu labels in all\n", who, (long long)lists, S, set_lab.size());
+    }
+    return JD_OK;
+}
+
+// Diagnostics / tests (host only, no device): the label sets of JD_LOOKAHEAD_SETS (juicer_amd.h; jd_labelsets.h)
+extern "C" int jd_debug_cl_label_sets(const jd_net *cl, int64_t *row_ptr, int32_t *labels, int64_t cap, int64_t *n_total, uint8_t *mayfin)
+{
+    return jd_label_sets_csr(cl, row_ptr, labels, cap, n_total, mayfin);
+}
+
 // Label pushing, the other half of the reference's -pushing (doLabelAndWeightPushing, juicer.cpp:240, 931-935).  The
 // reference gives every C.L transition the SET of output labels that can follow it (WFSTLabelPushingNetwork::
 // assignOutlabsToTrans, WFSTNetwork.cpp:1643-1764, loops included) and its on-the-fly decoder takes the G transition
@@ -403,13 +471,13 @@ extern "C" int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, i
                               int32_t pushing)
 {
     if (!out || !cl || !g) return jd_fail(JD_EINVAL, "jd_net_compose: null argument");
-    if (pushing < 0 || pushing > 3) return jd_fail(JD_EINVAL, "jd_net_compose: pushing is a combination of JD_PUSH_WEIGHTS and JD_PUSH_LABELS");
+    if (pushing < 0 || pushing > 7) return jd_fail(JD_EINVAL, "jd_net_compose: pushing is a combination of JD_PUSH_WEIGHTS, JD_PUSH_LABELS and JD_LOOKAHEAD_SETS");
+    if (cl->lazy_dev || g->lazy_dev) return jd_fail(JD_EINVAL, "jd_net_compose: the inputs must be ordinary networks");
     std::vector<JdArc> g_sorted;
     int rc = sorted_g_arcs(g, g_sorted);
     if (rc) return rc;
     struct Owned { jd_net *p = nullptr; ~Owned() { delete p; } } pushed;   // C.L with its labels pushed (JD_PUSH_LABELS)
     if (pushing & 2) {
-        if (cl->lazy_dev) return jd_fail(JD_EINVAL, "jd_net_compose: the inputs must be ordinary networks");
         std::vector<JdArc> pa;
         cl_push_labels(cl, pa, nullptr);
         pushed.p = net_with_arcs(cl, std::move(pa));
@@ -436,6 +504,7 @@ extern "C" int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, i
     jd_net *res = nullptr;
     int h_n = 1, h_err = 0, level = 0;
     unsigned long long h_arcs = 0ULL;
+    const bool sets = (pushing & JD_LOOKAHEAD_SETS) != 0;
     {
         size_t cap = 1;
         while (cap < (size_t)max_states * 2) cap <<= 1;
@@ -443,12 +512,24 @@ extern "C" int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, i
 #define DAL(p, T, n) do { p = (T *)dal(sizeof(T) * (size_t)(n)); if (!p) { rc = jd_fail(JD_ENOMEM, "jd_net_compose: hipMalloc of %zu bytes failed", sizeof(T) * (size_t)(n)); goto done; } } while (0)
         int *cl_row, *g_row; JdArc *cl_arcs, *g_arcs; float *cl_fin, *g_fin; int2 *cl_la;
         std::vector<int2> la;
-        cl_lookahead(cl, la);
+        std::vector<JdArc> cl_rel;                                      // (sets) C.L's arcs with the words renumbered
+        std::vector<int32_t> set_row, set_lab;
+        if (sets) {
+            rc = cl_label_sets("jd_net_compose", cl, g, la, cl_rel, g_sorted, set_row, set_lab);
+            if (rc) goto done;
+        } else cl_lookahead(cl, la);
         DAL(cl_row, int, cl->row_ptr.size()); DAL(cl_arcs, JdArc, cl->arcs.size()); DAL(cl_fin, float, cl->fin_w.size()); DAL(cl_la, int2, la.size());
         CHK(hipMemcpy(cl_la, la.data(), la.size() * sizeof(int2), hipMemcpyHostToDevice));
         DAL(g_row, int, g->row_ptr.size()); DAL(g_arcs, JdArc, g->arcs.size()); DAL(g_fin, float, g->fin_w.size());
+        if (sets) {
+            int *d_set_row, *d_set_lab;
+            DAL(d_set_row, int, set_row.size()); DAL(d_set_lab, int, set_lab.size());
+            CHK(hipMemcpy(d_set_row, set_row.data(), set_row.size() * 4, hipMemcpyHostToDevice));
+            if (!set_lab.empty()) CHK(hipMemcpy(d_set_lab, set_lab.data(), set_lab.size() * 4, hipMemcpyHostToDevice));
+            A.set_row = d_set_row; A.set_lab = d_set_lab;
+        }
         CHK(hipMemcpy(cl_row, cl->row_ptr.data(), cl->row_ptr.size() * 4, hipMemcpyHostToDevice));
-        CHK(hipMemcpy(cl_arcs, cl->arcs.data(), cl->arcs.size() * sizeof(JdArc), hipMemcpyHostToDevice));
+        CHK(hipMemcpy(cl_arcs, sets ? cl_rel.data() : cl->arcs.data(), cl->arcs.size() * sizeof(JdArc), hipMemcpyHostToDevice));
         CHK(hipMemcpy(cl_fin, cl->fin_w.data(), cl->fin_w.size() * 4, hipMemcpyHostToDevice));
         CHK(hipMemcpy(g_row, g->row_ptr.data(), g->row_ptr.size() * 4, hipMemcpyHostToDevice));
         CHK(hipMemcpy(g_arcs, g_sorted.data(), g_sorted.size() * sizeof(JdArc), hipMemcpyHostToDevice));
@@ -478,7 +559,8 @@ extern "C" int jd_net_compose(jd_net **out, const jd_net *cl, const jd_net *g, i
         while (begin < h_n) {
             const int end = h_n;
             const long long waves = end - begin;
-            hipLaunchKernelGGL(jc_expand, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, 0, A, begin, end);
+            if (sets) hipLaunchKernelGGL(jc_expand<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, 0, A, begin, end);
+            else hipLaunchKernelGGL(jc_expand<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, 0, A, begin, end);
             CHK(hipGetLastError());
             CHK(hipMemcpy(&h_n, A.n_states, 4, hipMemcpyDeviceToHost));
             CHK(hipMemcpy(&h_err, A.err, 4, hipMemcpyDeviceToHost));
@@ -582,7 +664,7 @@ extern "C" int jd_net_create_lazy(jd_net **out, const jd_net *cl, const jd_net *
 {
     if (!out || !cl || !g || !am) return jd_fail(JD_EINVAL, "jd_net_create_lazy: null argument");
     if (cl->lazy_dev || g->lazy_dev) return jd_fail(JD_EINVAL, "jd_net_create_lazy: the inputs must be ordinary networks");
-    if (pushing < 0 || pushing > 3) return jd_fail(JD_EINVAL, "jd_net_create_lazy: pushing is a combination of JD_PUSH_WEIGHTS and JD_PUSH_LABELS");
+    if (pushing < 0 || pushing > 7) return jd_fail(JD_EINVAL, "jd_net_create_lazy: pushing is a combination of JD_PUSH_WEIGHTS, JD_PUSH_LABELS and JD_LOOKAHEAD_SETS");
     std::vector<JdArc> g_sorted;
     int rc = sorted_g_arcs(g, g_sorted);
     if (rc) return rc;
@@ -617,11 +699,23 @@ extern "C" int jd_net_create_lazy(jd_net **out, const jd_net *cl, const jd_net *
 #define LAL(p, T, cnt) do { p = (T *)dal(sizeof(T) * (size_t)(cnt)); if (!p) { rc = jd_fail(JD_ENOMEM, "jd_net_create_lazy: hipMalloc of %zu bytes failed", sizeof(T) * (size_t)(cnt)); goto done; } } while (0)
         int *cl_row, *g_row; JdArc *cl_arcs, *g_arcs; float *cl_fin, *g_fin; int2 *cl_la;
         std::vector<int2> la;
-        cl_lookahead(cl, la);
+        std::vector<JdArc> cl_rel;                                      // (sets) C.L's arcs with the words renumbered
+        std::vector<int32_t> set_row, set_lab;
+        const bool sets = (pushing & JD_LOOKAHEAD_SETS) != 0;
+        if (sets) {
+            rc = cl_label_sets("jd_net_create_lazy", cl, g, la, cl_rel, g_sorted, set_row, set_lab);
+            if (rc) goto done;
+            // the renumbered G and the lists belong to the network (lazy_allocs): generations come and go, they stay
+            int *d_set_row, *d_set_lab;
+            LAL(d_set_row, int, set_row.size()); LAL(d_set_lab, int, set_lab.size());
+            CHK(hipMemcpy(d_set_row, set_row.data(), set_row.size() * 4, hipMemcpyHostToDevice));
+            if (!set_lab.empty()) CHK(hipMemcpy(d_set_lab, set_lab.data(), set_lab.size() * 4, hipMemcpyHostToDevice));
+            L.set_row = d_set_row; L.set_lab = d_set_lab;
+        } else cl_lookahead(cl, la);
         LAL(cl_row, int, cl->row_ptr.size()); LAL(cl_arcs, JdArc, cl->arcs.size()); LAL(cl_fin, float, cl->fin_w.size()); LAL(cl_la, int2, la.size());
         LAL(g_row, int, g->row_ptr.size()); LAL(g_arcs, JdArc, g_sorted.size()); LAL(g_fin, float, g->fin_w.size());
         CHK(hipMemcpy(cl_row, cl->row_ptr.data(), cl->row_ptr.size() * 4, hipMemcpyHostToDevice));
-        CHK(hipMemcpy(cl_arcs, cl->arcs.data(), cl->arcs.size() * sizeof(JdArc), hipMemcpyHostToDevice));
+        CHK(hipMemcpy(cl_arcs, sets ? cl_rel.data() : cl->arcs.data(), cl->arcs.size() * sizeof(JdArc), hipMemcpyHostToDevice));
         CHK(hipMemcpy(cl_fin, cl->fin_w.data(), cl->fin_w.size() * 4, hipMemcpyHostToDevice));
         CHK(hipMemcpy(cl_la, la.data(), la.size() * sizeof(int2), hipMemcpyHostToDevice));
         CHK(hipMemcpy(g_row, g->row_ptr.data(), g->row_ptr.size() * 4, hipMemcpyHostToDevice));

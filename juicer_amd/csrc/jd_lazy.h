@@ -2,7 +2,7 @@
 // search runs on grows while it runs.  Included by jd_search.h; the host side is in jd_compose.hip.
 //
 // The expansion step is jd_compose.hip's (binary-search match of the C.L arc's output label among the
-// G state's input-sorted arcs, back-off epsilons after a word only, interval look-ahead) applied to
+// G state's input-sorted arcs, back-off epsilons after a word only, interval or label-set look-ahead) applied to
 // ONE composed state at a time, by the wave of the search that needs it:
 //   invariant   every arc a live instance sits on leads to a CLOSED state: one that has its arcs and whose
 //               epsilon / tee arcs lead to closed states (what a token can reach within a frame) - phase X
@@ -42,6 +42,15 @@ enum { LZ_UNKNOWN = 0, LZ_EXPANDING = 1, LZ_EXPANDED = 2, LZ_CLOSED = 3 };
 #define LA_MAYFIN 0x80000000u
 __device__ __host__ __forceinline__ int la_hi(int2 la) { return (int)((unsigned)la.y & ~LA_MAYFIN); }
 __device__ __host__ __forceinline__ bool la_mayfin(int2 la) { return ((unsigned)la.y & LA_MAYFIN) != 0; }
+// Label-SET look-ahead (JD_LOOKAHEAD_SETS; host side: jd_labelsets.h): the words are renumbered so that most sets are
+// intervals again, and such a state's entry is as above.  A state whose set is NOT all of [lo, hi] carries LA_LIST (the
+// sign bit of lo) and has its labels, sorted, in set_lab[set_row[c] .. set_row[c + 1]); [lo, hi] still bounds them, so
+// the interval test comes first and the list is only looked at when it passes.  Without the option no entry has the bit
+// and set_row / set_lab are null.
+#define LA_LIST 0x80000000u
+#define LA_WAVE_MIN 32               // a list test of more than this many steps is done by the whole wave, 64 labels per step
+__device__ __host__ __forceinline__ int la_lo(int2 la) { return (int)((unsigned)la.x & ~LA_LIST); }
+__device__ __host__ __forceinline__ bool la_list(int2 la) { return ((unsigned)la.x & LA_LIST) != 0; }
 
 struct LazyDev {
     const int *cl_row; const JdArc *cl_arcs; const float *cl_fin; const int2 *cl_la;
@@ -54,6 +63,7 @@ struct LazyDev {
     int max_states; long long max_arcs;
     int push;                         // weights pushed along the lexicon tree (jd_compose.hip "pushing")
     int *err;                         // 1: states exhausted, 2: arcs exhausted, 3: a wave's queue overflowed
+    const int *set_row, *set_lab;     // label lists of the look-ahead (LA_LIST); null without JD_LOOKAHEAD_SETS
 };
 
 // 8-byte write-through (agent-scope) stores: the graph is read by other workgroups, on any XCD, with `sc1` loads
@@ -71,6 +81,186 @@ __device__ __forceinline__ unsigned long long lz_hash(unsigned long long k)
 {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
     return k;
+}
+
+// first arc in [lo, hi) of an input-sorted row whose input label is >= x
+__device__ __forceinline__ int la_lower(const JdArc *g_arcs, int lo, int hi, int x)
+{
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g_arcs[mid].in < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// position of x in the sorted labels lab[lo, hi), or of the first label above it
+__device__ __forceinline__ int la_lower_lab(const int *lab, int lo, int hi, int x)
+{
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (lab[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One lane: the sorted label list lab[l0, l1) against the input-sorted arcs g_arcs[r0, r1) of a G state (jc_any_in_set /
+// jc_potential_set of the composition, and the lazy expansion's).  The shorter of the two is walked and the longer one
+// binary-searched, from where the last search ended (both ascend).  all = false: leaves at the first common label;
+// all = true: *best = the best weight among the arcs with a common label.  Returns whether there is one.
+__device__ __forceinline__ bool la_set_lane(const JdArc *g_arcs, int r0, int r1, const int *lab, int l0, int l1, bool all, float *best)
+{
+    bool hit = false;
+    float b = 0.0f;
+    if (l1 - l0 <= r1 - r0) {
+        for (int i = l0; i < l1 && r0 < r1; ++i) {
+            const int x = lab[i];
+            r0 = la_lower(g_arcs, r0, r1, x);
+            if (r0 < r1 && g_arcs[r0].in == x) {
+                const float w = g_arcs[r0].w;
+                if (!hit || w > b) b = w;
+                hit = true;
+                if (!all) break;
+            }
+        }
+    } else {
+        for (int j = r0; j < r1 && l0 < l1; ++j) {
+            const int x = g_arcs[j].in;
+            l0 = la_lower_lab(lab, l0, l1, x);
+            if (l0 < l1 && lab[l0] == x) {
+                const float w = g_arcs[j].w;
+                if (!hit || w > b) b = w;
+                hit = true;
+                if (!all) break;
+            }
+        }
+    }
+    *best = b;
+    return hit;
+}
+
+// The same by a whole wave (every argument wave-uniform, all 64 lanes inside): 64 labels (or arcs) per step, each lane
+// one binary search over the other side; a ballot ends the `any` form at the first step with a hit, the `all` form
+// takes the maximum over the lanes at the end.  The result is wave-uniform.
+__device__ __forceinline__ bool la_set_wave(const JdArc *g_arcs, int r0, int r1, const int *lab, int l0, int l1, bool all, float *best)
+{
+    const int lane = threadIdx.x & 63;
+    bool hit = false;
+    float b = -__builtin_inff();
+    if (l1 - l0 <= r1 - r0) {
+        for (int i = l0; i < l1; i += 64) {
+            bool h = false;
+            if (i + lane < l1) {
+                const int x = lab[i + lane];
+                const int j = la_lower(g_arcs, r0, r1, x);
+                if (j < r1 && g_arcs[j].in == x) { h = true; b = fmaxf(b, g_arcs[j].w); }
+            }
+            hit = hit || __ballot(h) != 0ULL;
+            if (hit && !all) break;
+        }
+    } else {
+        for (int j = r0; j < r1; j += 64) {
+            bool h = false;
+            if (j + lane < r1) {
+                const int x = g_arcs[j + lane].in;
+                const int i = la_lower_lab(lab, l0, l1, x);
+                if (i < l1 && lab[i] == x) { h = true; b = fmaxf(b, g_arcs[j + lane].w); }
+            }
+            hit = hit || __ballot(h) != 0ULL;
+            if (hit && !all) break;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) b = fmaxf(b, __shfl_xor(b, o));
+    *best = hit ? b : 0.0f;
+    return hit;
+}
+
+// One lane, any length: does G state g have an arc with a label in the set behind entry `la` of C.L state c, and (all)
+// what is the best weight among such arcs (0 if none) - for the places where a single lane needs a state's potential
+// (lz_paid: the final weight of a state it has just created).
+template <class N> __device__ __forceinline__ bool la_lane_lookahead(const N &A, int g, int c, int2 la, bool all, float *pot)
+{
+    *pot = 0.0f;
+    const int lo_l = la_lo(la), hi_l = la_hi(la);
+    if (lo_l > hi_l) return false;
+    const int end = A.g_row[g + 1];
+    int r0 = la_lower(A.g_arcs, A.g_row[g], end, lo_l);
+    if (!la_list(la)) {
+        float best = 0.0f;
+        bool have = false;
+        for (; r0 < end && A.g_arcs[r0].in <= hi_l; ++r0) {
+            const float w = A.g_arcs[r0].w;
+            if (!have || w > best) best = w;
+            have = true;
+            if (!all) break;
+        }
+        *pot = best;
+        return have;
+    }
+    const int r1 = la_lower(A.g_arcs, r0, end, hi_l + 1);
+    return r1 > r0 && la_set_lane(A.g_arcs, r0, r1, A.set_lab, A.set_row[c], A.set_row[c + 1], all, pot);
+}
+
+// The look-ahead of up to 64 C.L states at ONE G state g (wave-uniform), called by all 64 lanes: a lane with ask set
+// gives its own C.L state c and that state's entry la, and gets whether g has an arc for a label of S(c) - and, with
+// all set, *pot = the best weight among those arcs (0 if none; without all, *pot is not meaningful).  Intervals and
+// short lists are done by the lane; the lanes whose list test is long hand it to the whole wave, one after the other.
+template <class N> __device__ __forceinline__ bool la_wave_lookahead(const N &A, int g, bool ask, int c, int2 la, bool all, float *pot)
+{
+    const int lane = threadIdx.x & 63;
+    bool hit = false, pending = false;
+    float best = 0.0f;
+    int r0 = 0, r1 = 0;
+    if (ask) {
+        const int lo_l = la_lo(la), hi_l = la_hi(la);
+        if (lo_l <= hi_l && la_list(la)) {
+            const int end = A.g_row[g + 1];
+            r0 = la_lower(A.g_arcs, A.g_row[g], end, lo_l);
+            r1 = la_lower(A.g_arcs, r0, end, hi_l + 1);
+            const int l0 = A.set_row[c], l1 = A.set_row[c + 1];
+            if (r1 > r0) {
+                if (min(l1 - l0, r1 - r0) > LA_WAVE_MIN) pending = true;
+                else hit = la_set_lane(A.g_arcs, r0, r1, A.set_lab, l0, l1, all, &best);
+            }
+        } else hit = la_lane_lookahead(A, g, c, la, all, &best);
+    }
+    for (unsigned long long m = __ballot(pending); m; m &= m - 1) {
+        const int j = __ffsll((long long)m) - 1;
+        const int cj = __shfl(c, j);
+        float b;
+        const bool h = la_set_wave(A.g_arcs, __shfl(r0, j), __shfl(r1, j), A.set_lab, A.set_row[cj], A.set_row[cj + 1], all, &b);
+        if (lane == j) { hit = h; best = b; }
+    }
+    *pot = hit ? best : 0.0f;
+    return hit;
+}
+
+// what C.L arc ca (of a lane that is `on`) contributes at G state g with label-set look-ahead: 0 = nothing, 1 = an arc;
+// *ga = the matched G arc (index, or -1); with all set, *pot = the potential of a label-less arc's destination.  Called
+// by all 64 lanes (la_wave_lookahead).
+template <class N> __device__ __forceinline__ int la_arc_kind(const N &A, bool on, const JdArc &ca, int g, bool all, int *ga, float *pot)
+{
+    *ga = -1;
+    const bool ask = on && ca.out == 0;
+    const int2 la = ask ? A.cl_la[ca.to] : make_int2(0x7fffffff, 0);
+    const bool hit = la_wave_lookahead(A, g, ask, ca.to, la, all, pot);
+    if (!on) return 0;
+    if (ca.out == 0) return (hit || (la_mayfin(la) && A.g_fin[g] < __builtin_inff())) ? 1 : 0;
+    int lo = A.g_row[g], hi = A.g_row[g + 1];                          // (lz_match / jc_match)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int l = A.g_arcs[mid].in;
+        if (l == ca.out) { *ga = mid; return 1; }
+        if (l < ca.out) lo = mid + 1; else hi = mid;
+    }
+    return 0;
+}
+// the potential of C.L state c at G state g (both wave-uniform), by the whole wave
+template <class N> __device__ __forceinline__ float la_wave_potential(const N &A, int g, int c)
+{
+    const int lane = threadIdx.x & 63;
+    float p = 0.0f;
+    (void)la_wave_lookahead(A, g, lane == 0, c, A.cl_la[c], true, &p);
+    return __shfl(p, 0);
 }
 
 // weight look-ahead (pushing): the best weight among the arcs of G state g with an input label in [lo, hi] (0 if none)
@@ -97,6 +287,9 @@ __device__ __forceinline__ float lz_paid(const LazyDev &L, unsigned cf, int g)
 {
     if (!L.push || (cf & LZ_FLAG)) return 0.0f;
     const int2 la = L.cl_la[cf];
+    // (sets: ONE lane walks the list, however long it is - this is called by the lane that has just created a state, inside
+    // lz_state_id's compare-and-swap branch, where the wave cannot help.  Rare: only a FINAL composed state with f = 0 asks)
+    if (L.set_row) { float p; (void)la_lane_lookahead(L, g, (int)cf, la, true, &p); return p; }
     return lz_potential(L, g, la.x, la_hi(la));
 }
 
@@ -193,9 +386,17 @@ __device__ bool lz_expand(const LazyDev &L, const float *hmm_tee, int D)
     JdArc boa = {0, 0.0f, 0, 0};
     if (flag && L.g_row[g + 1] > L.g_row[g]) { boa = L.g_arcs[L.g_row[g]]; bo = boa.in == 0; }
     const int a0 = L.cl_row[c], a1 = L.cl_row[c + 1];
-    const float p_src = lz_paid(L, cf, g);
+    const bool sets = L.set_row != nullptr;                            // label-set look-ahead (wave-uniform)
+    const float p_src = (sets && L.push && !flag) ? la_wave_potential(L, g, c) : lz_paid(L, cf, g);
     int mine = 0, ga;
-    for (int a = a0 + lane; a < a1; a += 64) mine += lz_arc_kind(L, L.cl_arcs[a], g, &ga);
+    float pot = 0.0f;
+    if (sets)
+        for (int a = a0; a < a1; a += 64) {
+            const bool on = a + lane < a1;
+            mine += la_arc_kind(L, on, on ? L.cl_arcs[a + lane] : JdArc{0, 0.0f, 0, 0}, g, false, &ga, &pot);
+        }
+    else
+        for (int a = a0 + lane; a < a1; a += 64) mine += lz_arc_kind(L, L.cl_arcs[a], g, &ga);
     int total = mine;
 #pragma unroll
     for (int o = 32; o; o >>= 1) total += __shfl_xor(total, o);
@@ -217,7 +418,9 @@ __device__ bool lz_expand(const LazyDev &L, const float *hmm_tee, int D)
         JdArc ca = {0, 0.0f, 0, 0};
         int cnt = 0;
         ga = -1;
-        if (on) { ca = L.cl_arcs[a + lane]; cnt = lz_arc_kind(L, ca, g, &ga); }
+        if (on) ca = L.cl_arcs[a + lane];
+        if (sets) cnt = la_arc_kind(L, on, ca, g, L.push != 0, &ga, &pot);
+        else if (on) cnt = lz_arc_kind(L, ca, g, &ga);
         int pre = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(pre, o); if (lane >= o) pre += y; }
@@ -228,7 +431,10 @@ __device__ bool lz_expand(const LazyDev &L, const float *hmm_tee, int D)
             const int in = ca.in | (tee ? TEE_FLAG : 0);
             if (ca.out == 0) {
                 float w = ca.w;
-                if (L.push) { const int2 la = L.cl_la[ca.to]; w = (ca.w + lz_potential(L, g, la.x, la_hi(la))) - p_src; }
+                if (L.push) {
+                    if (!sets) { const int2 la = L.cl_la[ca.to]; pot = lz_potential(L, g, la.x, la_hi(la)); }
+                    w = (ca.w + pot) - p_src;
+                }
                 lz_store_arc(&L.arcs[pos], lz_state_id(L, (unsigned)ca.to, g), w, in, 0);
             } else {
                 const JdArc m = L.g_arcs[ga];

@@ -16,7 +16,7 @@ Rules forced by the reference's behaviour (cited so the generators stay legal):
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional
 
 import numpy as np
@@ -428,6 +428,22 @@ def make_cl_g(seed: int, am: SynthAM, n_words: int, n_succ: int, n_tri: int = 0,
                  fweight_file=rng.uniform(0.0, 2.0, size=fstate.shape[0]).astype(np.float32),
                  n_words=V, prons=cl.prons, succ=succ, sp_hmm=cl.sp_hmm)
     return cl, g
+
+
+def random_word_permutation(cl: SynthNet, g: SynthNet, seed: int) -> np.ndarray:
+    """A random renumbering of the words of a (C.L, G) pair: perm[old label] = new label, perm[0] = 0."""
+    n = int(max(cl.olab.max(), g.ilab.max()))
+    perm = np.zeros(n + 1, np.int32)
+    perm[1:] = 1 + np.random.default_rng(seed).permutation(n)
+    return perm
+
+
+def permute_words(cl: SynthNet, g: SynthNet, perm):
+    """The pair with its words renumbered: C.L's output labels and G's INPUT labels.  G's output labels - what a composed
+    graph and a hypothesis carry - stay, so results need no mapping back.  (make_cl_g numbers the words in the lexicon tree's
+    depth-first order; a real vocabulary is numbered by spelling.)"""
+    perm = np.asarray(perm, np.int32)
+    return replace(cl, olab=perm[cl.olab]), replace(g, ilab=perm[g.ilab])
 
 
 def make_wfst_sized(seed: int, am: SynthAM, target_arcs: int, n_words: int,
