@@ -68,6 +68,20 @@ static SearchKernel slot_kernel(bool ne3, bool mdl)
     return tab[(mdl ? 0 : 2) + (ne3 ? 0 : 1)];
 }
 
+// the decoder's place in the per-device tables (g_search_mu and its counters)
+static size_t dev_index(const jd_dec *d) { return (size_t)std::min(std::max(d->device, 0), JD_MAX_DEVICES - 1); }
+
+// The device's search lock, taken: whoever waits for it is counted (a resident kernel makes room: jd_res_should_yield), and
+// whoever gets it counts the turn up (jd_res_yield: the one who let go sees the waiter take it).
+static std::unique_lock<std::mutex> lock_search(size_t dev_i)
+{
+    g_search_waiters[dev_i].fetch_add(1);
+    std::unique_lock<std::mutex> lock(g_search_mu[dev_i]);
+    g_search_waiters[dev_i].fetch_sub(1);
+    g_search_turn[dev_i].fetch_add(1);
+    return lock;
+}
+
 static int pf_launch(jd_dec *d);
 static bool pf_wants_scoring(const jd_dec *d);
 static double pf_scoring_rows(const jd_dec *d);
@@ -290,11 +304,7 @@ static int launch_search(jd_dec *d, const std::vector<int2> &work_first, const f
         // out: launches on one device are serialised here, from dispatch to completion.  (Other PROCESSES on the device
         // are outside this lock: the dispatcher starts the workgroups of a kernel in order, and a kernel that cannot
         // become fully resident ends in JDE_BARRIER after 30 s instead of hanging.)
-        const size_t dev_i = (size_t)std::min(std::max(d->device, 0), JD_MAX_DEVICES - 1);
-        g_search_waiters[dev_i].fetch_add(1);
-        std::unique_lock<std::mutex> search_lock(g_search_mu[dev_i]);
-        g_search_waiters[dev_i].fetch_sub(1);
-        g_search_turn[dev_i].fetch_add(1);
+        const std::unique_lock<std::mutex> search_lock = lock_search(dev_index(d));
         GpuLockGuard process_lock(d->device);                              // (other processes on this GPU: see GpuFileLock)
         const bool hold_replan = hold_replan_for_scoring(d, weight);
         bool slot_batch = false;

@@ -2,9 +2,12 @@
 // its own: it lives in jd_device.hip's TU because the kernels it launches are templates of that TU).
 //
 //   * Resident: the mailbox protocol of jd_resident.h / jd_slot.h (commands in host-mapped words, ready numbers counted up on the side
-//     stream, reports, the host heartbeat) - jd_res_start / _stop / _post / _poll / _collect / _finish, driven by jd_broker.cpp;
+//     stream, reports, the host heartbeat) - jd_res_start / _stop / _post / _poll / _collect / _finish, driven by jd_broker.cpp; the
+//     kernel's geometry is jd_plan.h's plan_resident, jd_res_start the steps that bring it onto the device;
 //   * Pipe: batches through the resident slot kernel utterance by utterance (jd_dec_set_pipeline: JD_FLOW_RESIDENT) - pipe_announce,
-//     pipe_pump, pipe_decode, jd_dec_quiesce, jd_dec_pipeline_stats.
+//     pipe_pump, pipe_decode, jd_dec_quiesce, jd_dec_pipeline_stats;
+//   * at the end, the setters that drop what the pipeline holds: jd_dec_set_output_level / _get_output_level, jd_dec_model_result,
+//     jd_dec_set_scoring.
 // The launch-per-call paths (one batch, two batches in flight, re-planning, the streaming calls) stay in jd_device.hip.
 #pragma once
 
@@ -14,6 +17,22 @@
 // allocates or frees device memory or synchronises the device - either would wait for the kernel.
 #define RES_RING 256
 #define RES_RING_W 2048
+struct ResStream {                                     // the protocol as the host sees it, for one stream
+    unsigned seq;                                      // last sequence number posted
+    unsigned rid;                                      // the last ready number enqueued for it (Resident::d_ready: how far the side stream has come)
+    int T_posted, T_done, err_done;
+    int slot_posted;
+    bool busy;                                         // a command is posted and its report not yet taken
+    bool init_pending;                                 // ... and it begins an utterance (ResPost::init): a re-post must say so again
+    // The kernel starts: the numbers of both sides begin again.  What the host knows of a stream beyond them - where it stands, a
+    // report not yet taken, an init that a re-post has to repeat - survives a restart; a new record (T_now: where the decoder's
+    // stream stands) is idle there.
+    void reset(const int *T_now)
+    {
+        seq = rid = 0u;
+        if (T_now) { T_posted = T_done = *T_now; err_done = slot_posted = 0; busy = init_pending = false; }
+    }
+};
 struct Resident {
     bool on = false;
     int n = 0, Cw = 0, rows = 0;                       // streams [0, n), workgroups per cluster, rows per likelihood buffer
@@ -23,17 +42,12 @@ struct Resident {
     ResDone *h_done = nullptr;                         // host-mapped: the reports
     unsigned *h_beat = nullptr;                        // host-mapped: counted up whenever the host looks after the kernel (k_resident: beat)
     unsigned *d_ready = nullptr;                       // per stream: how far the side stream has come for it
-    std::vector<unsigned> rid;                         // ... and the last number enqueued for it
+    std::vector<ResStream> stream;
     int *h_ring = nullptr, *d_ring = nullptr;          // row-tile lists of the scoring launches (RES_RING slots of RES_RING_W)
     int ring_turn = 0;
     float *d_feat = nullptr, *d_ll = nullptr;          // [n][2][rows] x D / x G
     int *d_src = nullptr;
     char *h_stage = nullptr;                           // pinned: the features of every buffer, [n][2][rows] x D
-    std::vector<unsigned> seq;                         // last sequence number posted per stream
-    std::vector<int> T_posted, T_done, err_done;
-    std::vector<int> slot_posted;
-    std::vector<char> busy;                            // a command is posted and its report not yet taken
-    std::vector<char> init_pending;                    // ... and it begins an utterance (ResPost::init): a re-post must say so again
     long long run_ticks = 0;                           // (statistics) what the clusters spent on their commands, 100 MHz ticks
     long long n_collect = 0;                           // (statistics) Path collections between commands
     std::unique_lock<std::mutex> search_lock;
@@ -63,24 +77,45 @@ static void res_free(jd_dec *d)
     d->res = nullptr;
 }
 
+// pred() every sleep_us until it holds or ms are over; whether it held
+template <class Pred>
+static bool wait_until(Pred pred, double ms, int sleep_us)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!pred()) {
+        if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() >= ms) return false;
+        std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+    }
+    return true;
+}
+
+// a workgroup of streams [0, n) has left the kernel (no command for 5 s, an exit request, a lost workgroup)
+static bool res_any_left(const Resident *R, int n)
+{
+    for (int s = 0; s < n; ++s)
+        if (__atomic_load_n(&R->h_done[s].left, __ATOMIC_ACQUIRE) != 0) return true;
+    return false;
+}
+
 // the report of stream s's command, if it is in
 static bool res_harvest(jd_dec *d, int s)
 {
     Resident *R = d->res;
-    if (!R->busy[(size_t)s]) return true;
-    if (__atomic_load_n(&R->h_done[s].seq, __ATOMIC_ACQUIRE) != R->seq[(size_t)s]) return false;
+    ResStream &S = R->stream[s];
+    if (!S.busy) return true;
+    if (__atomic_load_n(&R->h_done[s].seq, __ATOMIC_ACQUIRE) != S.seq) return false;
     if (d->pipe_on) {                                                  // (jd_dec_pipeline_stats: frames the slot has advanced)
-        d->pipe_frames_searched += std::max(0, R->h_done[s].frame - R->T_done[(size_t)s]);
+        d->pipe_frames_searched += std::max(0, R->h_done[s].frame - S.T_done);
         d->pipe_busy_ticks += R->h_done[s].run_ticks;
     }
-    R->T_done[(size_t)s] = R->h_done[s].frame; R->err_done[(size_t)s] = R->h_done[s].error;
+    S.T_done = R->h_done[s].frame; S.err_done = R->h_done[s].error;
     // (a stream that failed on the device - an arena overflow, a lost workgroup - may hold anything: wiped before its next init,
     // whether or not anybody fetches its result)
-    if (R->err_done[(size_t)s] != 0) d->stream_dirty[(size_t)s] = 1;
+    if (S.err_done != 0) d->stream_dirty[(size_t)s] = 1;
     R->run_ticks += R->h_done[s].run_ticks;
-    R->init_pending[(size_t)s] = 0;
-    d->stream_T[(size_t)s] = R->T_done[(size_t)s];
-    R->busy[(size_t)s] = 0;
+    S.init_pending = false;
+    d->stream_T[(size_t)s] = S.T_done;
+    S.busy = false;
     return true;
 }
 
@@ -97,7 +132,7 @@ int jd_res_stop(jd_dec *d)
     bool lost = false;
     for (int s = 0; s < R->n; ++s)
         if (!res_harvest(d, s)) {
-            R->busy[(size_t)s] = 0;
+            R->stream[s].busy = false;
             // a command the cluster never saw (it left by itself - idle for 5 s - just before the word was written) has not been
             // started: the stream stands where its last report says, short of what was posted, and whoever drives it posts the
             // rest again (the same way as behind a Path collection).  Anything else is a lost workgroup.
@@ -112,6 +147,215 @@ int jd_res_stop(jd_dec *d)
     return JD_OK;
 }
 
+// ---- jd_res_start, step by step
+
+// The flavours of the kernels that stay on the device (the counterparts of jd_host_launch.h's search_kernel / slot_kernel; they are
+// here and in this order because a template kernel's place in the device code object is where the translation unit first names it,
+// and the object stays as it has been): k_slot (jd_slot.h: HMM size class, word / model-level output) ...
+typedef void (*SlotMailboxKernel)(SearchArgs, const ResPost *, const unsigned *, ResDone *, const unsigned *, unsigned *);
+static SlotMailboxKernel slot_mailbox_kernel(bool ne3, bool mdl)
+{
+    static const SlotMailboxKernel tab[4] = { k_slot<3, true>, k_slot<3, false>, k_slot<6, true>, k_slot<6, false> };
+    return tab[(ne3 ? 0 : 2) + (mdl ? 0 : 1)];
+}
+// ... and k_resident (jd_resident.h: HMM size class, agent-scope / XCD-local memory model, word / model-level output)
+typedef void (*ResidentKernel)(SearchArgs, const ResPost *, ResMail *, const unsigned *, ResDone *, int, const unsigned *);
+static ResidentKernel resident_kernel(bool ne3, bool xl, bool mdl)
+{
+    static const ResidentKernel tab[8] = {
+        k_resident<3, false, true>, k_resident<3, false, false>, k_resident<6, false, true>, k_resident<6, false, false>,
+        k_resident<3, true, true>, k_resident<6, true, true>, k_resident<3, true, false>, k_resident<6, true, false>,
+    };
+    return tab[xl ? 4 + (mdl ? 0 : 2) + (ne3 ? 0 : 1) : (ne3 ? 0 : 2) + (mdl ? 0 : 1)];
+}
+
+static int res_knob(const char *name) { const char *e = jd_dev_env(name); return e ? atoi(e) : -1; }   // development; -1: unset
+
+// the kernel's geometry (jd_plan.h: plan_resident) from the decoder and the development knobs
+static ResPlanOut res_plan(const jd_dec *d, int n_streams, int rows_per_buf)
+{
+    ResPlanIn in;
+    in.n_cus = d->n_cus; in.n_streams = n_streams; in.rows_per_buf = rows_per_buf;
+    in.max_cw = d->max_cw; in.cap_slots = d->cap_slots; in.cap_items = d->cap_items;
+    in.pipeline = d->res_ll != nullptr;
+    in.free_cus = res_knob("JD_RES_FREE_CUS"); in.slot = res_knob("JD_RES_SLOT"); in.xl = res_knob("JD_RES_XL"); in.keep_se = res_knob("JD_SLOT_KEEP_SE");
+    in.sw = SW; in.wg_per_cu = WG_PER_CU; in.slot_wg_per_cu = SLOT_WG_PER_CU; in.gmm_rows2 = GMM_ROWS2; in.res_ring_w = RES_RING_W;
+    return plan_resident(in);
+}
+
+static int res_fill(jd_dec *d, Resident *R, int n_streams, int rows)
+{
+    const int D = d->am->D, G = d->am->n_gmm;
+    R->n = n_streams; R->rows = rows;
+    const size_t tr = (size_t)n_streams * 2 * rows;
+    if (hipMalloc(&R->d_mail, (size_t)n_streams * sizeof(ResMail)) != hipSuccess ||
+        hipHostMalloc((void **)&R->h_post, (size_t)n_streams * sizeof(ResPost), hipHostMallocMapped) != hipSuccess ||
+        hipHostMalloc((void **)&R->h_done, (size_t)n_streams * sizeof(ResDone), hipHostMallocMapped) != hipSuccess ||
+        hipHostMalloc((void **)&R->h_beat, 64, hipHostMallocMapped) != hipSuccess ||
+        hipMalloc(&R->d_ready, (size_t)n_streams * sizeof(unsigned)) != hipSuccess ||
+        hipHostMalloc((void **)&R->h_ring, (size_t)RES_RING * RES_RING_W * sizeof(int)) != hipSuccess ||
+        hipMalloc(&R->d_ring, (size_t)RES_RING * RES_RING_W * sizeof(int)) != hipSuccess ||
+        hipMalloc(&R->d_feat, tr * D * sizeof(float)) != hipSuccess || hipMalloc(&R->d_ll, tr * G * sizeof(float)) != hipSuccess ||
+        hipMalloc(&R->d_src, tr * sizeof(int)) != hipSuccess ||
+        hipHostMalloc((void **)&R->h_stage, tr * D * sizeof(float)) != hipSuccess)
+        return jd_fail(JD_ENOMEM, "jd_res_start: no memory for %d streams x 2 x %d rows", n_streams, rows);
+    *R->h_beat = 0u;
+    R->stream.resize((size_t)n_streams);
+    for (int t = 0; t < n_streams; ++t) R->stream[t].reset(&d->stream_T[(size_t)t]);
+    std::vector<int> ident(tr);            // the row table of every scoring launch: row r of the table is row r of the features
+    for (size_t r = 0; r < tr; ++r) ident[r] = (int)r;
+    HIPCHK(hipMemcpy(R->d_src, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
+    return JD_OK;
+}
+
+// d->res for n_streams streams and buffers of `rows` rows: the whole of it, or none (and the code)
+static int res_alloc(jd_dec *d, int n_streams, int rows)
+{
+    d->res = new Resident();
+    const int rc = res_fill(d, d->res, n_streams, rows);
+    if (rc) res_free(d);
+    return rc;
+}
+
+// the kernel is about to start: an empty mailbox, and the numbers of both sides begin again (ResStream::reset)
+static void res_reset(Resident *R)
+{
+    memset(R->h_done, 0, (size_t)R->n * sizeof(ResDone));
+    memset(R->h_post, 0, (size_t)R->n * sizeof(ResPost));
+    for (ResStream &S : R->stream) S.reset(nullptr);
+}
+
+// all the kernel's workgroups have to be resident at once: asked of the runtime for the kernel the plan chose
+static int res_occupancy(const jd_dec *d, const Resident *R)
+{
+    const bool ne3 = d->am->max_n <= 5;
+    int per_cu = 0;
+    // (k_resident: asked of the agent-scope flavour, XL = false, even where the XCD-local one is what is launched - as it has
+    // always been; the two differ in the scope of their memory operations.  Known, and not changed here.)
+    const void *kf = R->slot ? (const void *)slot_mailbox_kernel(ne3, d->models) : (const void *)resident_kernel(ne3, false, d->models);
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, SNT, 0));
+    const int need = R->slot ? SLOT_WG_PER_CU : WG_PER_CU;
+    if (per_cu < need)
+        return jd_fail(R->slot ? JD_EINVAL : JD_EHIP, "%s: %d workgroup(s) per CU fit, %d streams on %d CUs need %d", R->slot ? "k_slot" : "k_resident",
+                       per_cu, R->n, d->n_cus, need);
+    return JD_OK;
+}
+
+// The locks the kernel owns while it is on the device - the device's search lock, the GPU's file lock - go back when
+// jd_res_start is left without it (R->on is not set), whichever way.
+struct ResLocks {
+    Resident *R;
+    ~ResLocks()
+    {
+        if (R->on) return;
+        delete R->process_lock; R->process_lock = nullptr;
+        if (R->search_lock.owns_lock()) R->search_lock.unlock();
+    }
+};
+
+struct ResLaunch {                                     // what an attempt to start the kernel takes, the same for every attempt
+    SearchArgs A;
+    bool ne3, xl;
+    int park_cus, park_fill;                           // (slots) CUs parked while the grid is dealt, and the slots that find room beside them
+    hipEvent_t ev_side = nullptr, ev_null = nullptr;   // behind the probes on the side stream and the null stream
+    ~ResLaunch() { if (ev_side) (void)hipEventDestroy(ev_side); if (ev_null) (void)hipEventDestroy(ev_null); }
+};
+
+static int res_launch_init(jd_dec *d, const Resident *R, const ResPlanOut &P, ResLaunch *L)
+{
+    SearchArgs &A = L->A;
+    memset(&A, 0, sizeof A);
+    A.C = d->C; A.ctl = d->d_ctl; A.streams = d->d_streams; A.work = nullptr; A.n_work = R->n; A.Cw = R->Cw; A.n_slots = 0;
+    A.ll = d->res_ll ? d->res_ll : R->d_ll; A.ll_stride = (long long)d->am->n_gmm; A.f0 = 0; A.f_end = 0x7fffffff;
+    A.status = d->d_status; A.dbg = d->d_dbg; A.cells = nullptr; A.resident = nullptr; A.rebalance_at = 0; A.n_prio = 0;   // (dbg: jd_dec_debug_trace)
+    L->ne3 = d->am->max_n <= 5; L->xl = P.xl;
+    L->park_cus = P.park_cus; L->park_fill = P.park_fill;
+    if (L->park_cus > 0 && !d->h_park) {                               // (jd_park_kernel's words; without them nothing is parked)
+        if (hipHostMalloc((void **)&d->h_park, 64, hipHostMallocMapped) != hipSuccess || hipMalloc(&d->d_park, 64 * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            L->park_cus = 0;
+        }
+    }
+    HIPCHK(hipEventCreateWithFlags(&L->ev_side, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&L->ev_null, hipEventDisableTiming));
+    return JD_OK;
+}
+
+// Where the slots go.  A grid of at most one workgroup per CU is dealt one per CU, and that is what the pipeline wants: a slot's eight
+// waves take two of a SIMD's four wave slots and half its registers, the scoring kernel's waves (127 VGPRs, no LDS) take the other half
+// of the SAME CU - a search that waits for memory beside arithmetic that does not: 256 slots on 256 CUs 18.1 ms per configs[1] batch,
+// against 21.5 with the slots two per CU on half the chip and the scoring on the other half (jd_slot.h: jd_park_kernel, which is how
+// such a split is made: JD_SLOT_KEEP_SE = CUs per shader engine the slots get, development), 19.1 with 272 and 21.1 with 304 slots
+// dealt over all CUs (the CUs that hold two slots have no room for the scoring).
+static void park_and_launch_slots(jd_dec *d, Resident *R, const ResLaunch &L)
+{
+    bool parked = false;
+    if (L.park_cus > 0) {
+        // the CUs of every XCD that the slots are NOT to get: parked until the slots are on theirs
+        d->h_park[0] = d->h_park[1] = d->h_park[2] = d->h_park[3] = d->h_park[4] = 0u;
+        if (hipMemsetAsync(d->d_park, 0, 64 * sizeof(int), d->s_gmm) == hipSuccess) {
+            hipLaunchKernelGGL(jd_park_kernel, dim3((unsigned)d->n_cus), dim3(64), 0, d->s_gmm, (unsigned *)d->d_park, L.park_cus / 32, d->h_park);
+            parked = hipGetLastError() == hipSuccess;
+        }
+        if (parked)
+            wait_until([&] { return __atomic_load_n(&d->h_park[0], __ATOMIC_ACQUIRE) + __atomic_load_n(&d->h_park[1], __ATOMIC_ACQUIRE) >= (unsigned)d->n_cus; },
+                       50.0, 20);
+    }
+    unsigned *started = parked ? d->h_park + 4 : nullptr;
+    hipLaunchKernelGGL(slot_mailbox_kernel(L.ne3, d->models), dim3((unsigned)R->n), dim3(SNT), 0, R->st, L.A, R->h_post, R->d_ready, R->h_done, R->h_beat,
+                       started);
+    if (!parked) return;
+    // every slot is on its CU (or 100 ms are over): the parked CUs are the scoring's
+    const auto tp = std::chrono::steady_clock::now();
+    wait_until([&] { return __atomic_load_n(&d->h_park[4], __ATOMIC_ACQUIRE) >= (unsigned)L.park_fill; }, 100.0, 20);
+    if (getenv("JD_VERBOSE"))
+        fprintf(stderr, "k_slot: %u CUs parked (%u left free), %u of %d slots on their CUs after %.2f ms\n", d->h_park[0], d->h_park[1], d->h_park[4], R->n,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count());
+    __atomic_store_n(&d->h_park[2], 1u, __ATOMIC_RELEASE);
+}
+
+// HIP maps streams onto a few hardware queues, and whatever is queued BEHIND a kernel that stays waits until it leaves:
+// the side stream's scoring, the null stream's copies back.  Which queue a stream gets is the runtime's business
+// (tools/resident_alias_probe.py: one fresh stream in fourteen lands behind the kernel), so the kernel is started, a
+// small kernel is sent down the side stream and the null stream, and if either has not come back in 150 ms the
+// resident kernel leaves again (jd_res_start: it comes back on a NEW search stream - a few times, then it is an error).
+// One attempt.  *clear: the kernel is on the device and neither stream is queued behind it.
+static hipError_t launch_and_probe(jd_dec *d, Resident *R, const ResLaunch &L, bool *clear)
+{
+    hipLaunchKernelGGL(jd_res_reset_kernel, dim3((R->n + 63) / 64), dim3(64), 0, R->st, d->d_ctl, R->d_mail, R->d_ready, R->n);
+    __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELEASE);
+    if (R->slot) park_and_launch_slots(d, R, L);
+    else
+        hipLaunchKernelGGL(resident_kernel(L.ne3, L.xl, d->models), dim3((unsigned)(R->n * R->Cw)), dim3(SNT), 0, R->st, L.A, R->h_post, R->d_mail, R->d_ready,
+                           R->h_done, R->Cw, R->h_beat);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    ReadyList none; none.n = 0;
+    hipLaunchKernelGGL(jd_res_ready_kernel, dim3(1), dim3(64), 0, d->s_gmm, R->d_ready, none);
+    (void)hipEventRecord(L.ev_side, d->s_gmm);
+    hipLaunchKernelGGL(jd_res_ready_kernel, dim3(1), dim3(64), 0, (hipStream_t)0, R->d_ready, none);
+    (void)hipEventRecord(L.ev_null, (hipStream_t)0);
+    *clear = wait_until([&] { return hipEventQuery(L.ev_side) == hipSuccess && hipEventQuery(L.ev_null) == hipSuccess; }, 150.0, 200);
+    if (*clear) return hipSuccess;
+    // behind the kernel: it leaves (the exit word) and what waited for it runs
+    for (int t = 0; t < R->n; ++t) __atomic_store_n(&R->h_post[t].exit_req, 1, __ATOMIC_RELEASE);
+    (void)hipStreamSynchronize(R->st);
+    (void)hipEventSynchronize(L.ev_side); (void)hipEventSynchronize(L.ev_null);
+    res_reset(R);
+    return hipSuccess;
+}
+
+// the search stream is made anew (for the kernel's next attempt)
+static bool fresh_search_stream(jd_dec *d, Resident *R)
+{
+    hipStream_t fresh = nullptr;
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    if (hipStreamCreateWithPriority(&fresh, hipStreamNonBlocking, prio_hi) != hipSuccess) return false;
+    d->res_old_streams.push_back(d->s_search);                         // (destroyed with the decoder: somebody may still hold it)
+    d->s_search = fresh; R->st = fresh;
+    return true;
+}
+
 // streams [0, n_streams) of the decoder, likelihood buffers of rows_per_buf rows (two per stream)
 int jd_res_start(jd_dec *d, int n_streams, int rows_per_buf)
 {
@@ -123,211 +367,52 @@ int jd_res_start(jd_dec *d, int n_streams, int rows_per_buf)
     rc = ensure_arenas(d);
     if (rc) return rc;
     if (!d->pipe_on) pf_discard(d);                      // (not when the batch pipeline's kernel comes back: jd_dec_quiesce)
-    const int D = d->am->D, G = d->am->n_gmm;
-    const int rows = (rows_per_buf + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
-    if (d->res && (d->res->n != n_streams || d->res->rows != rows)) { if (d->res->on) { rc = jd_res_stop(d); if (rc) return rc; } res_free(d); }
+    const ResPlanOut P = res_plan(d, n_streams, rows_per_buf);
+    if (d->res && (d->res->n != n_streams || d->res->rows != P.rows)) { if (d->res->on) { rc = jd_res_stop(d); if (rc) return rc; } res_free(d); }
     if (!d->res) {
-        Resident *R = new Resident();
-        d->res = R;
-        R->n = n_streams; R->rows = rows;
-        const size_t tr = (size_t)n_streams * 2 * rows;
-        if (n_streams > 1024 || 2 * n_streams * ((rows + GMM_ROWS2 - 1) / GMM_ROWS2) > RES_RING_W) {
-            res_free(d);
-            return jd_fail(JD_EINVAL, "jd_res_start: at most 1024 streams and %d row tiles per scoring launch", RES_RING_W);
-        }
-        if (hipMalloc(&R->d_mail, (size_t)n_streams * sizeof(ResMail)) != hipSuccess ||
-            hipHostMalloc((void **)&R->h_post, (size_t)n_streams * sizeof(ResPost), hipHostMallocMapped) != hipSuccess ||
-            hipHostMalloc((void **)&R->h_done, (size_t)n_streams * sizeof(ResDone), hipHostMallocMapped) != hipSuccess ||
-            hipHostMalloc((void **)&R->h_beat, 64, hipHostMallocMapped) != hipSuccess ||
-            hipMalloc(&R->d_ready, (size_t)n_streams * sizeof(unsigned)) != hipSuccess ||
-            hipHostMalloc((void **)&R->h_ring, (size_t)RES_RING * RES_RING_W * sizeof(int)) != hipSuccess ||
-            hipMalloc(&R->d_ring, (size_t)RES_RING * RES_RING_W * sizeof(int)) != hipSuccess ||
-            hipMalloc(&R->d_feat, tr * D * sizeof(float)) != hipSuccess || hipMalloc(&R->d_ll, tr * G * sizeof(float)) != hipSuccess ||
-            hipMalloc(&R->d_src, tr * sizeof(int)) != hipSuccess ||
-            hipHostMalloc((void **)&R->h_stage, tr * D * sizeof(float)) != hipSuccess) {
-            res_free(d);
-            return jd_fail(JD_ENOMEM, "jd_res_start: no memory for %d streams x 2 x %d rows", n_streams, rows);
-        }
-        *R->h_beat = 0u;
-        R->seq.assign((size_t)n_streams, 0u); R->T_posted.assign((size_t)n_streams, 0); R->T_done.assign((size_t)n_streams, 0);
-        R->slot_posted.assign((size_t)n_streams, 0); R->err_done.assign((size_t)n_streams, 0); R->busy.assign((size_t)n_streams, 0); R->init_pending.assign((size_t)n_streams, 0);
-        for (int t = 0; t < n_streams; ++t) R->T_done[(size_t)t] = R->T_posted[(size_t)t] = d->stream_T[(size_t)t];
-        R->rid.assign((size_t)n_streams, 0u);
-        std::vector<int> ident(tr);            // the row table of every scoring launch: row r of the table is row r of the features
-        for (size_t r = 0; r < tr; ++r) ident[r] = (int)r;
-        HIPCHK(hipMemcpy(R->d_src, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
+        // (the limits bind where a Resident is made: one that exists has passed them)
+        if (P.verdict == RES_PLAN_LIMITS) return jd_fail(JD_EINVAL, "jd_res_start: at most 1024 streams and %d row tiles per scoring launch", RES_RING_W);
+        rc = res_alloc(d, n_streams, P.rows);
+        if (rc) return rc;
     }
     Resident *R = d->res;
     if (R->on) return JD_OK;
-    const bool ne3 = d->am->max_n <= 5;
-    // clusters: what the arenas allow, and a sixth of the chip left to the scoring, collection and finish kernels
-    const int cw_cap = (int)std::max<int64_t>(1, std::min<int64_t>(d->cap_slots / (64 * SW), d->cap_items / (512 * SW)));
-    // (the scoring of what the streams search: about 1.6 CUs per stream at their pace, and a quarter of the chip at least -
-    // sixteen C++ callers: 407 k frames/s with 24 CUs left, 433 k with 40, 469 k with 64, 462 k with 96)
-    int free_cus = std::min(d->n_cus / 2, std::max(d->n_cus / 4, (n_streams * 8) / 5));
-    if (const char *e = jd_dev_env("JD_RES_FREE_CUS")) { const int v = atoi(e); if (v >= 0 && v < d->n_cus) free_cus = v; }   // development
-    R->Cw = std::max(1, std::min(std::min(d->max_cw, cw_cap), (d->n_cus * WG_PER_CU - free_cus) / n_streams));
-    if (d->res_ll) R->Cw = 1;                                          // (the batch pipeline: every stream a slot of ONE workgroup, however few they are)
-    // One workgroup per stream: the slot kernel (jd_slot.h) - compiled for four waves per SIMD, SLOT_WG_PER_CU workgroups per CU,
-    // every per-frame word in LDS.  (JD_RES_SLOT=0, development: k_resident's one-workgroup clusters, one per CU.)
-    R->slot = R->Cw == 1;
-    if (const char *e = jd_dev_env("JD_RES_SLOT")) R->slot = R->slot && atoi(e) != 0;
-    {
-        int per_cu = 0;
-        const bool m = d->models;
-        const void *kf = R->slot ? (ne3 ? (m ? (const void *)k_slot<3, true> : (const void *)k_slot<3, false>)
-                                        : (m ? (const void *)k_slot<6, true> : (const void *)k_slot<6, false>))
-                                 : (ne3 ? (m ? (const void *)k_resident<3, false, true> : (const void *)k_resident<3, false, false>)
-                                        : (m ? (const void *)k_resident<6, false, true> : (const void *)k_resident<6, false, false>));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, SNT, 0));
-        const int need = R->slot ? SLOT_WG_PER_CU : WG_PER_CU;
-        if (per_cu < need)
-            return jd_fail(R->slot ? JD_EINVAL : JD_EHIP, "%s: %d workgroup(s) per CU fit, %d streams on %d CUs need %d", R->slot ? "k_slot" : "k_resident",
-                           per_cu, n_streams, d->n_cus, need);
-    }
-    if (!R->slot && R->Cw * n_streams > d->n_cus * WG_PER_CU) return jd_fail(JD_EINVAL, "jd_res_start: %d streams do not fit the device", n_streams);
-    // (the slot kernel's workgroups answer a mailbox: one that is never dispatched never answers - all of them resident, or none)
-    if (R->slot && n_streams > d->n_cus * SLOT_WG_PER_CU)
+    R->Cw = P.Cw; R->slot = P.slot;
+    rc = res_occupancy(d, R);
+    if (rc) return rc;
+    if (P.verdict == RES_PLAN_CLUSTERS) return jd_fail(JD_EINVAL, "jd_res_start: %d streams do not fit the device", n_streams);
+    if (P.verdict == RES_PLAN_SLOTS)
         return jd_fail(JD_EINVAL, "jd_res_start: %d one-workgroup slots do not fit the device (%d CUs x %d workgroups of k_slot resident at once)",
                        n_streams, d->n_cus, SLOT_WG_PER_CU);
-    memset(R->h_done, 0, (size_t)R->n * sizeof(ResDone));
-    memset(R->h_post, 0, (size_t)R->n * sizeof(ResPost));
-    std::fill(R->seq.begin(), R->seq.end(), 0u);
-    std::fill(R->rid.begin(), R->rid.end(), 0u);
-    {
-        const size_t dev_i = (size_t)std::min(std::max(d->device, 0), JD_MAX_DEVICES - 1);
-        if (d->res_yield_turn >= 0) {
-            // this kernel has just made room for somebody who waits for the device (jd_res_yield): a mutex hands itself to
-            // whoever asks first, which may well be the one who let go - so it asks only once the waiter has had its turn
-            const auto t0 = std::chrono::steady_clock::now();
-            while (g_search_turn[dev_i].load() == d->res_yield_turn && g_search_waiters[dev_i].load() > 0 &&
-                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() < 500.0)
-                std::this_thread::sleep_for(std::chrono::microseconds(100));
-            d->res_yield_turn = -1;
-        }
-        g_search_waiters[dev_i].fetch_add(1);
-        R->search_lock = std::unique_lock<std::mutex>(g_search_mu[dev_i]);
-        g_search_waiters[dev_i].fetch_sub(1);
-        g_search_turn[dev_i].fetch_add(1);
+    res_reset(R);
+    const size_t dev_i = dev_index(d);
+    if (d->res_yield_turn >= 0) {
+        // this kernel has just made room for somebody who waits for the device (jd_res_yield): a mutex hands itself to
+        // whoever asks first, which may well be the one who let go - so it asks only once the waiter has had its turn
+        wait_until([&] { return g_search_turn[dev_i].load() != d->res_yield_turn || g_search_waiters[dev_i].load() <= 0; }, 500.0, 100);
+        d->res_yield_turn = -1;
     }
+    R->search_lock = lock_search(dev_i);
     R->process_lock = new GpuLockGuard(d->device);
-    SearchArgs A;
-    memset(&A, 0, sizeof A);
-    A.C = d->C; A.ctl = d->d_ctl; A.streams = d->d_streams; A.work = nullptr; A.n_work = R->n; A.Cw = R->Cw; A.n_slots = 0;
-    A.ll = d->res_ll ? d->res_ll : R->d_ll; A.ll_stride = (long long)G; A.f0 = 0; A.f_end = 0x7fffffff;
-    A.status = d->d_status; A.dbg = d->d_dbg; A.cells = nullptr; A.resident = nullptr; A.rebalance_at = 0; A.n_prio = 0;   // (dbg: jd_dec_debug_trace)
-    const dim3 rgrid((unsigned)(R->n * R->Cw));
-    // (one workgroup per stream: the XCD-local flavour of the memory operations - a cluster of one sits on one XCD)
-    bool xl = R->Cw == 1;
-    const bool slot = R->slot;
-    if (const char *e = jd_dev_env("JD_RES_XL")) xl = xl && atoi(e) != 0;   // development
-    typedef void (*ResKernel)(SearchArgs, const ResPost *, ResMail *, const unsigned *, ResDone *, int, const unsigned *);
-    const ResKernel rk = d->models ? (ne3 ? (xl ? k_resident<3, true, true> : k_resident<3, false, true>) : (xl ? k_resident<6, true, true> : k_resident<6, false, true>))
-                                   : (ne3 ? (xl ? k_resident<3, true, false> : k_resident<3, false, false>) : (xl ? k_resident<6, true, false> : k_resident<6, false, false>));
-    // HIP maps streams onto a few hardware queues, and whatever is queued BEHIND a kernel that stays waits until it leaves:
-    // the side stream's scoring, the null stream's copies back.  Which queue a stream gets is the runtime's business
-    // (tools/resident_alias_probe.py: one fresh stream in fourteen lands behind the kernel), so the kernel is started, a
-    // small kernel is sent down the side stream and the null stream, and if either has not come back in 150 ms the
-    // resident kernel leaves again and comes back on a NEW search stream - a few times, then it is an error.
-    // Where the slots go.  A grid of at most one workgroup per CU is dealt one per CU, and that is what the pipeline wants: a slot's eight
-    // waves take two of a SIMD's four wave slots and half its registers, the scoring kernel's waves (127 VGPRs, no LDS) take the other half
-    // of the SAME CU - a search that waits for memory beside arithmetic that does not: 256 slots on 256 CUs 18.1 ms per configs[1] batch,
-    // against 21.5 with the slots two per CU on half the chip and the scoring on the other half (jd_slot.h: jd_park_kernel, which is how
-    // such a split is made: JD_SLOT_KEEP_SE = CUs per shader engine the slots get, development), 19.1 with 272 and 21.1 with 304 slots
-    // dealt over all CUs (the CUs that hold two slots have no room for the scoring).
+    const ResLocks locks{R};
+    ResLaunch L;
+    rc = res_launch_init(d, R, P, &L);
+    if (rc) return rc;
     R->st = d->s_search;
-    int park_cus = 0, park_fill = 0;
-    if (slot) {
-        // (whole CUs per shader engine: 32 engines of n_cus / 32 CUs each, every one keeps the same number for the slots)
-        const int per_se = std::max(1, d->n_cus / 32);
-        int keep_se = per_se;
-        if (const char *e2 = jd_dev_env("JD_SLOT_KEEP_SE")) { const int v = atoi(e2); if (v >= 1 && v <= per_se && v * 32 * SLOT_WG_PER_CU >= R->n) keep_se = v; }
-        park_cus = (per_se - keep_se) * 32;
-        park_fill = std::min(R->n, keep_se * 32 * SLOT_WG_PER_CU);     // slots that find room while the others are parked
-        if (park_cus > 0 && !d->h_park) {
-            if (hipHostMalloc((void **)&d->h_park, 64, hipHostMallocMapped) != hipSuccess || hipMalloc(&d->d_park, 64 * sizeof(int)) != hipSuccess) {
-                (void)hipGetLastError();
-                park_cus = 0;
-            }
-        }
-    }
     hipError_t e = hipSuccess;
     bool clear = false;
-    ReadyList none; none.n = 0;
-    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev_side, ev_null;
-    HIPCHK(hipEventCreateWithFlags(&ev_side.e, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_null.e, hipEventDisableTiming));
     for (int attempt = 0; attempt < 8 && !clear; ++attempt) {
-        hipLaunchKernelGGL(jd_res_reset_kernel, dim3((R->n + 63) / 64), dim3(64), 0, R->st, d->d_ctl, R->d_mail, R->d_ready, R->n);
-        __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELEASE);
-        if (slot) {
-            bool parked = false;
-            if (park_cus > 0) {
-                // the CUs of every XCD that the slots are NOT to get: parked until the slots are on theirs
-                d->h_park[0] = d->h_park[1] = d->h_park[2] = d->h_park[3] = d->h_park[4] = 0u;
-                if (hipMemsetAsync(d->d_park, 0, 64 * sizeof(int), d->s_gmm) == hipSuccess) {
-                    hipLaunchKernelGGL(jd_park_kernel, dim3((unsigned)d->n_cus), dim3(64), 0, d->s_gmm, (unsigned *)d->d_park, park_cus / 32, d->h_park);
-                    parked = hipGetLastError() == hipSuccess;
-                }
-                const auto tp = std::chrono::steady_clock::now();
-                while (parked && __atomic_load_n(&d->h_park[0], __ATOMIC_ACQUIRE) + __atomic_load_n(&d->h_park[1], __ATOMIC_ACQUIRE) < (unsigned)d->n_cus &&
-                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count() < 50.0)
-                    std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            unsigned *started = parked ? d->h_park + 4 : nullptr;
-            if (d->models) {
-                if (ne3) hipLaunchKernelGGL((k_slot<3, true>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
-                else hipLaunchKernelGGL((k_slot<6, true>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
-            } else if (ne3) hipLaunchKernelGGL((k_slot<3, false>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
-            else hipLaunchKernelGGL((k_slot<6, false>), rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_ready, R->h_done, R->h_beat, started);
-            if (parked) {                                              // every slot is on its CU (or 100 ms are over): the parked CUs are the scoring's
-                const auto tp = std::chrono::steady_clock::now();
-                while (__atomic_load_n(&d->h_park[4], __ATOMIC_ACQUIRE) < (unsigned)park_fill &&
-                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count() < 100.0)
-                    std::this_thread::sleep_for(std::chrono::microseconds(20));
-                if (getenv("JD_VERBOSE"))
-                    fprintf(stderr, "k_slot: %u CUs parked (%u left free), %u of %d slots on their CUs after %.2f ms\n", d->h_park[0], d->h_park[1], d->h_park[4], R->n,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count());
-                __atomic_store_n(&d->h_park[2], 1u, __ATOMIC_RELEASE);
-            }
-        } else
-        hipLaunchKernelGGL(rk, rgrid, dim3(SNT), 0, R->st, A, R->h_post, R->d_mail, R->d_ready, R->h_done, R->Cw, R->h_beat);
-        e = hipGetLastError();
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(jd_res_ready_kernel, dim3(1), dim3(64), 0, d->s_gmm, R->d_ready, none);
-        (void)hipEventRecord(ev_side.e, d->s_gmm);
-        hipLaunchKernelGGL(jd_res_ready_kernel, dim3(1), dim3(64), 0, (hipStream_t)0, R->d_ready, none);
-        (void)hipEventRecord(ev_null.e, (hipStream_t)0);
-        const auto t0 = std::chrono::steady_clock::now();
-        while (!clear && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() < 150.0) {
-            clear = hipEventQuery(ev_side.e) == hipSuccess && hipEventQuery(ev_null.e) == hipSuccess;
-            if (!clear) std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-        if (clear) break;
-        // behind the kernel: it leaves (the exit word), what waited for it runs, and the search stream is made anew
-        for (int t = 0; t < R->n; ++t) __atomic_store_n(&R->h_post[t].exit_req, 1, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(R->st);
-        (void)hipEventSynchronize(ev_side.e); (void)hipEventSynchronize(ev_null.e);
-        memset(R->h_post, 0, (size_t)R->n * sizeof(ResPost));
-        memset(R->h_done, 0, (size_t)R->n * sizeof(ResDone));
-        hipStream_t fresh = nullptr;
-        {
-            int prio_lo = 0, prio_hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            if (hipStreamCreateWithPriority(&fresh, hipStreamNonBlocking, prio_hi) != hipSuccess) { e = hipErrorUnknown; break; }
-            d->res_old_streams.push_back(d->s_search);                 // (destroyed with the decoder: somebody may still hold it)
-            d->s_search = fresh; R->st = fresh;
-        }
+        e = launch_and_probe(d, R, L, &clear);
+        if (e != hipSuccess || clear) break;
+        if (!fresh_search_stream(d, R)) { e = hipErrorUnknown; break; }
         if (getenv("JD_VERBOSE")) fprintf(stderr, "k_resident: the side stream or the null stream was queued behind it - a new search stream (%d)\n", attempt + 1);
     }
-    if (e != hipSuccess || !clear) {
-        delete R->process_lock; R->process_lock = nullptr; R->search_lock.unlock();
-        if (e != hipSuccess) return jd_fail(JD_EHIP, "k_resident: %s", hipGetErrorString(e));
-        return jd_fail(JD_EHIP, "k_resident: no search stream whose hardware queue the side stream and the null stream do not share");
-    }
+    if (e != hipSuccess) return jd_fail(JD_EHIP, "k_resident: %s", hipGetErrorString(e));
+    if (!clear) return jd_fail(JD_EHIP, "k_resident: no search stream whose hardware queue the side stream and the null stream do not share");
     R->on = true;
     R->t_start = std::chrono::steady_clock::now();
     if (getenv("JD_VERBOSE")) fprintf(stderr, "%s: %d streams, clusters of %d workgroups, %d rows per buffer%s\n", R->slot ? "k_slot" : "k_resident", R->n, R->Cw, R->rows,
-                                      park_cus > 0 ? " (the other CUs parked while its grid was dealt)" : "");
+                                      L.park_cus > 0 ? " (the other CUs parked while its grid was dealt)" : "");
     return JD_OK;
 }
 
@@ -336,13 +421,13 @@ int jd_res_cluster(const jd_dec *d) { return (d && d->res) ? d->res->Cw : 0; }
 int jd_res_yield(jd_dec *d)
 {
     if (!d || !d->res || !d->res->on) return JD_OK;
-    d->res_yield_turn = g_search_turn[(size_t)std::min(std::max(d->device, 0), JD_MAX_DEVICES - 1)].load();
+    d->res_yield_turn = g_search_turn[dev_index(d)].load();
     return jd_res_stop(d);
 }
 // somebody else of this process waits for the device's search lock (another decoder's launch, another broker's kernel)
 int jd_res_should_yield(const jd_dec *d)
 {
-    return (d && d->res && d->res->on) ? g_search_waiters[(size_t)std::min(std::max(d->device, 0), JD_MAX_DEVICES - 1)].load() > 0 : 0;
+    return (d && d->res && d->res->on) ? g_search_waiters[dev_index(d)].load() > 0 : 0;
 }
 long long jd_res_run_us(const jd_dec *d) { return (d && d->res) ? d->res->run_ticks / 100 : 0; }
 long long jd_res_collections(const jd_dec *d) { return (d && d->res) ? d->res->n_collect : 0; }
@@ -354,7 +439,7 @@ static int res_bump(jd_dec *d, int n, const int *streams)
     for (int i0 = 0; i0 < n; i0 += 64) {
         ReadyList L;
         L.n = std::min(64, n - i0);
-        for (int i = 0; i < L.n; ++i) { const int s = streams[i0 + i]; R->rid[(size_t)s] += 1; L.s[i] = s; L.id[i] = R->rid[(size_t)s]; }
+        for (int i = 0; i < L.n; ++i) { const int s = streams[i0 + i]; L.s[i] = s; L.id[i] = ++R->stream[s].rid; }
         hipLaunchKernelGGL(jd_res_ready_kernel, dim3(1), dim3(64), 0, d->s_gmm, R->d_ready, L);
         HIPCHK(hipGetLastError());
     }
@@ -378,7 +463,7 @@ int jd_res_init(jd_dec *d, int s)
     hipLaunchKernelGGL(jd_mark_init_kernel, dim3(1), dim3(64), 0, d->s_gmm, d->d_ctl, s, 1);
     HIPCHK(hipGetLastError());
     d->stream_T[(size_t)s] = 0; d->stream_started[(size_t)s] = 1; d->stream_open[(size_t)s] = 0;
-    R->T_posted[(size_t)s] = 0; R->T_done[(size_t)s] = 0; R->err_done[(size_t)s] = 0;
+    R->stream[s].T_posted = 0; R->stream[s].T_done = 0; R->stream[s].err_done = 0;
     return res_bump(d, 1, &s);
 }
 
@@ -417,16 +502,22 @@ int jd_res_stage_many(jd_dec *d, int n, const int *streams, const int *bufs, con
     return res_bump(d, ns, who.data());
 }
 
-// the command itself: a word in host-mapped memory (the cluster's first workgroup polls it)
-static void res_write_post(Resident *R, int s, int T, int slot, int init = 0)
+// The command "frames up to T, likelihood rows from `slot`" for stream s: the host's record of it, and the command itself - a word
+// in host-mapped memory (the cluster's first workgroup polls it), behind the ready number the stream has now.
+// init: the command begins an utterance.
+static void res_command(Resident *R, int s, int T, int slot, bool init)
 {
+    ResStream &S = R->stream[s];
+    S.seq += 1;
+    S.busy = true;
+    S.T_posted = T; S.slot_posted = slot;
+    if (init) S.init_pending = true;
     __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);               // (a sign of life: k_resident's `beat`)
     ResPost &P = R->h_post[s];
     P.T = T;
-    P.init = init;
-    if (init) R->init_pending[(size_t)s] = 1;
-    P.ready_id = R->rid[(size_t)s];
-    __atomic_store_n(&P.word, ((unsigned long long)R->seq[(size_t)s] << 32) | (unsigned)slot, __ATOMIC_RELEASE);
+    P.init = init ? 1 : 0;
+    P.ready_id = S.rid;
+    __atomic_store_n(&P.word, ((unsigned long long)S.seq << 32) | (unsigned)slot, __ATOMIC_RELEASE);
 }
 
 // The command "frames up to T + n_frames are scored in buffer buf" for stream s (idle), behind what has been staged
@@ -434,12 +525,9 @@ int jd_res_post(jd_dec *d, int s, int buf, int n_frames)
 {
     Resident *R = d->res;
     if (!R || !R->on || s < 0 || s >= R->n) return jd_fail(JD_ESTATE, "jd_res_post: no resident kernel for stream %d", s);
-    const int T0 = R->T_done[(size_t)s], T1 = T0 + n_frames;
+    const int T0 = R->stream[s].T_done;
     const long long slot = ((long long)s * 2 + buf) * R->rows - T0;    // (k_search reads row  slot + f: see jd_streams_push)
-    R->seq[(size_t)s] += 1;
-    R->busy[(size_t)s] = 1;
-    R->T_posted[(size_t)s] = T1; R->slot_posted[(size_t)s] = (int)slot;
-    res_write_post(R, s, T1, (int)slot);
+    res_command(R, s, T0 + n_frames, (int)slot, false);
     return JD_OK;
 }
 
@@ -451,10 +539,11 @@ int jd_res_poll(jd_dec *d, int s, int *idle, int *frame, int *error, int *stoppe
     if (!R || !R->on || s < 0 || s >= R->n) return jd_fail(JD_ESTATE, "jd_res_poll: no resident kernel for stream %d", s);
     __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);               // (a sign of life: k_resident's `beat`)
     const bool through = res_harvest(d, s);
+    const ResStream &S = R->stream[s];
     *idle = through ? 1 : 0;
-    if (frame) *frame = R->T_done[(size_t)s];
-    if (error) *error = R->err_done[(size_t)s];
-    if (stopped) *stopped = (through && R->err_done[(size_t)s] == 0 && R->T_done[(size_t)s] < R->T_posted[(size_t)s]) ? 1 : 0;
+    if (frame) *frame = S.T_done;
+    if (error) *error = S.err_done;
+    if (stopped) *stopped = (through && S.err_done == 0 && S.T_done < S.T_posted) ? 1 : 0;
     if (through) return JD_OK;
     if (__atomic_load_n(&R->h_done[s].left, __ATOMIC_ACQUIRE))
         return jd_fail(JD_ESTATE, "the resident search kernel has ended (no command for 5 s, or a lost workgroup)");
@@ -474,13 +563,13 @@ int jd_res_collect(jd_dec *d, int s)
     if (!R || !R->on || s < 0 || s >= R->n) return jd_fail(JD_ESTATE, "jd_res_collect: no resident kernel for stream %d", s);
     launch_gc(d->C, d->d_ctl, d->d_streams, nullptr, 1, s, d->am->max_n <= 5, std::max(8, d->n_cus / 6), d->s_gmm);
     HIPCHK(hipGetLastError());
-    R->seq[(size_t)s] += 1;
-    R->busy[(size_t)s] = 1;
     R->n_collect += 1;
     if (d->pipe_on) d->pipe_collections += 1;
-    const int rc = res_bump(d, 1, &s);                                 // (the command waits for the collection)
+    // (the command waits for the collection: the ready number first - the word carries the one the stream has THEN)
+    const int rc = res_bump(d, 1, &s);
     if (rc) return rc;
-    res_write_post(R, s, R->T_posted[(size_t)s], R->slot_posted[(size_t)s], R->init_pending[(size_t)s]);
+    const ResStream &S = R->stream[s];
+    res_command(R, s, S.T_posted, S.slot_posted, S.init_pending);     // (an utterance's first command says again that it is)
     return JD_OK;
 }
 
@@ -583,75 +672,79 @@ static void pipe_drain(jd_dec *d)
     }
 }
 
-// slots whose utterance is through -> their results exported, the slots free; free slots -> the next queued utterances
-static int pipe_pump(jd_dec *d)
+// the results of the slots in EL to their virtual result slots (jd_finish_export_kernel, on the side stream); EL is empty afterwards
+static int pipe_export(jd_dec *d, ExportList *EL)
+{
+    Pipe *P = d->pipe;
+    if (EL->n == 0) return JD_OK;
+    hipLaunchKernelGGL(jd_finish_export_kernel, dim3((unsigned)EL->n), dim3(64), 0, d->s_gmm, d->d_ctl, d->d_streams, *EL, P->d_vctl, P->d_vresn,
+                       P->d_vres, d->res_cap, d->models ? P->d_vres_model : nullptr);
+    HIPCHK(hipGetLastError());
+    EL->n = 0;
+    return JD_OK;
+}
+
+// The pump, step 1: the reports that are in.  A slot that stopped for a Path collection collects and goes on, one in the middle
+// of its utterance gets its next frames, one whose utterance is through has its result exported and is free.
+static int pump_harvest(jd_dec *d)
 {
     Pipe *P = d->pipe;
     Resident *R = d->res;
     ExportList EL; EL.n = 0;
-    auto flush_exports = [&]() -> int {
-        if (EL.n == 0) return JD_OK;
-        hipLaunchKernelGGL(jd_finish_export_kernel, dim3((unsigned)EL.n), dim3(64), 0, d->s_gmm, d->d_ctl, d->d_streams, EL, P->d_vctl, P->d_vresn,
-                           P->d_vres, d->res_cap, d->models ? P->d_vres_model : nullptr);
-        HIPCHK(hipGetLastError());
-        EL.n = 0;
-        return JD_OK;
-    };
-    if (R->h_beat) __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);   // (a sign of life: k_resident's `beat`)
-    if (R->on) {
-        // the kernel has gone by itself: nobody gave it a command for 5 s (a caller that was away between two calls) - seen
-        // BEFORE anything is posted to it: the reports are all in, and it comes back like behind jd_dec_quiesce
-        bool left = false;
-        for (int s = 0; s < P->n_slots && !left; ++s) left = __atomic_load_n(&R->h_done[s].left, __ATOMIC_ACQUIRE) != 0;
-        if (left) { const int rc = jd_res_stop(d); if (rc) return rc; }
-    }
-    if (!R->on) {                                                      // (after jd_dec_quiesce: the kernel comes back, the slots go on where they were)
-        const int rc = jd_res_start(d, P->n_slots, GMM_ROWS2);
-        if (rc) return rc;
-    }
     for (int s = 0; s < P->n_slots; ++s) {
         if (P->slot_batch_id[(size_t)s] < 0) continue;
-        if (R->busy[(size_t)s] && !res_harvest(d, s)) continue;
-        const int er = R->err_done[(size_t)s], fr = R->T_done[(size_t)s];
+        if (!res_harvest(d, s)) continue;
+        const ResStream &S = R->stream[s];
+        const int er = S.err_done, fr = S.T_done;
         PipeBatch &B = P->q[(size_t)(P->slot_batch_id[(size_t)s] - P->serial0)];
         const int ui = P->slot_utt[(size_t)s];
         const PipeUtt &U = B.u[(size_t)ui];
-        if (er == 0 && fr < R->T_posted[(size_t)s]) {                  // stopped for a Path collection: collect, go on
+        if (er == 0 && fr < S.T_posted) {                              // stopped for a Path collection: collect, go on
             const int rc = jd_res_collect(d, s);
             if (rc) return rc;
             continue;
         }
         if (er == 0 && fr < U.T) {                                     // its next frames
-            R->seq[(size_t)s] += 1; R->busy[(size_t)s] = 1;
-            R->T_posted[(size_t)s] = std::min(U.T, fr + P->chunk);
-            res_write_post(R, s, R->T_posted[(size_t)s], (int)U.row0, 0);
+            res_command(R, s, std::min(U.T, fr + P->chunk), (int)U.row0, false);
             continue;
         }
         EL.slot[EL.n] = s; EL.vslot[EL.n] = B.table * P->max_batch + ui; EL.n += 1;
-        if (EL.n == 64) { const int rc = flush_exports(); if (rc) return rc; }
+        if (EL.n == 64) { const int rc = pipe_export(d, &EL); if (rc) return rc; }
         B.u[(size_t)ui].state = 2; B.n_done += 1; P->frames_done += fr; d->pipe_utts_through += 1;
         if (er) P->slot_dirty[(size_t)s] = 1;                          // (its arenas may be inconsistent: out of the game until the pipeline stops)
         P->slot_batch_id[(size_t)s] = -1;
     }
-    int rc = flush_exports();
-    if (rc) return rc;
-    // scoring, a piece at a time: a batch's table in ONE launch holds the side stream for ~20 ms, and the exports and ready
-    // numbers of every slot that finishes meanwhile queue up behind it (measured: slots 12 % idle); the next piece goes out when
-    // the one before it is through, so that those wait for a piece at most
+    return pipe_export(d, &EL);
+}
+
+// The pump, step 2: scoring, a piece at a time: a batch's table in ONE launch holds the side stream for ~20 ms, and the exports and
+// ready numbers of every slot that finishes meanwhile queue up behind it (measured: slots 12 % idle); the next piece goes out when
+// the one before it is through, so that those wait for a piece at most
+static int pump_score(jd_dec *d)
+{
+    Pipe *P = d->pipe;
     if (P->piece_out && hipEventQuery(P->ev_piece) == hipSuccess) P->piece_out = false;
-    if (!P->piece_out)
-        for (PipeBatch &B : P->q) {
-            if (B.rows_scored >= B.rows) continue;
-            const size_t n = std::min(P->piece_rows, B.rows - B.rows_scored);
-            const size_t base = (size_t)B.table * P->table_rows + B.rows_scored;
-            rc = launch_gmm(d->am, d->amb, B.feats + ((size_t)B.offs[0] + B.rows_scored) * (size_t)d->am->D, P->d_ident, (int)n,
-                            P->d_ll + base * (size_t)d->am->n_gmm, d->s_gmm);
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(P->ev_piece, d->s_gmm));
-            B.rows_scored += n; P->piece_out = true; d->pipe_rows_scored += (long long)n;
-            break;
-        }
-    // refill (from batches whose scoring is enqueued to the last row: a slot's ready number is counted up behind it)
+    if (P->piece_out) return JD_OK;
+    for (PipeBatch &B : P->q) {
+        if (B.rows_scored >= B.rows) continue;
+        const size_t n = std::min(P->piece_rows, B.rows - B.rows_scored);
+        const size_t base = (size_t)B.table * P->table_rows + B.rows_scored;
+        const int rc = launch_gmm(d->am, d->amb, B.feats + ((size_t)B.offs[0] + B.rows_scored) * (size_t)d->am->D, P->d_ident, (int)n,
+                                  P->d_ll + base * (size_t)d->am->n_gmm, d->s_gmm);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(P->ev_piece, d->s_gmm));
+        B.rows_scored += n; P->piece_out = true; d->pipe_rows_scored += (long long)n;
+        break;
+    }
+    return JD_OK;
+}
+
+// The pump, step 3: free slots take the next queued utterances (from batches whose scoring is enqueued to the last row: a slot's
+// ready number is counted up behind it)
+static int pump_refill(jd_dec *d)
+{
+    Pipe *P = d->pipe;
+    Resident *R = d->res;
     std::vector<int> who;
     std::vector<std::pair<int, int>> what;                             // (batch index in q, utterance)
     size_t bi = 0;
@@ -666,17 +759,34 @@ static int pipe_pump(jd_dec *d)
         who.push_back(s); what.push_back(std::make_pair((int)bi, ui));
     }
     if (who.empty()) return JD_OK;
-    rc = res_bump(d, (int)who.size(), who.data());                    // (behind the exports and every scoring launch enqueued so far)
+    const int rc = res_bump(d, (int)who.size(), who.data());           // (behind the exports and every scoring launch enqueued so far)
     if (rc) return rc;
     for (size_t k = 0; k < who.size(); ++k) {
         const int s = who[k];
         const PipeUtt &U = P->q[(size_t)what[k].first].u[(size_t)what[k].second];
-        R->seq[(size_t)s] += 1; R->busy[(size_t)s] = 1;
-        R->T_done[(size_t)s] = 0; R->err_done[(size_t)s] = 0;
-        R->T_posted[(size_t)s] = std::min(U.T, P->chunk); R->slot_posted[(size_t)s] = (int)U.row0;
-        res_write_post(R, s, R->T_posted[(size_t)s], (int)U.row0, 1);
+        R->stream[s].T_done = 0; R->stream[s].err_done = 0;
+        res_command(R, s, std::min(U.T, P->chunk), (int)U.row0, true);
     }
     return JD_OK;
+}
+
+// slots whose utterance is through -> their results exported, the slots free; free slots -> the next queued utterances
+static int pipe_pump(jd_dec *d)
+{
+    Pipe *P = d->pipe;
+    Resident *R = d->res;
+    if (R->h_beat) __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);   // (a sign of life: k_resident's `beat`)
+    // the kernel has gone by itself: nobody gave it a command for 5 s (a caller that was away between two calls) - seen
+    // BEFORE anything is posted to it: the reports are all in, and it comes back like behind jd_dec_quiesce
+    if (R->on && res_any_left(R, P->n_slots)) { const int rc = jd_res_stop(d); if (rc) return rc; }
+    if (!R->on) {                                                      // (after jd_dec_quiesce: the kernel comes back, the slots go on where they were)
+        const int rc = jd_res_start(d, P->n_slots, GMM_ROWS2);
+        if (rc) return rc;
+    }
+    int rc = pump_harvest(d);
+    if (!rc) rc = pump_score(d);
+    if (!rc) rc = pump_refill(d);
+    return rc;
 }
 
 // The decoder's work on the device comes to rest: a search kernel of its own that stays on the device (the batch pipeline)
@@ -729,6 +839,174 @@ extern "C" int jd_dec_set_pipeline(jd_dec *d, int32_t mode, int32_t depth, int32
     return JD_OK;
 }
 
+extern "C" int jd_dec_pipeline_stats(const jd_dec *d, jd_pipe_stats *out)
+{
+    if (!d || !out) return jd_fail(JD_EINVAL, "jd_dec_pipeline_stats: null");
+    memset(out, 0, sizeof *out);
+    out->mode = d->pipe_mode ? JD_FLOW_RESIDENT : (d->pipeline ? JD_FLOW_TWO_IN_FLIGHT : JD_FLOW_SERIAL);
+    out->depth = d->pipe_mode ? d->pipe_depth : 0;
+    out->slots = d->pipe_mode ? (d->pipe ? d->pipe->n_slots : (d->pipe_slots > 0 ? d->pipe_slots : d->max_streams)) : 0;
+    out->resident = (d->pipe_on && d->res && d->res->on) ? 1 : 0;
+    out->batches_announced = d->pipe ? (int32_t)d->pipe->q.size() : 0;
+    out->frames_searched = d->pipe_frames_searched; out->utts_through = d->pipe_utts_through; out->rows_scored = d->pipe_rows_scored;
+    out->batches_back = d->pipe_batches_back; out->collections = d->pipe_collections;
+    out->slot_busy_us = (double)d->pipe_busy_ticks / 100.0;
+    out->on_us = d->pipe_on_us;
+    if (out->resident) out->on_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - d->res->t_start).count();
+    return JD_OK;
+}
+
+static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
+{
+    const int G = d->am->n_gmm;
+    // (tables and result slots for batches up to twice this one: a larger one later starts the pipeline again, with larger ones)
+    P->K = d->pipe_depth; P->max_batch = 2 * n_utts;
+    P->n_slots = (d->pipe_slots > 0 && d->pipe_slots <= d->max_streams) ? d->pipe_slots : d->max_streams;
+    if (const char *e = jd_dev_env("JD_PIPE_CHUNK")) { const int v = atoi(e); if (v >= 16) P->chunk = v; }   // development
+    if (const char *e = jd_dev_env("JD_PIPE_PIECE")) { const int v = atoi(e); if (v >= 128) P->piece_rows = (size_t)v / GMM_ROWS2 * GMM_ROWS2; }
+    if (hipEventCreateWithFlags(&P->ev_piece, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
+    P->table_rows = ((2 * rows + 1024) + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
+    const size_t V = (size_t)P->K * P->max_batch;
+    if (hipMalloc(&P->d_ll, (size_t)P->K * P->table_rows * G * sizeof(float)) != hipSuccess ||
+        hipMalloc(&P->d_ident, P->table_rows * sizeof(int)) != hipSuccess ||
+        hipMalloc(&P->d_vctl, V * sizeof(StreamCtl)) != hipSuccess || hipMalloc(&P->d_vresn, V * sizeof(int)) != hipSuccess ||
+        hipMalloc(&P->d_vres, V * 5 * (size_t)d->res_cap * sizeof(int)) != hipSuccess ||
+        (d->models && hipMalloc(&P->d_vres_model, V * (size_t)d->res_cap * sizeof(int)) != hipSuccess)) {
+        (void)hipGetLastError();
+        return jd_fail(JD_ENOMEM, "jd_dec_prefetch_scores: no memory for %d likelihood tables of %zu rows", d->pipe_depth, rows);
+    }
+    std::vector<int> ident(P->table_rows);
+    for (size_t r = 0; r < P->table_rows; ++r) ident[r] = (int)r;
+    HIPCHK(hipMemcpy(P->d_ident, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
+    P->table_used.assign((size_t)P->K, 0);
+    P->slot_batch_id.assign((size_t)P->n_slots, -1); P->slot_utt.assign((size_t)P->n_slots, -1); P->slot_dirty.assign((size_t)P->n_slots, 0);
+    return JD_OK;
+}
+
+// d->pipe for batches like this one (n_utts utterances, `rows` frames): the whole of it, or none (and the code)
+static int pipe_alloc(jd_dec *d, int n_utts, size_t rows)
+{
+    d->pipe = new Pipe();
+    const int rc = pipe_fill(d, d->pipe, n_utts, rows);
+    if (rc) pipe_free(d);
+    return rc;
+}
+
+// jd_dec_prefetch_scores in pipe mode: 1 = taken, 0 = not this way (the caller goes on with the usual announcement)
+static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int64_t *offs, int *taken)
+{
+    *taken = 0;
+    if (!d->pipe_mode || d->net->lazy_dev || d->partial_interval > 0 || d->am->hybrid || n_utts < 1) return JD_OK;
+    const size_t rows = (size_t)(offs[n_utts] - offs[0]);
+    if (d->pipe && (n_utts > d->pipe->max_batch || rows > d->pipe->table_rows)) {   // a larger batch than the tables were made for: not this way
+        pipe_drain(d);
+        pipe_free(d);
+    }
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    if (!d->pipe) {
+        rc = ensure_arenas(d);
+        if (rc) return rc;
+        if (d->res && d->res->on) return JD_OK;                        // (a broker owns the resident kernel)
+        rc = pipe_alloc(d, n_utts, rows);
+        if (rc) return rc;
+    }
+    Pipe *P = d->pipe;
+    if ((int)P->q.size() >= P->K)
+        return jd_fail(JD_ESTATE, "jd_dec_prefetch_scores: %d batches are announced and not decoded - the pipeline is %d deep (JD_PIPE_DEPTH)",
+                       (int)P->q.size(), P->K);
+    if (!P->on) {
+        pf_discard(d);                                                 // (what the other way of working ahead holds)
+        for (int s = 0; s < P->n_slots; ++s)
+            if (d->stream_dirty[(size_t)s]) { rc = wipe_stream(d, s); if (rc) return rc; }
+        d->res_ll = P->d_ll;
+        rc = jd_res_start(d, P->n_slots, GMM_ROWS2);
+        if (rc) { d->res_ll = nullptr; return rc; }
+        P->on = true; d->pipe_on = true;
+        P->serial0 = 0; P->t_on = std::chrono::steady_clock::now(); P->frames_done = 0; d->res->run_ticks = 0;
+    }
+    PipeBatch B;
+    B.feats = d_feats; B.n = n_utts; B.offs.assign(offs, offs + n_utts + 1);
+    int t = 0;
+    while (t < P->K && P->table_used[(size_t)t]) ++t;
+    B.table = t; P->table_used[(size_t)t] = 1;
+    B.u.resize((size_t)n_utts);
+    const long long base = (long long)t * (long long)P->table_rows;
+    for (int u = 0; u < n_utts; ++u) { B.u[(size_t)u].T = (int)(offs[u + 1] - offs[u]); B.u[(size_t)u].row0 = base + (offs[u] - offs[0]); }
+    B.order.resize((size_t)n_utts);
+    std::iota(B.order.begin(), B.order.end(), 0);
+    std::stable_sort(B.order.begin(), B.order.end(), [&](int a, int b) { return B.u[(size_t)a].T > B.u[(size_t)b].T; });
+    B.rows = rows; B.rows_scored = 0;                                  // (scored by the pump, a piece at a time, on the CUs the slots leave)
+    P->q.push_back(std::move(B));
+    *taken = 1;
+    return pipe_pump(d);
+}
+
+// jd_decode_batch_device in pipe mode: 1 = handled (the oldest announced batch, handed back), 0 = not this way
+static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_t *offs, jd_hyp *out, int *handled)
+{
+    *handled = 0;
+    Pipe *P = d->pipe;
+    if (!P || !P->on || P->q.empty()) return JD_OK;
+    {
+        const PipeBatch &F = P->q.front();
+        bool same = F.feats == d_feats && F.n == n_utts;
+        for (int u = 0; same && u <= n_utts; ++u) same = F.offs[(size_t)u] == offs[u];
+        if (!same) { pipe_drain(d); return JD_OK; }                    // not the announced one: as if nothing had been announced
+    }
+    const auto w0 = std::chrono::steady_clock::now();
+    int restarts = 0;
+    long long seen_frames = -1;
+    auto t_progress = w0;
+    for (;;) {
+        const int rc = pipe_pump(d);
+        if (rc) { pipe_drain(d); return rc; }
+        if (P->q.front().n_done == P->q.front().n) break;
+        {   // (no utterance through for 30 s: something is stuck - better an error, and the other paths, than a caller that waits for ever)
+            const auto now = std::chrono::steady_clock::now();
+            if (P->frames_done != seen_frames) { seen_frames = P->frames_done; t_progress = now; }
+            else if (std::chrono::duration<double>(now - t_progress).count() > 30.0) {
+                pipe_drain(d);
+                return jd_fail(JD_EHIP, "the batch pipeline has not finished an utterance for 30 s");
+            }
+        }
+        if (d->res->on && res_any_left(d->res, P->n_slots)) {
+            // the kernel has gone by itself: nobody gave it a command for 5 s (a caller that was away between two calls) - the
+            // reports are taken and it comes back like behind jd_dec_quiesce; a command that was never answered is a lost workgroup
+            const int rs = jd_res_stop(d);
+            if (rs || ++restarts > 3) {
+                pipe_drain(d);
+                return rs ? rs : jd_fail(JD_EHIP, "the resident search kernel keeps ending under a batch");
+            }
+            continue;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    HIPCHK(hipStreamSynchronize(d->s_gmm));                            // (the exports)
+    PipeBatch &F = P->q.front();
+    std::vector<int> slot_of((size_t)n_utts);
+    for (int u = 0; u < n_utts; ++u) slot_of[(size_t)u] = F.u[(size_t)u].slot;
+    if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);
+    d->timing = jd_timing();
+    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), F.table * P->max_batch, n_utts, out, 0, nullptr,
+                                      P->d_vres_model);
+    for (int u = 0; u < n_utts; ++u) d->timing.search_frames += F.u[(size_t)u].T;
+    d->timing.gmm_frames = d->timing.search_frames; d->timing.gmm_states = d->am->n_gmm;
+    d->timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    d->timing.search_ms = d->timing.total_ms; d->timing.search_launches = 0; d->timing.cluster_wgs = 1; d->timing.prefetched = 1;
+    d->load_sum = d->load_frames = 0.0;
+    P->table_used[(size_t)F.table] = 0;
+    P->q.pop_front();
+    d->pipe_batches_back += 1;
+    P->serial0 += 1;
+    if (P->q.empty()) pipe_drain(d);                                   // nothing announced behind it: the kernel leaves the device
+    *handled = 1;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Setters that drop what the pipeline holds (they are here for pipe_drain / pipe_free; nothing else of them is about the
+// resident kernel): the output level and its results, the way the likelihood tables are scored.
 // What a decode returns (include/juicer_amd.h): words, or words and the model-level chain.  The search kernels come in a flavour
 // for each (MDL): the resident pipeline's kernel leaves, and whatever is announced under the old setting is dropped.
 extern "C" int jd_dec_set_output_level(jd_dec *d, int32_t level)
@@ -803,159 +1081,3 @@ extern "C" int jd_dec_set_scoring(jd_dec *d, int32_t mode)
     d->amb.fast = mode == JD_SCORE_FAST ? 1 : 0;
     return JD_OK;
 }
-
-extern "C" int jd_dec_pipeline_stats(const jd_dec *d, jd_pipe_stats *out)
-{
-    if (!d || !out) return jd_fail(JD_EINVAL, "jd_dec_pipeline_stats: null");
-    memset(out, 0, sizeof *out);
-    out->mode = d->pipe_mode ? JD_FLOW_RESIDENT : (d->pipeline ? JD_FLOW_TWO_IN_FLIGHT : JD_FLOW_SERIAL);
-    out->depth = d->pipe_mode ? d->pipe_depth : 0;
-    out->slots = d->pipe_mode ? (d->pipe ? d->pipe->n_slots : (d->pipe_slots > 0 ? d->pipe_slots : d->max_streams)) : 0;
-    out->resident = (d->pipe_on && d->res && d->res->on) ? 1 : 0;
-    out->batches_announced = d->pipe ? (int32_t)d->pipe->q.size() : 0;
-    out->frames_searched = d->pipe_frames_searched; out->utts_through = d->pipe_utts_through; out->rows_scored = d->pipe_rows_scored;
-    out->batches_back = d->pipe_batches_back; out->collections = d->pipe_collections;
-    out->slot_busy_us = (double)d->pipe_busy_ticks / 100.0;
-    out->on_us = d->pipe_on_us;
-    if (out->resident) out->on_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - d->res->t_start).count();
-    return JD_OK;
-}
-
-// jd_dec_prefetch_scores in pipe mode: 1 = taken, 0 = not this way (the caller goes on with the usual announcement)
-static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int64_t *offs, int *taken)
-{
-    *taken = 0;
-    if (!d->pipe_mode || d->net->lazy_dev || d->partial_interval > 0 || d->am->hybrid || n_utts < 1) return JD_OK;
-    const int G = d->am->n_gmm;
-    const size_t rows = (size_t)(offs[n_utts] - offs[0]);
-    Pipe *P = d->pipe;
-    if (P && (n_utts > P->max_batch || rows > P->table_rows)) {        // a larger batch than the tables were made for: not this way
-        pipe_drain(d);
-        pipe_free(d);
-        P = nullptr;
-    }
-    int rc = check_device(d->device);
-    if (rc) return rc;
-    if (!P) {
-        rc = ensure_arenas(d);
-        if (rc) return rc;
-        if (d->res && d->res->on) return JD_OK;                        // (a broker owns the resident kernel)
-        P = new Pipe();
-        d->pipe = P;
-        // (tables and result slots for batches up to twice this one: a larger one later starts the pipeline again, with larger ones)
-        P->K = d->pipe_depth; P->max_batch = 2 * n_utts;
-        P->n_slots = (d->pipe_slots > 0 && d->pipe_slots <= d->max_streams) ? d->pipe_slots : d->max_streams;
-        if (const char *e = jd_dev_env("JD_PIPE_CHUNK")) { const int v = atoi(e); if (v >= 16) P->chunk = v; }   // development
-        if (const char *e = jd_dev_env("JD_PIPE_PIECE")) { const int v = atoi(e); if (v >= 128) P->piece_rows = (size_t)v / GMM_ROWS2 * GMM_ROWS2; }
-        if (hipEventCreateWithFlags(&P->ev_piece, hipEventDisableTiming) != hipSuccess) { pipe_free(d); return jd_fail(JD_EHIP, "hipEventCreate failed"); }
-        P->table_rows = ((2 * rows + 1024) + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
-        const size_t V = (size_t)P->K * P->max_batch;
-        if (hipMalloc(&P->d_ll, (size_t)P->K * P->table_rows * G * sizeof(float)) != hipSuccess ||
-            hipMalloc(&P->d_ident, P->table_rows * sizeof(int)) != hipSuccess ||
-            hipMalloc(&P->d_vctl, V * sizeof(StreamCtl)) != hipSuccess || hipMalloc(&P->d_vresn, V * sizeof(int)) != hipSuccess ||
-            hipMalloc(&P->d_vres, V * 5 * (size_t)d->res_cap * sizeof(int)) != hipSuccess ||
-            (d->models && hipMalloc(&P->d_vres_model, V * (size_t)d->res_cap * sizeof(int)) != hipSuccess)) {
-            (void)hipGetLastError();
-            pipe_free(d);
-            return jd_fail(JD_ENOMEM, "jd_dec_prefetch_scores: no memory for %d likelihood tables of %zu rows", d->pipe_depth, rows);
-        }
-        std::vector<int> ident(P->table_rows);
-        for (size_t r = 0; r < P->table_rows; ++r) ident[r] = (int)r;
-        HIPCHK(hipMemcpy(P->d_ident, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
-        P->table_used.assign((size_t)P->K, 0);
-        P->slot_batch_id.assign((size_t)P->n_slots, -1); P->slot_utt.assign((size_t)P->n_slots, -1); P->slot_dirty.assign((size_t)P->n_slots, 0);
-    }
-    if ((int)P->q.size() >= P->K)
-        return jd_fail(JD_ESTATE, "jd_dec_prefetch_scores: %d batches are announced and not decoded - the pipeline is %d deep (JD_PIPE_DEPTH)",
-                       (int)P->q.size(), P->K);
-    if (!P->on) {
-        pf_discard(d);                                                 // (what the other way of working ahead holds)
-        for (int s = 0; s < P->n_slots; ++s)
-            if (d->stream_dirty[(size_t)s]) { rc = wipe_stream(d, s); if (rc) return rc; }
-        d->res_ll = P->d_ll;
-        rc = jd_res_start(d, P->n_slots, GMM_ROWS2);
-        if (rc) { d->res_ll = nullptr; return rc; }
-        P->on = true; d->pipe_on = true;
-        P->serial0 = 0; P->t_on = std::chrono::steady_clock::now(); P->frames_done = 0; d->res->run_ticks = 0;
-    }
-    PipeBatch B;
-    B.feats = d_feats; B.n = n_utts; B.offs.assign(offs, offs + n_utts + 1);
-    int t = 0;
-    while (t < P->K && P->table_used[(size_t)t]) ++t;
-    B.table = t; P->table_used[(size_t)t] = 1;
-    B.u.resize((size_t)n_utts);
-    const long long base = (long long)t * (long long)P->table_rows;
-    for (int u = 0; u < n_utts; ++u) { B.u[(size_t)u].T = (int)(offs[u + 1] - offs[u]); B.u[(size_t)u].row0 = base + (offs[u] - offs[0]); }
-    B.order.resize((size_t)n_utts);
-    std::iota(B.order.begin(), B.order.end(), 0);
-    std::stable_sort(B.order.begin(), B.order.end(), [&](int a, int b) { return B.u[(size_t)a].T > B.u[(size_t)b].T; });
-    B.rows = rows; B.rows_scored = 0;                                  // (scored by the pump, a piece at a time, on the CUs the slots leave)
-    P->q.push_back(std::move(B));
-    *taken = 1;
-    return pipe_pump(d);
-}
-
-// jd_decode_batch_device in pipe mode: 1 = handled (the oldest announced batch, handed back), 0 = not this way
-static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_t *offs, jd_hyp *out, int *handled)
-{
-    *handled = 0;
-    Pipe *P = d->pipe;
-    if (!P || !P->on || P->q.empty()) return JD_OK;
-    {
-        const PipeBatch &F = P->q.front();
-        bool same = F.feats == d_feats && F.n == n_utts;
-        for (int u = 0; same && u <= n_utts; ++u) same = F.offs[(size_t)u] == offs[u];
-        if (!same) { pipe_drain(d); return JD_OK; }                    // not the announced one: as if nothing had been announced
-    }
-    const auto w0 = std::chrono::steady_clock::now();
-    int restarts = 0;
-    long long seen_frames = -1;
-    auto t_progress = w0;
-    for (;;) {
-        const int rc = pipe_pump(d);
-        if (rc) { pipe_drain(d); return rc; }
-        if (P->q.front().n_done == P->q.front().n) break;
-        {   // (no utterance through for 30 s: something is stuck - better an error, and the other paths, than a caller that waits for ever)
-            const auto now = std::chrono::steady_clock::now();
-            if (P->frames_done != seen_frames) { seen_frames = P->frames_done; t_progress = now; }
-            else if (std::chrono::duration<double>(now - t_progress).count() > 30.0) {
-                pipe_drain(d);
-                return jd_fail(JD_EHIP, "the batch pipeline has not finished an utterance for 30 s");
-            }
-        }
-        bool left = false;
-        for (int s = 0; s < P->n_slots && d->res->on && !left; ++s) left = __atomic_load_n(&d->res->h_done[s].left, __ATOMIC_ACQUIRE) != 0;
-        if (left) {
-            // the kernel has gone by itself: nobody gave it a command for 5 s (a caller that was away between two calls) - the
-            // reports are taken and it comes back like behind jd_dec_quiesce; a command that was never answered is a lost workgroup
-            const int rs = jd_res_stop(d);
-            if (rs || ++restarts > 3) {
-                pipe_drain(d);
-                return rs ? rs : jd_fail(JD_EHIP, "the resident search kernel keeps ending under a batch");
-            }
-            continue;
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-    HIPCHK(hipStreamSynchronize(d->s_gmm));                            // (the exports)
-    PipeBatch &F = P->q.front();
-    std::vector<int> slot_of((size_t)n_utts);
-    for (int u = 0; u < n_utts; ++u) slot_of[(size_t)u] = F.u[(size_t)u].slot;
-    if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);
-    d->timing = jd_timing();
-    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), F.table * P->max_batch, n_utts, out, 0, nullptr,
-                                      P->d_vres_model);
-    for (int u = 0; u < n_utts; ++u) d->timing.search_frames += F.u[(size_t)u].T;
-    d->timing.gmm_frames = d->timing.search_frames; d->timing.gmm_states = d->am->n_gmm;
-    d->timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-    d->timing.search_ms = d->timing.total_ms; d->timing.search_launches = 0; d->timing.cluster_wgs = 1; d->timing.prefetched = 1;
-    d->load_sum = d->load_frames = 0.0;
-    P->table_used[(size_t)F.table] = 0;
-    P->q.pop_front();
-    d->pipe_batches_back += 1;
-    P->serial0 += 1;
-    if (P->q.empty()) pipe_drain(d);                                   // nothing announced behind it: the kernel leaves the device
-    *handled = 1;
-    return rc;
-}
-

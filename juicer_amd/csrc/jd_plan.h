@@ -3,6 +3,8 @@
 // the first workgroup of every stream's cluster - uniform clusters, or the weighted plan (clusters sized so that the streams finish
 // together), the batch behind the running one beside it, its XCD-local packing, and when to cut the launch short for a new plan.
 // launch_search (jd_host_launch.h) turns the result into the kernel's work list.
+// At the end, plan_resident: the geometry of the search kernels that stay on the device (jd_host_resident.h: jd_res_start;
+// tests/test_res_plan_cpu.py).
 #pragma once
 
 #include <algorithm>
@@ -272,5 +274,66 @@ static inline PlanOut plan_clusters(const PlanIn &in)
         out.grid = first;
     }
     out.rebalance_at = plan_rebalance_at(in, m, out);
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The geometry of the search kernels that STAY on the device (jd_host_resident.h: jd_res_start): the rows of a likelihood buffer, the
+// streams' clusters, which kernel serves them and where the slots go.  The build's constants come in as fields (no HIP macro here).
+struct ResPlanIn {
+    int n_cus, n_streams, rows_per_buf;
+    int max_cw;                           // largest cluster JD_CW allows
+    long long cap_slots, cap_items;       // ... and the arenas: instance slots and frontier items per stream
+    bool pipeline;                        // the batch pipeline drives the kernel: every stream a slot of ONE workgroup
+    int free_cus, slot, xl, keep_se;      // development knobs (JD_RES_FREE_CUS, JD_RES_SLOT, JD_RES_XL, JD_SLOT_KEEP_SE), -1: unset
+    int sw, wg_per_cu, slot_wg_per_cu, gmm_rows2, res_ring_w;   // the build's SW, WG_PER_CU, SLOT_WG_PER_CU, GMM_ROWS2, RES_RING_W
+};
+
+enum ResPlanVerdict {
+    RES_PLAN_OK = 0,
+    RES_PLAN_LIMITS,                      // more than 1024 streams, or more row tiles than a scoring launch's list holds
+    RES_PLAN_CLUSTERS,                    // the clusters of k_resident do not fit the device
+    RES_PLAN_SLOTS,                       // the slots of k_slot are not all resident at once
+};
+
+struct ResPlanOut {                       // (what follows the point a verdict other than ok was reached stays 0)
+    ResPlanVerdict verdict = RES_PLAN_OK;
+    int rows = 0;                         // rows per likelihood buffer: whole scoring tiles
+    int Cw = 0;                           // workgroups per cluster
+    bool slot = false;                    // one workgroup per stream: the slot kernel (jd_slot.h), SLOT_WG_PER_CU of them per CU
+    bool xl = false;                      // k_resident's XCD-local flavour of the memory operations - a cluster of one sits on one XCD
+    int park_cus = 0, park_fill = 0;      // slots: CUs parked while the grid is dealt, and the slots that find room beside them
+};
+
+static inline ResPlanOut plan_resident(const ResPlanIn &in)
+{
+    ResPlanOut out;
+    const int n = in.n_streams;
+    const int tiles = (in.rows_per_buf + in.gmm_rows2 - 1) / in.gmm_rows2;
+    out.rows = tiles * in.gmm_rows2;
+    if (n > 1024 || 2 * n * tiles > in.res_ring_w) { out.verdict = RES_PLAN_LIMITS; return out; }
+    // clusters: what the arenas allow, and a sixth of the chip left to the scoring, collection and finish kernels
+    const int cw_cap = (int)std::max<long long>(1, std::min<long long>(in.cap_slots / (64 * in.sw), in.cap_items / (512 * in.sw)));
+    // (the scoring of what the streams search: about 1.6 CUs per stream at their pace, and a quarter of the chip at least -
+    // sixteen C++ callers: 407 k frames/s with 24 CUs left, 433 k with 40, 469 k with 64, 462 k with 96)
+    int free_cus = std::min(in.n_cus / 2, std::max(in.n_cus / 4, (n * 8) / 5));
+    if (in.free_cus >= 0 && in.free_cus < in.n_cus) free_cus = in.free_cus;
+    out.Cw = std::max(1, std::min(std::min(in.max_cw, cw_cap), (in.n_cus * in.wg_per_cu - free_cus) / n));
+    if (in.pipeline) out.Cw = 1;                                       // (however few they are)
+    // One workgroup per stream: the slot kernel (jd_slot.h) - compiled for four waves per SIMD, SLOT_WG_PER_CU workgroups per CU,
+    // every per-frame word in LDS.  (JD_RES_SLOT=0, development: k_resident's one-workgroup clusters, one per CU.)
+    out.slot = out.Cw == 1 && in.slot != 0;
+    if (!out.slot && out.Cw * n > in.n_cus * in.wg_per_cu) { out.verdict = RES_PLAN_CLUSTERS; return out; }
+    // (the slot kernel's workgroups answer a mailbox: one that is never dispatched never answers - all of them resident, or none)
+    if (out.slot && n > in.n_cus * in.slot_wg_per_cu) { out.verdict = RES_PLAN_SLOTS; return out; }
+    out.xl = out.Cw == 1 && in.xl != 0;
+    if (out.slot) {
+        // (whole CUs per shader engine: 32 engines of n_cus / 32 CUs each, every one keeps the same number for the slots)
+        const int per_se = std::max(1, in.n_cus / 32);
+        int keep_se = per_se;
+        if (in.keep_se >= 1 && in.keep_se <= per_se && in.keep_se * 32 * in.slot_wg_per_cu >= n) keep_se = in.keep_se;
+        out.park_cus = (per_se - keep_se) * 32;
+        out.park_fill = std::min(n, keep_se * 32 * in.slot_wg_per_cu);
+    }
     return out;
 }
