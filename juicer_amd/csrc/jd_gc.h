@@ -458,35 +458,43 @@ __global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int
 // can take its next utterance before the batch this one belongs to is handed back.  One 64-thread block per utterance.
 // vres_model (model-level output, else null): the records' models, [vslot][res_cap].
 struct ExportList { int n; int slot[64]; int vslot[64]; };
-__global__ void jd_finish_export_kernel(const StreamCtl *ctl, const StreamDev *streams, ExportList L, StreamCtl *vctl, int *vres_n, int *vres,
-                                        int res_cap, int *vres_model)
+// Where the virtual result slots are (the pipeline's; all null where there is none: the broker's kernel, k_resident)
+struct ExportDst { StreamCtl *vctl; int *vres_n, *vres, *vres_model; int res_cap; };
+// The export of ONE utterance - stream s to virtual slot v - by the lanes [0, n_lanes) of a wave or a 64-thread block (lane: this
+// thread's).  The caller has made the stream's state visible to these lanes; what they write is the caller's to publish.
+// (the jd_finish_export_kernel launch, and k_slot for the utterance its slot has just finished: jd_slot.h)
+__device__ __forceinline__ void jd_export_utt(const StreamCtl &c, const StreamDev &S, int v, const ExportDst &E, int lane, int n_lanes)
 {
-    const int i = blockIdx.x;
-    if (i >= L.n) return;
-    const int s = L.slot[i], v = L.vslot[i];
-    const StreamDev &S = streams[s];
-    const StreamCtl &c = ctl[s];
     {   // the control block, word by word
         const int *src = (const int *)&c;
-        int *dst = (int *)&vctl[v];
-        for (int k = threadIdx.x; k < (int)(sizeof(StreamCtl) / sizeof(int)); k += blockDim.x) dst[k] = src[k];
+        int *dst = (int *)&E.vctl[v];
+        for (int k = lane; k < (int)(sizeof(StreamCtl) / sizeof(int)); k += n_lanes) dst[k] = src[k];
     }
-    if (threadIdx.x != 0) return;
+    if (lane != 0) return;
+    const int res_cap = E.res_cap;
     const Tok best = c.best_final;
-    if (!(best.score > LZ) || c.frame == 0) { vres_n[v] = -1; return; }
-    int *lab = vres + (size_t)v * 5 * res_cap, *tim = lab + res_cap;
+    if (!(best.score > LZ) || c.frame == 0) { E.vres_n[v] = -1; return; }
+    int *lab = E.vres + (size_t)v * 5 * res_cap, *tim = lab + res_cap;
     float *sc = (float *)(lab + 2 * (size_t)res_cap), *ac = (float *)(lab + 3 * (size_t)res_cap), *lm = (float *)(lab + 4 * (size_t)res_cap);
     int k = 0;
     for (int p = best.path; p >= 0; p = S.paths[p].prev) {
         if (k < res_cap) {
             const PathRec pr = S.paths[p];
             lab[k] = pr.label; tim[k] = pr.frame; sc[k] = pr.score; ac[k] = pr.ac; lm[k] = pr.lm;
-            if (vres_model) vres_model[(size_t)v * res_cap + k] = pr.model;
+            if (E.vres_model) E.vres_model[(size_t)v * res_cap + k] = pr.model;
             if (k == 0) { sc[0] = best.score; ac[0] = best.ac; lm[0] = best.lm; }     // :293-300
         }
         ++k;
     }
-    vres_n[v] = k;
+    E.vres_n[v] = k;
+}
+__global__ void jd_finish_export_kernel(const StreamCtl *ctl, const StreamDev *streams, ExportList L, StreamCtl *vctl, int *vres_n, int *vres,
+                                        int res_cap, int *vres_model)
+{
+    const int i = blockIdx.x;
+    if (i >= L.n) return;
+    const ExportDst E = { vctl, vres_n, vres, vres_model, res_cap };
+    jd_export_utt(ctl[L.slot[i]], streams[L.slot[i]], L.vslot[i], E, (int)threadIdx.x, (int)blockDim.x);
 }
 
 __global__ void jd_mark_init_kernel(StreamCtl *ctl, int s0, int n)

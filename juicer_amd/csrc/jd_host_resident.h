@@ -21,7 +21,8 @@ struct ResStream {                                     // the protocol as the ho
     unsigned seq;                                      // last sequence number posted
     unsigned rid;                                      // the last ready number enqueued for it (Resident::d_ready: how far the side stream has come)
     int T_posted, T_done, err_done;
-    int slot_posted;
+    int slot_posted, vslot_posted;                     // (vslot_posted: ResPost::vslot of the command, -1 none)
+    bool exported;                                     // the last report says the slot has exported its utterance (ResDone::exported)
     bool busy;                                         // a command is posted and its report not yet taken
     bool init_pending;                                 // ... and it begins an utterance (ResPost::init): a re-post must say so again
     // The kernel starts: the numbers of both sides begin again.  What the host knows of a stream beyond them - where it stands, a
@@ -30,7 +31,7 @@ struct ResStream {                                     // the protocol as the ho
     void reset(const int *T_now)
     {
         seq = rid = 0u;
-        if (T_now) { T_posted = T_done = *T_now; err_done = slot_posted = 0; busy = init_pending = false; }
+        if (T_now) { T_posted = T_done = *T_now; err_done = slot_posted = 0; vslot_posted = -1; exported = busy = init_pending = false; }
     }
 };
 struct Resident {
@@ -57,6 +58,7 @@ struct Resident {
 };
 
 static void res_free(jd_dec *d);
+static ExportDst pipe_export_dst(const jd_dec *d);      // (the pipeline's virtual result slots, below: what k_slot is started with)
 static void res_free_fwd(jd_dec *d) { res_free(d); }
 static void res_free(jd_dec *d)
 {
@@ -108,7 +110,7 @@ static bool res_harvest(jd_dec *d, int s)
         d->pipe_frames_searched += std::max(0, R->h_done[s].frame - S.T_done);
         d->pipe_busy_ticks += R->h_done[s].run_ticks;
     }
-    S.T_done = R->h_done[s].frame; S.err_done = R->h_done[s].error;
+    S.T_done = R->h_done[s].frame; S.err_done = R->h_done[s].error; S.exported = R->h_done[s].exported != 0;
     // (a stream that failed on the device - an arena overflow, a lost workgroup - may hold anything: wiped before its next init,
     // whether or not anybody fetches its result)
     if (S.err_done != 0) d->stream_dirty[(size_t)s] = 1;
@@ -152,7 +154,7 @@ int jd_res_stop(jd_dec *d)
 // The flavours of the kernels that stay on the device (the counterparts of jd_host_launch.h's search_kernel / slot_kernel; they are
 // here and in this order because a template kernel's place in the device code object is where the translation unit first names it,
 // and the object stays as it has been): k_slot (jd_slot.h: HMM size class, word / model-level output) ...
-typedef void (*SlotMailboxKernel)(SearchArgs, const ResPost *, const unsigned *, ResDone *, const unsigned *, unsigned *);
+typedef void (*SlotMailboxKernel)(SearchArgs, const ResPost *, const unsigned *, ResDone *, const unsigned *, unsigned *, ExportDst);
 static SlotMailboxKernel slot_mailbox_kernel(bool ne3, bool mdl)
 {
     static const SlotMailboxKernel tab[4] = { k_slot<3, true>, k_slot<3, false>, k_slot<6, true>, k_slot<6, false> };
@@ -222,6 +224,7 @@ static void res_reset(Resident *R)
 {
     memset(R->h_done, 0, (size_t)R->n * sizeof(ResDone));
     memset(R->h_post, 0, (size_t)R->n * sizeof(ResPost));
+    for (int s = 0; s < R->n; ++s) R->h_post[s].vslot = -1;
     for (ResStream &S : R->stream) S.reset(nullptr);
 }
 
@@ -257,6 +260,7 @@ struct ResLaunch {                                     // what an attempt to sta
     SearchArgs A;
     bool ne3, xl;
     int park_cus, park_fill;                           // (slots) CUs parked while the grid is dealt, and the slots that find room beside them
+    ExportDst E;                                       // (slots) the pipeline's virtual result slots, or nulls
     hipEvent_t ev_side = nullptr, ev_null = nullptr;   // behind the probes on the side stream and the null stream
     ~ResLaunch() { if (ev_side) (void)hipEventDestroy(ev_side); if (ev_null) (void)hipEventDestroy(ev_null); }
 };
@@ -270,6 +274,7 @@ static int res_launch_init(jd_dec *d, const Resident *R, const ResPlanOut &P, Re
     A.status = d->d_status; A.dbg = d->d_dbg; A.cells = nullptr; A.resident = nullptr; A.rebalance_at = 0; A.n_prio = 0;   // (dbg: jd_dec_debug_trace)
     L->ne3 = d->am->max_n <= 5; L->xl = P.xl;
     L->park_cus = P.park_cus; L->park_fill = P.park_fill;
+    L->E = pipe_export_dst(d);
     if (L->park_cus > 0 && !d->h_park) {                               // (jd_park_kernel's words; without them nothing is parked)
         if (hipHostMalloc((void **)&d->h_park, 64, hipHostMallocMapped) != hipSuccess || hipMalloc(&d->d_park, 64 * sizeof(int)) != hipSuccess) {
             (void)hipGetLastError();
@@ -302,7 +307,7 @@ static void park_and_launch_slots(jd_dec *d, Resident *R, const ResLaunch &L)
     }
     unsigned *started = parked ? d->h_park + 4 : nullptr;
     hipLaunchKernelGGL(slot_mailbox_kernel(L.ne3, d->models), dim3((unsigned)R->n), dim3(SNT), 0, R->st, L.A, R->h_post, R->d_ready, R->h_done, R->h_beat,
-                       started);
+                       started, L.E);
     if (!parked) return;
     // every slot is on its CU (or 100 ms are over): the parked CUs are the scoring's
     const auto tp = std::chrono::steady_clock::now();
@@ -504,18 +509,19 @@ int jd_res_stage_many(jd_dec *d, int n, const int *streams, const int *bufs, con
 
 // The command "frames up to T, likelihood rows from `slot`" for stream s: the host's record of it, and the command itself - a word
 // in host-mapped memory (the cluster's first workgroup polls it), behind the ready number the stream has now.
-// init: the command begins an utterance.
-static void res_command(Resident *R, int s, int T, int slot, bool init)
+// init: the command begins an utterance.  vslot (the pipeline's slots): the command ends one - ResPost::vslot.
+static void res_command(Resident *R, int s, int T, int slot, bool init, int vslot = -1)
 {
     ResStream &S = R->stream[s];
     S.seq += 1;
     S.busy = true;
-    S.T_posted = T; S.slot_posted = slot;
+    S.T_posted = T; S.slot_posted = slot; S.vslot_posted = vslot; S.exported = false;
     if (init) S.init_pending = true;
     __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);               // (a sign of life: k_resident's `beat`)
     ResPost &P = R->h_post[s];
     P.T = T;
     P.init = init ? 1 : 0;
+    P.vslot = vslot;
     P.ready_id = S.rid;
     __atomic_store_n(&P.word, ((unsigned long long)S.seq << 32) | (unsigned)slot, __ATOMIC_RELEASE);
 }
@@ -569,7 +575,7 @@ int jd_res_collect(jd_dec *d, int s)
     const int rc = res_bump(d, 1, &s);
     if (rc) return rc;
     const ResStream &S = R->stream[s];
-    res_command(R, s, S.T_posted, S.slot_posted, S.init_pending);     // (an utterance's first command says again that it is)
+    res_command(R, s, S.T_posted, S.slot_posted, S.init_pending, S.vslot_posted);   // (an utterance's first command says again that it is)
     return JD_OK;
 }
 
@@ -603,10 +609,13 @@ int jd_res_finish(jd_dec *d, int s, jd_hyp *out)
 // through and hands them back; it is also what keeps the slots fed (the pump runs inside the calls - no thread).  Results
 // are those of any other path; what changes is that a batch takes as long as its longest utterance on one workgroup.
 struct PipeUtt { int state = 0, slot = -1, T = 0; long long row0 = 0; };      // state: 0 queued, 1 running, 2 through
+#define PIPE_PIECE_ROWS0 6144            // rows per scoring launch where nothing is planned (JD_PIPE_DECOUPLE=0)
 #define PIPE_CHUNK 128                  // frames per command: what a slot runs before it looks at its mailbox again (jd_dec_quiesce waits that long)
 struct PipeBatch {
     const float *feats = nullptr; int n = 0; int table = 0; int next = 0, n_done = 0;
     size_t rows = 0, rows_scored = 0;                  // rows of its table, and how many of them have a scoring launch enqueued
+    int n_kexport = 0;                                 // utterances of it exported by jd_finish_export_kernel (on the side stream)
+    bool scored = false;                               // its table is scored to the last row (Pipe::ev_batch of its table has completed)
     std::vector<int64_t> offs;
     std::vector<PipeUtt> u;
     std::vector<int> order;                            // its utterances by length, longest first: the order in which slots take them
@@ -627,10 +636,23 @@ struct Pipe {
     int chunk = PIPE_CHUNK;
     std::chrono::steady_clock::time_point t_on;        // (statistics)
     long long frames_done = 0;
-    hipEvent_t ev_piece = nullptr;                     // behind the last scoring launch enqueued
-    bool piece_out = false;
-    size_t piece_rows = 6144;                          // rows per scoring launch (JD_PIPE_PIECE)
+    // Scoring launches, a piece at a time (pump_score): up to max_out of them enqueued - one running, one behind it - each with
+    // its event; the oldest is ev_piece[piece_turn].
+    hipEvent_t ev_piece[2] = { nullptr, nullptr };
+    int piece_out = 0, piece_turn = 0, max_out = 2;
+    size_t piece_rows = PIPE_PIECE_ROWS0;              // rows per scoring launch (plan_piece_rows, or JD_PIPE_PIECE)
+    std::vector<hipEvent_t> ev_batch;                  // per table: behind the last piece of the batch that has it
+    std::vector<char> slot_kexport;                    // per slot: its last utterance went out by jd_finish_export_kernel (side stream)
+    // JD_PIPE_DECOUPLE=0 (development) clears it: every export by the kernel on the side stream, a ready number with every
+    // utterance, one piece of PIPE_PIECE_ROWS0 rows in flight
+    bool decouple = true;
 };
+static ExportDst pipe_export_dst(const jd_dec *d)
+{
+    const Pipe *P = d->pipe;
+    if (!P || !d->res_ll) return ExportDst{ nullptr, nullptr, nullptr, nullptr, 0 };
+    return ExportDst{ P->d_vctl, P->d_vresn, P->d_vres, d->models ? P->d_vres_model : nullptr, d->res_cap };
+}
 
 static void pipe_free(jd_dec *d);
 static void pipe_free_fwd(jd_dec *d) { pipe_free(d); }
@@ -644,7 +666,8 @@ static void pipe_free(jd_dec *d)
     if (P->d_vresn) (void)hipFree(P->d_vresn);
     if (P->d_vres) (void)hipFree(P->d_vres);
     if (P->d_vres_model) (void)hipFree(P->d_vres_model);
-    if (P->ev_piece) (void)hipEventDestroy(P->ev_piece);
+    for (hipEvent_t e : P->ev_piece) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : P->ev_batch) if (e) (void)hipEventDestroy(e);
     delete P;
     d->pipe = nullptr;
 }
@@ -661,14 +684,14 @@ static void pipe_drain(jd_dec *d)
                 wall_us / 1e3, 100.0 * (double)(d->res->run_ticks / 100) / (wall_us * P->n_slots), P->frames_done,
                 P->frames_done ? (double)(d->res->run_ticks / 100) / (double)P->frames_done : 0.0);
     }
-    P->on = false; d->pipe_on = false; P->piece_out = false;
+    P->on = false; d->pipe_on = false; P->piece_out = 0;              // (jd_res_stop has synchronised the side stream)
     P->q.clear();
     std::fill(P->table_used.begin(), P->table_used.end(), 0);
     std::fill(P->slot_batch_id.begin(), P->slot_batch_id.end(), -1);
     d->res_ll = nullptr;
     for (int s = 0; s < P->n_slots; ++s) {                             // (streams left in the middle of an utterance, or failed)
         if (P->slot_dirty[(size_t)s]) d->stream_dirty[(size_t)s] = 1;
-        P->slot_dirty[(size_t)s] = 0;
+        P->slot_dirty[(size_t)s] = 0; P->slot_kexport[(size_t)s] = 0;
     }
 }
 
@@ -685,7 +708,8 @@ static int pipe_export(jd_dec *d, ExportList *EL)
 }
 
 // The pump, step 1: the reports that are in.  A slot that stopped for a Path collection collects and goes on, one in the middle
-// of its utterance gets its next frames, one whose utterance is through has its result exported and is free.
+// of its utterance gets its next frames, one whose utterance is through is free: its result is in its virtual result slot already
+// (the report says "exported": k_slot), or goes there by jd_finish_export_kernel - after an error, and wherever the slot did not.
 static int pump_harvest(jd_dec *d)
 {
     Pipe *P = d->pipe;
@@ -704,12 +728,18 @@ static int pump_harvest(jd_dec *d)
             if (rc) return rc;
             continue;
         }
-        if (er == 0 && fr < U.T) {                                     // its next frames
-            res_command(R, s, std::min(U.T, fr + P->chunk), (int)U.row0, false);
+        const int vslot = B.table * P->max_batch + ui;
+        if (er == 0 && fr < U.T) {                                     // its next frames (the command that ends the utterance names its result slot)
+            const int T = std::min(U.T, fr + P->chunk);
+            res_command(R, s, T, (int)U.row0, false, (P->decouple && T == U.T) ? vslot : -1);
             continue;
         }
-        EL.slot[EL.n] = s; EL.vslot[EL.n] = B.table * P->max_batch + ui; EL.n += 1;
-        if (EL.n == 64) { const int rc = pipe_export(d, &EL); if (rc) return rc; }
+        if (!(S.exported && er == 0)) {
+            EL.slot[EL.n] = s; EL.vslot[EL.n] = vslot; EL.n += 1;
+            P->slot_kexport[(size_t)s] = 1;                            // (the slot's next utterance waits for it: pump_refill)
+            B.n_kexport += 1;
+            if (EL.n == 64) { const int rc = pipe_export(d, &EL); if (rc) return rc; }
+        }
         B.u[(size_t)ui].state = 2; B.n_done += 1; P->frames_done += fr; d->pipe_utts_through += 1;
         if (er) P->slot_dirty[(size_t)s] = 1;                          // (its arenas may be inconsistent: out of the game until the pipeline stops)
         P->slot_batch_id[(size_t)s] = -1;
@@ -717,35 +747,39 @@ static int pump_harvest(jd_dec *d)
     return pipe_export(d, &EL);
 }
 
-// The pump, step 2: scoring, a piece at a time: a batch's table in ONE launch holds the side stream for ~20 ms, and the exports and
-// ready numbers of every slot that finishes meanwhile queue up behind it (measured: slots 12 % idle); the next piece goes out when
-// the one before it is through, so that those wait for a piece at most
+// The pump, step 3: scoring, a piece at a time.  A batch's table in ONE launch holds the side stream for ~20 ms, and whatever a
+// slot waits for on that stream - a kernel export, a ready number - queues up behind it.  Up to max_out pieces are enqueued, one
+// running and one behind it, so that the stream has no gap between them; the ready numbers this pump call enqueued (steps 1
+// and 2) are in front of the new piece.  Behind a batch's last piece, the event that tells pump_refill its table is scored.
 static int pump_score(jd_dec *d)
 {
     Pipe *P = d->pipe;
-    if (P->piece_out && hipEventQuery(P->ev_piece) == hipSuccess) P->piece_out = false;
-    if (P->piece_out) return JD_OK;
+    while (P->piece_out > 0 && hipEventQuery(P->ev_piece[P->piece_turn]) == hipSuccess) { P->piece_out -= 1; P->piece_turn ^= 1; }
     for (PipeBatch &B : P->q) {
-        if (B.rows_scored >= B.rows) continue;
-        const size_t n = std::min(P->piece_rows, B.rows - B.rows_scored);
-        const size_t base = (size_t)B.table * P->table_rows + B.rows_scored;
-        const int rc = launch_gmm(d->am, d->amb, B.feats + ((size_t)B.offs[0] + B.rows_scored) * (size_t)d->am->D, P->d_ident, (int)n,
-                                  P->d_ll + base * (size_t)d->am->n_gmm, d->s_gmm);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(P->ev_piece, d->s_gmm));
-        B.rows_scored += n; P->piece_out = true; d->pipe_rows_scored += (long long)n;
-        break;
+        while (B.rows_scored < B.rows && P->piece_out < P->max_out) {
+            const size_t n = std::min(P->piece_rows, B.rows - B.rows_scored);
+            const size_t base = (size_t)B.table * P->table_rows + B.rows_scored;
+            const int rc = launch_gmm(d->am, d->amb, B.feats + ((size_t)B.offs[0] + B.rows_scored) * (size_t)d->am->D, P->d_ident, (int)n,
+                                      P->d_ll + base * (size_t)d->am->n_gmm, d->s_gmm);
+            if (rc) return rc;
+            HIPCHK(hipEventRecord(P->ev_piece[P->piece_turn ^ (P->piece_out & 1)], d->s_gmm));
+            B.rows_scored += n; P->piece_out += 1; d->pipe_rows_scored += (long long)n;
+            if (B.rows_scored >= B.rows) HIPCHK(hipEventRecord(P->ev_batch[(size_t)B.table], d->s_gmm));
+        }
+        if (P->piece_out >= P->max_out) break;
     }
     return JD_OK;
 }
 
-// The pump, step 3: free slots take the next queued utterances (from batches whose scoring is enqueued to the last row: a slot's
-// ready number is counted up behind it)
+// The pump, step 2: free slots take the next queued utterances, from batches whose scoring is enqueued to the last row.  Where
+// the host knows that the table is scored (the batch's event) and the slot's last result went out without the side stream, the
+// command carries the ready number the slot has: nothing to wait for.  Otherwise a new ready number, counted up behind the kernel
+// export and every scoring launch enqueued so far.
 static int pump_refill(jd_dec *d)
 {
     Pipe *P = d->pipe;
     Resident *R = d->res;
-    std::vector<int> who;
+    std::vector<int> who, bump;
     std::vector<std::pair<int, int>> what;                             // (batch index in q, utterance)
     size_t bi = 0;
     for (int s = 0; s < P->n_slots; ++s) {
@@ -753,19 +787,26 @@ static int pump_refill(jd_dec *d)
         while (bi < P->q.size() && P->q[bi].next >= P->q[bi].n) ++bi;
         if (bi >= P->q.size() || P->q[bi].rows_scored < P->q[bi].rows) break;
         PipeBatch &B = P->q[bi];
+        if (P->decouple && !B.scored && hipEventQuery(P->ev_batch[(size_t)B.table]) == hipSuccess) B.scored = true;
         const int ui = B.order[(size_t)B.next++];                      // (longest first: a batch is handed back when its LAST utterance is through)
         B.u[(size_t)ui].state = 1; B.u[(size_t)ui].slot = s;
         P->slot_batch_id[(size_t)s] = (int)(P->serial0 + (long long)bi); P->slot_utt[(size_t)s] = ui;
         who.push_back(s); what.push_back(std::make_pair((int)bi, ui));
+        if (!B.scored || P->slot_kexport[(size_t)s]) bump.push_back(s);
+        P->slot_kexport[(size_t)s] = 0;
     }
     if (who.empty()) return JD_OK;
-    const int rc = res_bump(d, (int)who.size(), who.data());           // (behind the exports and every scoring launch enqueued so far)
-    if (rc) return rc;
+    if (!bump.empty()) {
+        const int rc = res_bump(d, (int)bump.size(), bump.data());     // (behind the exports and every scoring launch enqueued so far)
+        if (rc) return rc;
+    }
     for (size_t k = 0; k < who.size(); ++k) {
         const int s = who[k];
-        const PipeUtt &U = P->q[(size_t)what[k].first].u[(size_t)what[k].second];
+        const PipeBatch &B = P->q[(size_t)what[k].first];
+        const PipeUtt &U = B.u[(size_t)what[k].second];
+        const int T = std::min(U.T, P->chunk);
         R->stream[s].T_done = 0; R->stream[s].err_done = 0;
-        res_command(R, s, std::min(U.T, P->chunk), (int)U.row0, true);
+        res_command(R, s, T, (int)U.row0, true, (P->decouple && T == U.T) ? B.table * P->max_batch + what[k].second : -1);
     }
     return JD_OK;
 }
@@ -784,8 +825,8 @@ static int pipe_pump(jd_dec *d)
         if (rc) return rc;
     }
     int rc = pump_harvest(d);
-    if (!rc) rc = pump_score(d);
     if (!rc) rc = pump_refill(d);
+    if (!rc) rc = pump_score(d);
     return rc;
 }
 
@@ -856,6 +897,30 @@ extern "C" int jd_dec_pipeline_stats(const jd_dec *d, jd_pipe_stats *out)
     return JD_OK;
 }
 
+// Rows per scoring launch (jd_plan.h: plan_piece_rows): the piece between 4096 and 8192 rows - DESIGN.md 3.4's sweep: shorter
+// ones pay per launch, longer ones hold what waits behind them - whose last round of workgroups is fullest, with what the runtime
+// says of the slot kernel and of the scoring kernel on a CU.  (The kernels of 128-row tiles; the others keep PIPE_PIECE_ROWS0.)
+static_assert(PLAN_PIECE_TILE == GMM_ROWS2, "plan_piece_rows counts the scoring kernels' row tiles");
+static int pipe_plan_piece(const jd_dec *d, Pipe *P)
+{
+    int occ_gmm = 0, occ_slot = 0;
+    const int rc = gmm_tiles128_occupancy(d->am, d->amb, &occ_gmm);
+    if (rc) return rc;
+    if (occ_gmm <= 0) return JD_OK;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_slot, (const void *)slot_mailbox_kernel(d->am->max_n <= 5, d->models), SNT, 0));
+    const int wgs = plan_resident_scoring_wgs(d->n_cus, P->n_slots, occ_slot, occ_gmm);
+    int lo = 4096, hi = 8192;
+    int groups = (d->am->n_gmm + GMM_GT - 1) / GMM_GT;
+    // (launch_gmm: a launch of fewer than 1024 tiles is one of 16-state tiles)
+    if ((long long)(hi / GMM_ROWS2) * groups < 1024) groups = (d->am->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL;
+    else lo = std::max(lo, (1024 + groups - 1) / groups * GMM_ROWS2);
+    P->piece_rows = (size_t)plan_piece_rows(groups, wgs, lo, hi);
+    if (getenv("JD_VERBOSE"))
+        fprintf(stderr, "pipeline: pieces of %zu rows (%d state groups, %d scoring workgroups resident beside %d slots: %d + %d per CU alone)\n",
+                P->piece_rows, groups, wgs, P->n_slots, occ_slot, occ_gmm);
+    return JD_OK;
+}
+
 static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
 {
     const int G = d->am->n_gmm;
@@ -863,8 +928,13 @@ static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
     P->K = d->pipe_depth; P->max_batch = 2 * n_utts;
     P->n_slots = (d->pipe_slots > 0 && d->pipe_slots <= d->max_streams) ? d->pipe_slots : d->max_streams;
     if (const char *e = jd_dev_env("JD_PIPE_CHUNK")) { const int v = atoi(e); if (v >= 16) P->chunk = v; }   // development
+    if (const char *e = jd_dev_env("JD_PIPE_DECOUPLE")) P->decouple = atoi(e) != 0;                         // development
+    P->max_out = P->decouple ? 2 : 1;
+    if (P->decouple) { const int rc = pipe_plan_piece(d, P); if (rc) return rc; }
     if (const char *e = jd_dev_env("JD_PIPE_PIECE")) { const int v = atoi(e); if (v >= 128) P->piece_rows = (size_t)v / GMM_ROWS2 * GMM_ROWS2; }
-    if (hipEventCreateWithFlags(&P->ev_piece, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
+    P->ev_batch.assign((size_t)P->K, nullptr);
+    for (hipEvent_t &e : P->ev_piece) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
+    for (hipEvent_t &e : P->ev_batch) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
     P->table_rows = ((2 * rows + 1024) + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
     const size_t V = (size_t)P->K * P->max_batch;
     if (hipMalloc(&P->d_ll, (size_t)P->K * P->table_rows * G * sizeof(float)) != hipSuccess ||
@@ -880,6 +950,7 @@ static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
     HIPCHK(hipMemcpy(P->d_ident, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
     P->table_used.assign((size_t)P->K, 0);
     P->slot_batch_id.assign((size_t)P->n_slots, -1); P->slot_utt.assign((size_t)P->n_slots, -1); P->slot_dirty.assign((size_t)P->n_slots, 0);
+    P->slot_kexport.assign((size_t)P->n_slots, 0);
     return JD_OK;
 }
 
@@ -982,8 +1053,10 @@ static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_
         }
         std::this_thread::sleep_for(std::chrono::microseconds(20));
     }
-    HIPCHK(hipStreamSynchronize(d->s_gmm));                            // (the exports)
     PipeBatch &F = P->q.front();
+    // (the kernel's exports.  What the slots exported themselves is in memory since their reports: nothing to wait for, and the
+    // side stream has pieces of later batches on it)
+    if (F.n_kexport > 0) HIPCHK(hipStreamSynchronize(d->s_gmm));
     std::vector<int> slot_of((size_t)n_utts);
     for (int u = 0; u < n_utts; ++u) slot_of[(size_t)u] = F.u[(size_t)u].slot;
     if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);

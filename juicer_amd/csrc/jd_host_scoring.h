@@ -86,6 +86,11 @@ static void free_am_gmm(AmDevBuf &b)
     b = AmDevBuf();
 }
 
+// dynamic LDS of the kernels of 128-row tiles
+static size_t gmm39_lds() { return 130 * sizeof(JdLogTab) + 32 * sizeof(unsigned long long) + (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float); }
+static size_t gmm_fast39_lds() { return (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float); }
+static size_t gmm_fast_lds() { return (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * sizeof(float); }
+
 // max_blocks > 0 bounds the grid (the kernel strides over the tiles): next to the search, a
 // chip-filling scoring launch holds every wave slot for milliseconds and the latency-bound search
 // kernels, which need slots for microseconds at a time, all but stop (measured: 25 ms of
@@ -116,7 +121,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
     if (small_tiles) tiles = row_tiles * ((a->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL);
     dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
     if (a->D == 39 && b.fast && b.par_fast) {
-        const size_t sm = (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float);
+        const size_t sm = gmm_fast39_lds();
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
@@ -124,7 +129,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
             hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
     } else if (fast_any) {
-        const size_t sm = (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * sizeof(float);
+        const size_t sm = gmm_fast_lds();
         const int DP = jd_fast_dp(a->D);
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_fast<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
@@ -133,7 +138,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
             hipLaunchKernelGGL(jd_gmm_fast<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
     } else if (a->D == 39) {
-        const size_t sm = 130 * sizeof(JdLogTab) + 32 * sizeof(unsigned long long) + (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float);
+        const size_t sm = gmm39_lds();
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_kernel39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, b.logtab, rt_base, n_rt_list);
@@ -147,6 +152,18 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
                            b.n_mix, a->n_gmm, a->max_mix, a->D, d_ll, skip_unused, b.logtab);
     }
     HIPCHK(hipGetLastError());
+    return JD_OK;
+}
+
+// Workgroups of the scoring kernel launch_gmm chooses for a large launch that a CU holds, as the runtime counts them for the kernel
+// alone; *per_cu = 0 where the kernel is not one of 128-row tiles (hybrid models, exact scoring of D != 39)
+static int gmm_tiles128_occupancy(const jd_am *a, const AmDevBuf &b, int *per_cu)
+{
+    *per_cu = 0;
+    if (a->hybrid) return JD_OK;
+    if (a->D == 39 && b.fast && b.par_fast) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_fast39<GMM_GT>, 256, gmm_fast39_lds()));
+    else if (a->D != 39 && b.fast && b.par_fast) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_fast<GMM_GT>, 256, gmm_fast_lds()));
+    else if (a->D == 39) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_kernel39<GMM_GT>, 256, gmm39_lds()));
     return JD_OK;
 }
 

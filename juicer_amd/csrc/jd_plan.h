@@ -337,3 +337,39 @@ static inline ResPlanOut plan_resident(const ResPlanIn &in)
     }
     return out;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// The batch pipeline's scoring launches (jd_host_resident.h: pump_score).  A piece is a grid of row tiles x state groups; the device
+// holds `resident_scoring_wgs` of the scoring kernel's workgroups at once beside the slots, so the piece runs in rounds of that
+// many, and the kernel behind it on the side stream cannot start under a last round that is half empty.
+
+// Scoring workgroups resident at once beside the slots, from what the runtime says of each kernel ALONE: occ_slot slot workgroups
+// fill a CU, occ_gmm scoring workgroups fill one, and a CU that holds k slots has (occ_slot - k) / occ_slot of itself left.  The
+// slots are dealt one per CU first (jd_host_resident.h: park_and_launch_slots).
+static inline int plan_resident_scoring_wgs(int n_cus, int n_slots, int occ_slot, int occ_gmm)
+{
+    if (n_cus < 1 || occ_slot < 1 || occ_gmm < 1) return 1;
+    const int base = std::max(0, n_slots) / n_cus, extra = std::max(0, n_slots) % n_cus;   // `extra` CUs hold base + 1 slots
+    auto beside = [&](int k) { return k >= occ_slot ? 0 : occ_gmm * (occ_slot - k) / occ_slot; };
+    return std::max(1, extra * beside(base + 1) + (n_cus - extra) * beside(base));
+}
+
+// Rows per piece: the multiple of 128 (GMM_ROWS2) in [lo, hi] whose tiles - rows / 128 x n_state_groups - leave the smallest share
+// of their last round empty; of two that leave the same, the smaller.  (lo, hi: rounded inwards to whole tiles; one tile at least.)
+#define PLAN_PIECE_TILE 128
+static inline long long plan_piece_waste(long long row_tiles, int n_state_groups, int resident_scoring_wgs)
+{
+    const long long w = std::max(1, resident_scoring_wgs), tiles = row_tiles * std::max(1, n_state_groups);
+    return (w - tiles % w) % w;                                        // workgroup places of the last round nobody takes
+}
+static inline int plan_piece_rows(int n_state_groups, int resident_scoring_wgs, int lo, int hi)
+{
+    long long t_lo = std::max(1, (lo + PLAN_PIECE_TILE - 1) / PLAN_PIECE_TILE), t_hi = std::max(1, hi / PLAN_PIECE_TILE);
+    if (t_hi < t_lo) t_hi = t_lo;
+    long long best = t_lo, best_w = plan_piece_waste(t_lo, n_state_groups, resident_scoring_wgs);
+    for (long long t = t_lo + 1; t <= t_hi && best_w > 0; ++t) {
+        const long long w = plan_piece_waste(t, n_state_groups, resident_scoring_wgs);
+        if (w < best_w) { best = t; best_w = w; }
+    }
+    return (int)(best * PLAN_PIECE_TILE);
+}

@@ -23,7 +23,9 @@ struct __align__(64) ResPost {  // host-mapped, one per stream: the HOST writes 
     int exit_req;              // != 0: leave the kernel
     int init;                  // != 0: a new utterance begins with this command (IDecoder::init: what jd_mark_init_kernel does,
                                // done by the cluster's first workgroup - the batch pipeline, jd_pipe_*)
-    int pad[10];
+    int vslot;                 // >= 0: the command ends an utterance, and a slot that brings it to T without an error exports the
+                               // result to this virtual result slot itself (k_slot; -1: none - always, from the broker and for k_resident)
+    int pad[9];
 };
 struct __align__(128) ResMail { // device memory, one per stream: workgroup 0 of the cluster passes the command on to the others
     unsigned long long word;
@@ -36,6 +38,8 @@ struct ResDone {               // host-mapped, one per stream: written by workgr
     int error;                 // StreamCtl::error
     int left;                  // 1: the cluster has left the kernel (exit request, or nobody posted anything for RES_IDLE_TICKS)
     long long run_ticks;       // (statistics) 100 MHz ticks the cluster spent on the command
+    int exported;              // 1: the slot has exported the utterance's result to the command's virtual result slot (ResPost::vslot)
+    int pad;
 };
 #define RES_IDLE_TICKS 500000000LL      // 5 s at 100 MHz without a command AND without a sign of life from the host: the kernel ends by itself
 

@@ -720,9 +720,18 @@ __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot_batch(SearchArgs A)
 // The slot kernel under the mailbox of jd_resident.h (the same commands, reports, ready numbers and host heartbeat as
 // k_resident; grid = streams, one workgroup each, SLOT_WG_PER_CU of them per CU - all resident at once).
 // started (host-mapped, or null): counted up by every workgroup when it is on its CU - the host releases the parked CUs then (jd_park_kernel)
+// E: the pipeline's virtual result slots.  A command that says so (ResPost::vslot) and brings its utterance to T without an error
+// has the result exported by the slot itself (jd_gc.h: jd_export_utt, the walk of jd_finish_export_kernel) before the report,
+// which then says "exported": nothing of that hand-over goes down the side stream.
+// k_slot's export of the utterance its slot has finished, by the lanes of one wave.  A function of its own, called: inlined, what it
+// computes from the kernel's arguments is hoisted out of the mailbox loop and kept over slot_run (see slot_tid: 5 more VGPRs spilled).
+__device__ __attribute__((noinline)) void slot_export(const StreamCtl *c, const StreamDev *S, int v, ExportDst E, int lane)
+{
+    jd_export_utt(*c, *S, v, E, lane, 64);
+}
 template <int NE, bool MDL>
 __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot(SearchArgs A, const ResPost *post, const unsigned *ready, ResDone *done, const unsigned *beat,
-                                                        unsigned *started)
+                                                        unsigned *started, ExportDst E)
 {
     __shared__ SlotShared sh;
     __shared__ unsigned long long sh_word;
@@ -791,13 +800,21 @@ __global__ __launch_bounds__(SNT, SLOT_WPE) void k_slot(SearchArgs A, const ResP
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();                                               // every wave's end-of-command words are written before the host hears of it
-        if (tid == 0) {
+        if (tid < 64) {                                                // (the first wave, whole: its lanes share the export)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             const int fr = __hip_atomic_load(&c.frame, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int er = __hip_atomic_load(&c.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // the utterance is through: its result to the virtual slot the command names.  One wave writes, and the system-scope
+            // release below is that wave's: the host's later copy finds the stores in memory, as it finds the end-of-command words.
+            const int vslot = __hip_atomic_load(&post[s].vslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const int T = __hip_atomic_load(&c.T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool exp = E.vctl != nullptr && vslot >= 0 && er == 0 && fr == T;
+            if (exp) slot_export(&c, &A.streams[s], vslot, E, tid);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            done[s].frame = fr; done[s].error = er; done[s].run_ticks = wall_clock64() - t_cmd;
-            __hip_atomic_store(&done[s].seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (tid == 0) {
+                done[s].frame = fr; done[s].error = er; done[s].run_ticks = wall_clock64() - t_cmd; done[s].exported = exp ? 1 : 0;
+                __hip_atomic_store(&done[s].seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
         seen = seq;
     }
