@@ -49,8 +49,8 @@
 #include <vector>
 
 #include "jd_internal.h"
+#include "jd_prep.h"            // LZ, the device arc's flags, XState; the graph preparation of jd_dec_create
 
-#define LZ (-3.402823466e+38f)
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
 #define GMM_GT_SMALL 16         // ... of a launch with few rows (jd_gmm_kernel39 only)
@@ -412,9 +412,12 @@ extern "C" void jd_dec_destroy(jd_dec *d)
     delete d;
 }
 
-extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, float start_beam, float main_beam,
-                             float end_beam, float word_beam, int32_t max_hyps, int32_t block_size,
-                             int32_t device, int32_t max_streams)
+// ---- jd_dec_create, step by step.  What the search kernels see of the graph and the models is decided in jd_prep.h (pure, tested on
+// the CPU: tests/test_prep_cpu.py); the steps here read the knobs, say what was decided (JD_VERBOSE) and upload it.  A step that fails
+// returns its code and jd_dec_create destroys the decoder.
+
+static int dec_check_args(jd_dec **out, const jd_net *net, const jd_am *am, float main_beam, int32_t max_hyps, int32_t block_size,
+                          int32_t device, int32_t max_streams, PrepHist *hist)
 {
     if (!out || !net || !am) return jd_fail(JD_EINVAL, "jd_dec_create: null argument");
     if (block_size < 1 || block_size > 20)      // HTKFlatModels::setBlockSize, HTKFlatModels.cpp:311-312
@@ -429,254 +432,101 @@ extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, f
         return jd_fail(JD_EINVAL, "networks with more than %lld states unsupported", (long long)(0xf0000000LL / (int64_t)sizeof(StateRec)));
     int rc = check_device(device);
     if (rc) return rc;
-    jd_dec *d = new jd_dec();
-    d->net = net; d->am = am; d->device = device; d->max_streams = max_streams; d->block_size = block_size;
-    // development: frames per chunk of a batch
-    if (const char *e = jd_dev_env("JD_FC")) { const int v = atoi(e); if (v >= 16 && v <= 65536) d->Fw_env = v; }
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) d->n_cus = prop.multiProcessorCount;
-    }
-    DecConst &C = d->C;
-    C.start_win = start_beam; C.emit_win = main_beam; C.end_win = end_beam; C.word_win = word_beam;
-    C.max_hyps = max_hyps;
-    C.x_chunks = 2;
-    if (const char *e = jd_dev_env("JD_XCH")) { const int v = atoi(e); if (v >= 1 && v <= 16) { C.x_chunks = v; d->xch_forced = true; } }   // development
-    C.exp = 0; C.path_rule = 0; C.pcount = nullptr;
-    if (const char *e = jd_dev_env("JD_EXP")) C.exp = atoi(e);                                                    // development
-    C.hist_min = 0; C.hist_max = 0; C.hist_nbins = 0;
-    if (max_hyps > 0) {                          // WFSTDecoderLite.cpp:76-82, Histogram.cpp:29-37
-        float mn = (main_beam > 0.0) ? (float)(-main_beam - 800.0) : -1000.0f;
-        C.hist_min = (int)(mn - 1.0);
-        C.hist_max = (int)(200.0f + 1.0);
-        C.hist_nbins = C.hist_max - C.hist_min + 1;
-        if (C.hist_nbins > HIST_MAX_BINS) {
-            delete d;
-            return jd_fail(JD_EINVAL, "mainBeam %.1f needs %d histogram bins (> %d supported)", main_beam,
-                           C.hist_nbins, HIST_MAX_BINS);
-        }
-    }
-#define TRY(x) do { rc = (x); if (rc) { jd_dec_destroy(d); return rc; } } while (0)
-    const bool lazy = net->lazy_dev != nullptr;
-    if (lazy && net->lazy_device != device) {
-        jd_dec_destroy(d);
+    *hist = prep_hist(main_beam, max_hyps);
+    if (hist->hist_nbins > HIST_MAX_BINS)
+        return jd_fail(JD_EINVAL, "mainBeam %.1f needs %d histogram bins (> %d supported)", main_beam, hist->hist_nbins, HIST_MAX_BINS);
+    if (net->lazy_dev && net->lazy_device != device)
         return jd_fail(JD_EINVAL, "jd_dec_create: the lazily composed network lives on device %d, not %d", net->lazy_device, device);
-    }
-    // The decoder's OWN numbering of the states.  A stream's per-state words (jd_search.h: StateRec) are gathered by state number, eight
-    // arrival keys to a 64-byte line, so which states are neighbours in NUMBER decides how many lines a frame fetches - and tokens
-    // move along chains.  The numbering: a state, then, arc by arc, the chain of one-arc states behind each of its arcs (the phones of
-    // a word, one state after the other; the chains that leave one state side by side, as their instances are attached in the same
-    // frame); the states the chains END in - the ones with a choice to make - get their number there and take their turn first come,
-    // first served.  That is how a lexicon written chain after chain is laid out already, and such a network keeps its numbering; one
-    // numbered by its composition (jd_net_compose: canonical, breadth first) gets this one.  State numbers never leave the device and
-    // nothing breaks a tie by them (the frontier item's number does): results are bit-identical.  Measured on the composed configs[4]
-    // graph (k frames/s, tools/r6_run21-24.sh): the network's numbers 36.7, along the chains of first model arcs 36.7 (round 6's first
-    // attempt), depth first 41.3, blocks of 16 filled breadth first 43.5, this 45.0; on the bench's generated graphs it equals the
-    // generator's own order (129.8 / 129.1 k, 5.60 / 5.65 k), every other order loses 1-4 % to it.
-    // (JD_RENUMBER, development: 1 / 0 - always / never.)
-    std::vector<int> rp_own;                                           // row_ptr in the decoder's numbering (empty: the network's)
-    std::vector<JdArc> arcs_own;
-    int64_t n_next_net = 0;                                            // arcs of the network that lead to the next state number
-    if (!lazy)
-        for (int q = 0; q < net->n_states; ++q)
-            for (int b = net->row_ptr[(size_t)q]; b < net->row_ptr[(size_t)q + 1]; ++b) n_next_net += net->arcs[(size_t)b].to == q + 1;
-    bool renumber = !lazy && net->n_states > 0 && 4 * n_next_net < (int64_t)net->n_arcs;
-    if (const char *e = jd_dev_env("JD_RENUMBER")) renumber = !lazy && net->n_states > 0 && atoi(e) != 0;
-    if (renumber) {
-        const int ns = net->n_states;
-        std::vector<int> new_of((size_t)ns, -1), old_of((size_t)ns);
-        int next = 0;
-        auto take = [&](int q) { new_of[(size_t)q] = next; old_of[(size_t)next] = q; ++next; };
-        std::vector<int> pend;                                         // numbered states whose arcs are still to be followed, in the order they were met
-        for (int pass = 0; pass < 2; ++pass)                           // (from the initial state; then whatever it does not reach, in the network's order)
-            for (int s0 = pass == 0 ? net->init : 0; s0 < (pass == 0 ? net->init + 1 : ns); ++s0) {
-                if (new_of[(size_t)s0] >= 0) continue;
-                take(s0);
-                pend.clear(); pend.push_back(s0);
-                for (size_t ph = 0; ph < pend.size(); ++ph) {
-                    const int q = pend[ph];
-                    for (int b = net->row_ptr[(size_t)q]; b < net->row_ptr[(size_t)q + 1]; ++b) {
-                        int t = net->arcs[(size_t)b].to;
-                        while (new_of[(size_t)t] < 0 && net->row_ptr[(size_t)t + 1] - net->row_ptr[(size_t)t] == 1) {
-                            take(t);
-                            t = net->arcs[(size_t)net->row_ptr[(size_t)t]].to;
-                        }
-                        if (new_of[(size_t)t] < 0) { take(t); pend.push_back(t); }
-                    }
-                }
-            }
-        bool same = true;
-        for (int q = 0; q < ns && same; ++q) same = new_of[(size_t)q] == q;
-        if (!same) {
-            rp_own.assign((size_t)ns + 1, 0);
-            for (int n = 0; n < ns; ++n) rp_own[(size_t)n + 1] = rp_own[(size_t)n] + (net->row_ptr[(size_t)old_of[(size_t)n] + 1] - net->row_ptr[(size_t)old_of[(size_t)n]]);
-            arcs_own.resize(net->arcs.size());
-            for (int n = 0; n < ns; ++n) {
-                const int q = old_of[(size_t)n], r0 = net->row_ptr[(size_t)q], r1 = net->row_ptr[(size_t)q + 1];
-                for (int b = r0; b < r1; ++b) {
-                    JdArc a = net->arcs[(size_t)b];
-                    a.to = new_of[(size_t)a.to];
-                    arcs_own[(size_t)rp_own[(size_t)n] + (size_t)(b - r0)] = a;
-                }
-            }
-            d->state_new.swap(new_of);
-        }
-        if (getenv("JD_VERBOSE")) fprintf(stderr, "state numbers: %s\n", same ? "the network's (already along its chains)" : "the decoder's own (a state, the chains behind its arcs side by side)");
-    }
-    const std::vector<int> &row_ptr_h = rp_own.empty() ? net->row_ptr : rp_own;
-    const std::vector<JdArc> &arcs_h = arcs_own.empty() ? net->arcs : arcs_own;
-    if (!lazy) TRY(dupload(d, &d->d_row_ptr, row_ptr_h.data(), row_ptr_h.size()));
-    std::vector<float> tmax0((size_t)am->n_hmm, LZ);   // largest log transition probability out of the entry state of every HMM
-    for (int h = 0; h < am->n_hmm; ++h) {
-        const float *t0 = am->trP.data() + (size_t)am->hmm_tm[(size_t)h] * am->max_n * am->max_n;
-        for (int j = 0; j < am->hmm_n[(size_t)h]; ++j) tmax0[(size_t)h] = std::max(tmax0[(size_t)h], t0[j]);
-    }
-    if (!lazy) {   // device arc table: bit 30 of the in-label marks arcs whose HMM is a tee model
-        std::vector<JdArc> darcs(arcs_h);
-        for (JdArc &a : darcs)
-            if (a.in > 0 && am->hmm_tee[(size_t)a.in - 1] > LZ) a.in |= TEE_FLAG;
-        // The decoder's OWN order of a state's arcs (XState, jd_search.h): what every arrival walks first, then the arcs that
-        // enter a model by descending w + tmax - phase X of the slot kernel walks a prefix of those.  Arc numbers never leave
-        // the device (results carry labels, times and scores), and every arc has an instance of its own, so the order changes no
-        // score; it can change which of two EQUAL-scored tokens a state keeps (the frontier item's number breaks the tie), which
-        // the reference's own traversal order decides no better (tests: decode_certified).  JD_NO_XSORT (development): the file's order.
-        const bool xsort = jd_dev_env("JD_NO_XSORT") == nullptr;
-        std::vector<XState> xst((size_t)net->n_states);
-        std::vector<std::pair<float, JdArc>> ent;
-        for (int q = 0; q < net->n_states; ++q) {
-            const int r0 = row_ptr_h[(size_t)q], r1 = row_ptr_h[(size_t)q + 1];
-            XState &X = xst[(size_t)q];
-            X.n_always = 0; X.n_entry = 0; X.wmax = LZ; X.n_model = 0;
-            for (int i = 0; i < XNCAND; ++i) X.k[i] = LZ;
-            ent.clear();
-            // (only rows the cut can apply to - up to 57 arcs, jd_slot.h: the flags of a longer row do not fit an item's loads -
-            // change their order: the long rows of trigram-shaped graphs keep the file's, which the searches of such graphs
-            // are 2-3 % faster on; measured on the north-star graph)
-            const bool sort_row = xsort && r1 - r0 <= 57;
-            int at = r0;
-            for (int b = r0; b < r1; ++b) {
-                const JdArc a = darcs[(size_t)b];
-                const int inl = a.in & ~TEE_FLAG;
-                if (inl != 0) { ++X.n_model; X.wmax = std::max(X.wmax, a.w); }
-                if (sort_row && inl != 0 && !(a.in & TEE_FLAG)) ent.push_back({a.w + tmax0[(size_t)inl - 1], a});
-                else darcs[(size_t)at++] = a;                          // (in place: `at` never passes b)
-            }
-            X.n_always = at - r0;
-            std::stable_sort(ent.begin(), ent.end(), [](const std::pair<float, JdArc> &x, const std::pair<float, JdArc> &y) { return x.first > y.first; });
-            X.n_entry = (int)ent.size();
-            for (size_t i = 0; i < ent.size(); ++i) darcs[(size_t)at + i] = ent[i].second;
-            for (int i = 0; i < XNCAND; ++i) if (xcand(i) < X.n_entry) X.k[i] = ent[(size_t)xcand(i)].first;
-        }
-        {   // SOLE_FLAG (jd_search.h: REC_SOLE): the arc that enters a model and is the only arc of the network that leads to its
-            // destination - its exit tokens recombine with nobody.  (JD_NO_SOLE, development: off.)
-            std::vector<int> indeg((size_t)net->n_states, 0);
-            for (const JdArc &a : darcs) ++indeg[(size_t)a.to];
-            int64_t n_sole = 0, n_model = 0;
-            const bool sole_on = jd_dev_env("JD_NO_SOLE") == nullptr;
-            for (JdArc &a : darcs)
-                if ((a.in & ~TEE_FLAG) != 0) { ++n_model; if (sole_on && indeg[(size_t)a.to] == 1 && !(a.in & TEE_FLAG)) { a.in |= SOLE_FLAG; ++n_sole; } }   // (a tee model's pass-through arrives beside its exit token)
-            if (getenv("JD_VERBOSE")) fprintf(stderr, "exit tokens that recombine with nobody: those of %lld of %lld model arcs (the only arc into their state)\n", (long long)n_sole, (long long)n_model);
-        }
-        TRY(dupload(d, &d->d_arcs, darcs.data(), darcs.size()));
-        TRY(dupload(d, &d->d_xst, xst.data(), xst.size()));
-        // (k_search takes the cut where it pays - graphs whose rows are short throughout, like configs[1]'s: 99.7 % of its model arcs
-        // sit in sorted rows, two batches in flight gain 10 % - and not where a few long rows carry the traffic: trigram-shaped
-        // graphs have 85-87 % of their arcs in short rows, yet configs[3] loses 4 % to the item stage's extra loads and the
-        // north-star graph gains nothing)
-        int64_t n_sorted = 0, n_model_all = 0;
-        for (const XState &X : xst) { n_sorted += X.n_entry; n_model_all += X.n_model; }
-        C.xcut = (xsort && n_model_all > 0 && 20 * n_sorted >= 19 * n_model_all) ? 1 : 0;
-        if (const char *e = jd_dev_env("JD_XCUT")) C.xcut = (atoi(e) != 0 && xsort) ? 1 : 0;
-        if (getenv("JD_VERBOSE")) fprintf(stderr, "arc order: %lld of %lld model arcs in sorted rows (<= 57 arcs), %d states; k_search cuts walks: %d\n",
-                                          (long long)n_sorted, (long long)n_model_all, net->n_states, C.xcut);
-    }
-    {   // The layout of a stream's per-state words (jd_search.h: StateRec): split - the arrival keys of all states in an array of their own,
-        // four states to a 64-byte line - where the graph's numbering puts the states of a chain side by side (an arc to the NEXT state
-        // number: the lexicon chains of a composed C.L.G written state after state - 42 % of the arcs of the bench graphs), joint where it
-        // does not (a graph numbered by its composition: what neighbours in number have in common is nothing, and every exit token would
-        // pay a second line).  (JD_SREC_SPLIT, development: 1 / 0.)
-        int64_t n_next = 0;
-        if (!lazy)
-            for (int q = 0; q < net->n_states; ++q)
-                for (int b = row_ptr_h[(size_t)q]; b < row_ptr_h[(size_t)q + 1]; ++b) n_next += arcs_h[(size_t)b].to == q + 1;
-        int split = (!lazy && net->n_arcs > 0 && 4 * n_next >= (int64_t)net->n_arcs) ? 2 : 0;   // 0 joint, 1 split (both parities of a state together), 2 split by parity
-        if (const char *e = jd_dev_env("JD_SREC_SPLIT")) split = std::max(0, std::min(2, atoi(e)));
-        const unsigned ns = (unsigned)net->n_states;
-        C.srec_stride = split ? 16u : 32u;
-        C.srec_arr = split ? 16u * ns : 16u;
-        C.srec_estride = split == 2 ? 8u : (split ? 16u : 32u);
-        C.srec_par = split == 2 ? 8u * ns : 8u;
-        if (getenv("JD_VERBOSE")) fprintf(stderr, "per-state words: %s (%lld of %lld arcs lead to the next state number)\n",
-                                          split == 2 ? "split (bids | arrival keys of either frame parity)" : split ? "split (bids | arrival keys)" : "joint records",
-                                          (long long)n_next, (long long)net->n_arcs);
-    }
+    return JD_OK;
+}
+
+// the development knobs of the preparation (docs/DEV_KNOBS.md), as jd_prep.h takes them
+static PrepKnobs dec_prep_knobs()
+{
+    PrepKnobs k;
+    if (const char *e = jd_dev_env("JD_RENUMBER")) k.renumber = atoi(e) != 0;
+    if (jd_dev_env("JD_NO_XSORT")) k.xsort = 0;
+    if (jd_dev_env("JD_NO_SOLE")) k.sole = 0;
+    if (const char *e = jd_dev_env("JD_XCUT")) k.xcut = atoi(e) != 0;
+    if (const char *e = jd_dev_env("JD_SREC_SPLIT")) k.srec_split = std::max(0, std::min(2, atoi(e)));
+    if (jd_dev_env("JD_NO_LR")) k.no_lr = 1;
+    return k;
+}
+
+// The graph as the kernels see it: the decoder's own state numbering, arc order and arc flags, the layout of the per-state words, the
+// final weights.  A lazily composed network has no graph of its own to prepare: joint records unless the knob says otherwise, no XState.
+static int dec_upload_graph(jd_dec *d, const PrepKnobs &knobs, const std::vector<float> &tmax0)
+{
+    const jd_net *net = d->net;
+    DecConst &C = d->C;
+    const bool lazy = net->lazy_dev != nullptr, verbose = getenv("JD_VERBOSE") != nullptr;
+    int rc;
+    PrepNumbering N;
     if (!lazy) {
-        if (d->state_new.empty()) TRY(dupload(d, &d->d_fin_w, net->fin_w.data(), net->fin_w.size()));
-        else {
-            std::vector<float> fw(net->fin_w.size());
-            for (size_t q = 0; q < fw.size(); ++q) fw[(size_t)d->state_new[q]] = net->fin_w[q];
-            TRY(dupload(d, &d->d_fin_w, fw.data(), fw.size()));
-        }
+        N = prep_renumber(*net, knobs.renumber);
+        if (N.tried && verbose) fprintf(stderr, "state numbers: %s\n", N.same ? "the network's (already along its chains)" : "the decoder's own (a state, the chains behind its arcs side by side)");
     }
-    TRY(dupload(d, &d->d_hmm_tee, am->hmm_tee.data(), am->hmm_tee.size()));
-    TRY(dupload(d, &d->d_hmm_tmax0, tmax0.data(), tmax0.size()));     // (phase X, hopeless candidates)
-    TRY(dupload(d, &d->d_trP, am->trP.data(), am->trP.size()));
-    std::vector<int> se32((size_t)am->n_tm * am->max_n);
-    for (size_t i = 0; i < se32.size(); ++i)
-        se32[i] = ((int)am->se[i * 2] & 0xffff) | ((int)am->se[i * 2 + 1] << 16);
-    TRY(dupload(d, &d->d_se32, se32.data(), se32.size()));
-    TRY(upload_am_gmm(am, d->amb));
+    const std::vector<int32_t> &row_ptr_h = N.state_new.empty() ? net->row_ptr : N.row_ptr;
+    const std::vector<JdArc> &arcs_h = N.state_new.empty() ? net->arcs : N.arcs;
+    if (!lazy) {
+        if ((rc = dupload(d, &d->d_row_ptr, row_ptr_h.data(), row_ptr_h.size()))) return rc;
+        const PrepArcs A = prep_arcs(row_ptr_h, arcs_h, net->n_states, *d->am, tmax0, knobs);
+        if (verbose) fprintf(stderr, "exit tokens that recombine with nobody: those of %lld of %lld model arcs (the only arc into their state)\n", (long long)A.n_sole, (long long)A.n_model);
+        if ((rc = dupload(d, &d->d_arcs, A.arcs.data(), A.arcs.size()))) return rc;
+        if ((rc = dupload(d, &d->d_xst, A.xst.data(), A.xst.size()))) return rc;
+        C.xcut = A.xcut;
+        if (verbose) fprintf(stderr, "arc order: %lld of %lld model arcs in sorted rows (<= %d arcs), %d states; k_search cuts walks: %d\n",
+                             (long long)A.n_sorted, (long long)A.n_model_all, XSORT_MAX_ROW, net->n_states, C.xcut);
+    }
+    const PrepSrec S = prep_srec_layout(row_ptr_h, arcs_h, net->n_states, net->n_arcs, knobs.srec_split);
+    C.srec_stride = S.stride; C.srec_arr = S.arr; C.srec_estride = S.estride; C.srec_par = S.par;
+    if (verbose) fprintf(stderr, "per-state words: %s (%lld of %lld arcs lead to the next state number)\n",
+                         S.split == 2 ? "split (bids | arrival keys of either frame parity)" : S.split ? "split (bids | arrival keys)" : "joint records",
+                         (long long)S.n_next, (long long)net->n_arcs);
+    if (!lazy) {
+        if (N.state_new.empty()) rc = dupload(d, &d->d_fin_w, net->fin_w.data(), net->fin_w.size());
+        else {
+            const std::vector<float> fw = permute_by_state(N.state_new, net->fin_w);
+            rc = dupload(d, &d->d_fin_w, fw.data(), fw.size());
+        }
+        if (rc) return rc;
+    }
+    d->state_new = std::move(N.state_new);
+    return JD_OK;
+}
+
+static int dec_upload_models(jd_dec *d, const PrepModels &M)
+{
+    const jd_am *am = d->am;
+    int rc;
+    if ((rc = dupload(d, &d->d_hmm_tee, am->hmm_tee.data(), am->hmm_tee.size()))) return rc;
+    if ((rc = dupload(d, &d->d_hmm_tmax0, M.tmax0.data(), M.tmax0.size()))) return rc;     // (phase X, hopeless candidates)
+    if ((rc = dupload(d, &d->d_trP, am->trP.data(), am->trP.size()))) return rc;
+    if ((rc = dupload(d, &d->d_se32, M.se32.data(), M.se32.size()))) return rc;
+    if ((rc = upload_am_gmm(am, d->amb))) return rc;
+    if ((rc = dupload(d, &d->d_aux, M.aux.data(), M.aux.size()))) return rc;
+    if (!M.lrt.empty() && (rc = dupload(d, &d->d_lrt, M.lrt.data(), M.lrt.size()))) return rc;
+    return JD_OK;
+}
+
+// what the kernels are handed of all that (the pruning windows and the histogram's range are set before the uploads)
+static void dec_fill_const(jd_dec *d)
+{
+    const jd_net *net = d->net;
+    const jd_am *am = d->am;
+    DecConst &C = d->C;
     C.row_ptr = d->d_row_ptr; C.arcs = d->d_arcs; C.fin_w = d->d_fin_w; C.init_state = d->state_new.empty() ? net->init : d->state_new[(size_t)net->init]; C.n_states = net->n_states;
     C.xst = d->d_xst;
     C.G = am->n_gmm; C.max_n = am->max_n; C.n_tm = am->n_tm;
     C.hmm_tee = d->d_hmm_tee; C.n_hmm = am->n_hmm; C.hmm_tmax0 = d->d_hmm_tmax0;
-    C.lazy = (const LazyDev *)net->lazy_dev; C.aux_h = nullptr;
-    {   // instance template: what phase A needs to attach an instance (attachNetInst :751-774), by HMM -
-        // {nStates | transMat << 8, g0, g1, g2} (+ {g3, g4, g5, 0}): one hop behind the arc record's label, but the
-        // table is a few tens of KB (L2 hits) where a per-arc copy was a second random 64-byte sector per new
-        // instance and 16-32 B per arc of HBM (measured: same speed at configs[1], +0.5 % in the heavy legs)
-        const int AI = (am->max_n <= 5) ? 4 : 8;
-        std::vector<int> aux((size_t)am->n_hmm * AI, 0);
-        for (int hm = 0; hm < am->n_hmm; ++hm) {
-            const int n = am->hmm_n[(size_t)hm];
-            int *a = aux.data() + (size_t)hm * AI;
-            a[0] = n | (am->hmm_tm[(size_t)hm] << 8);
-            for (int j = 1; j < n - 1 && j <= (AI == 4 ? 3 : 6); ++j)
-                a[j] = am->hmm_gmm[(size_t)hm * am->max_n + j];
-        }
-        TRY(dupload(d, &d->d_aux, aux.data(), aux.size()));
-        C.aux_h = d->d_aux;
-    }
+    C.lazy = (const LazyDev *)net->lazy_dev; C.aux_h = d->d_aux;
     C.trP = d->d_trP; C.se32 = d->d_se32;
-    {   // Plain left-to-right topologies (every emitting state entered from its predecessor and itself,
-        // the exit state from the last emitting state - createTrPandSEIndex, HTKModels.cpp:2330-2390,
-        // gives SEIndex[j] = {j-1, j+1}): phase A then needs a_k = log P(k-1 -> k), s_k = log P(k -> k) only
-        const int MNn = am->max_n, NEn = (MNn <= 5) ? 3 : 6, LRW = (NEn == 3) ? 8 : 16;
-        bool all_lr = (size_t)am->n_tm * LRW <= TRP_LDS_MAX;
-        for (int t = 0; t < am->n_tm && all_lr; ++t) {
-            const int n = am->tm_n[(size_t)t];
-            if (n < 3) all_lr = false;
-            for (int j = 1; j < n && all_lr; ++j) {
-                const int st = am->se[((size_t)t * MNn + j) * 2], en = am->se[((size_t)t * MNn + j) * 2 + 1];
-                if (j < n - 1 ? (st != j - 1 || en != j + 1) : (st != n - 2 || en != n - 1)) all_lr = false;
-            }
-        }
-        for (int h = 0; h < am->n_hmm && all_lr; ++h)
-            if (am->hmm_n[(size_t)h] != am->tm_n[(size_t)am->hmm_tm[(size_t)h]]) all_lr = false;
-        if (jd_dev_env("JD_NO_LR")) all_lr = false;                                  // development: force the general path
-        C.lrt = nullptr;
-        if (all_lr) {
-            std::vector<float> lrt((size_t)am->n_tm * LRW, LZ);
-            for (int t = 0; t < am->n_tm; ++t) {
-                const float *tp = am->trP.data() + (size_t)t * MNn * MNn;
-                const int n = am->tm_n[(size_t)t];
-                for (int k = 1; k <= n - 1; ++k) lrt[(size_t)t * LRW + k - 1] = tp[(k - 1) * MNn + k];          // a_k
-                for (int k = 1; k <= n - 2; ++k) lrt[(size_t)t * LRW + NEn + k] = tp[k * MNn + k];              // s_k
-            }
-            TRY(dupload(d, &d->d_lrt, lrt.data(), lrt.size()));
-            C.lrt = d->d_lrt;
-        }
-    }
+    C.lrt = d->d_lrt;
+}
+
+// the planner's and the pipeline's development knobs (docs/DEV_KNOBS.md)
+static void dec_read_planner_knobs(jd_dec *d)
+{
     if (const char *e = jd_dev_env("JD_CW")) { const int v = atoi(e); if (v >= 1 && v <= MAXCW) d->max_cw = v; }   // development
     if (const char *e = jd_dev_env("JD_WEIGHTED")) d->weighted = atoi(e) != 0;
     if (const char *e = jd_dev_env("JD_REBALANCE")) d->rebalance = atoi(e) != 0;
@@ -703,36 +553,69 @@ extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, f
     if (const char *e = jd_dev_env("JD_BG_MAX_LOAD")) d->bg_max_load = atof(e);
     if (const char *e = jd_dev_env("JD_FG_CW")) d->fg_cw_cap = std::max(1, atoi(e));
     if (const char *e = jd_dev_env("JD_BG_CW")) d->bg_cw_cap = std::max(1, atoi(e));
+    if (const char *e = jd_dev_env("JD_RES_CAP")) { const int v = atoi(e); if (v >= 16 && v <= (1 << 20)) d->res_cap = v; }   // (tests)
+}
+
+// the two HIP streams, the host-mapped "resident" word and the per-stream host state
+static int dec_create_streams(jd_dec *d)
+{
     hipError_t e;
     // the search stream has the highest priority, the scoring stream the lowest: when a table is scored while a search
     // runs (jd_dec_prefetch_scores) a search launch that needs CUs gets them before further scoring blocks do
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     if ((e = hipStreamCreateWithPriority(&d->s_gmm, hipStreamNonBlocking, prio_lo)) != hipSuccess ||
-        (e = hipStreamCreateWithPriority(&d->s_search, hipStreamNonBlocking, prio_hi)) != hipSuccess) {
-        jd_dec_destroy(d);
+        (e = hipStreamCreateWithPriority(&d->s_search, hipStreamNonBlocking, prio_hi)) != hipSuccess)
         return jd_fail(JD_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
     if ((e = hipHostMalloc((void **)&d->h_resident, 64, hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&d->d_resident, d->h_resident, 0)) != hipSuccess) {
-        jd_dec_destroy(d);
+        (e = hipHostGetDevicePointer((void **)&d->d_resident, d->h_resident, 0)) != hipSuccess)
         return jd_fail(JD_EHIP, "hipHostMalloc failed: %s", hipGetErrorString(e));
-    }
     *d->h_resident = 0;
-    d->stream_T.assign((size_t)max_streams, 0);
-    d->stream_started.assign((size_t)max_streams, 0);
-    d->stream_open.assign((size_t)max_streams, 0);
-    d->lazy_in.assign((size_t)max_streams, 0);
-    d->stream_dirty.assign((size_t)max_streams, 0);
-    d->last_collect.assign((size_t)max_streams, -1);
-    d->n_collect_host.assign((size_t)max_streams, 0);
-    d->last_trace.assign((size_t)max_streams, -1);
-    d->partial_label.resize((size_t)max_streams);
-    d->partial_time.resize((size_t)max_streams);
-    d->partial_m.resize((size_t)max_streams);
-    d->results.resize((size_t)max_streams);
-    if (const char *e = jd_dev_env("JD_RES_CAP")) { const int v = atoi(e); if (v >= 16 && v <= (1 << 20)) d->res_cap = v; }   // (tests)
-#undef TRY
+    const size_t n = (size_t)d->max_streams;
+    d->stream_T.assign(n, 0);
+    d->stream_started.assign(n, 0);
+    d->stream_open.assign(n, 0);
+    d->lazy_in.assign(n, 0);
+    d->stream_dirty.assign(n, 0);
+    d->last_collect.assign(n, -1);
+    d->n_collect_host.assign(n, 0);
+    d->last_trace.assign(n, -1);
+    d->partial_label.resize(n);
+    d->partial_time.resize(n);
+    d->partial_m.resize(n);
+    d->results.resize(n);
+    return JD_OK;
+}
+
+extern "C" int jd_dec_create(jd_dec **out, const jd_net *net, const jd_am *am, float start_beam, float main_beam,
+                             float end_beam, float word_beam, int32_t max_hyps, int32_t block_size,
+                             int32_t device, int32_t max_streams)
+{
+    PrepHist hist;
+    int rc = dec_check_args(out, net, am, main_beam, max_hyps, block_size, device, max_streams, &hist);
+    if (rc) return rc;
+    jd_dec *d = new jd_dec();
+    d->net = net; d->am = am; d->device = device; d->max_streams = max_streams; d->block_size = block_size;
+    // development: frames per chunk of a batch
+    if (const char *e = jd_dev_env("JD_FC")) { const int v = atoi(e); if (v >= 16 && v <= 65536) d->Fw_env = v; }
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) d->n_cus = prop.multiProcessorCount;
+    }
+    DecConst &C = d->C;
+    C.start_win = start_beam; C.emit_win = main_beam; C.end_win = end_beam; C.word_win = word_beam;
+    C.max_hyps = max_hyps;
+    C.x_chunks = 2;
+    if (const char *e = jd_dev_env("JD_XCH")) { const int v = atoi(e); if (v >= 1 && v <= 16) { C.x_chunks = v; d->xch_forced = true; } }   // development
+    C.exp = 0; C.path_rule = 0; C.pcount = nullptr;
+    if (const char *e = jd_dev_env("JD_EXP")) C.exp = atoi(e);                                                    // development
+    C.hist_min = hist.hist_min; C.hist_max = hist.hist_max; C.hist_nbins = hist.hist_nbins;
+    const PrepKnobs knobs = dec_prep_knobs();
+    const PrepModels M = prep_models(*am, knobs);
+    if ((rc = dec_upload_graph(d, knobs, M.tmax0)) || (rc = dec_upload_models(d, M))) { jd_dec_destroy(d); return rc; }
+    dec_fill_const(d);
+    dec_read_planner_knobs(d);
+    if ((rc = dec_create_streams(d))) { jd_dec_destroy(d); return rc; }
     *out = d;
     return JD_OK;
 }

@@ -262,49 +262,7 @@ extern "C" int jd_stream_collect_info(jd_dec *d, int32_t s, int32_t *n_collectio
 
 // setPartialDecodeOptions (WFSTDecoderLite.cpp:892-896; the reference reads PartialTraceInterval
 // from the environment, :116-119)
-// The Path objects WFSTDecoderLite::propagateToken creates behind ONE token that arrives at state q (:497-509 inside
-// the recursion of :533-541 and :583-599): one per labelled epsilon arc and per labelled arc of a tee model that leaves
-// q, plus what arrives behind each of those arcs - with multiplicity, the recursion does not recombine.  Static as
-// long as nothing prunes inside the closure, i.e. with the end and word beams off (the thresholds of :538, :591-596 are
-// LOG_ZERO then).  Saturates at 2^20 (the rule's own mark is 10000).  false: the label-less part of the graph has a
-// cycle (the reference would not come back from it).
-static bool closure_path_counts(const jd_net *net, const jd_am *am, std::vector<int> &P)
-{
-    const int nS = net->n_states;
-    P.assign((size_t)nS, -1);
-    std::vector<char> open((size_t)nS, 0);
-    std::vector<std::pair<int, int>> stack;                           // (state, next arc)
-    auto passes = [&](const JdArc &a) { return a.in == 0 || am->hmm_tee[(size_t)a.in - 1] > LZ; };
-    for (int q0 = 0; q0 < nS; ++q0) {
-        if (P[(size_t)q0] >= 0) continue;
-        stack.assign(1, std::make_pair(q0, net->row_ptr[(size_t)q0]));
-        open[(size_t)q0] = 1;
-        while (!stack.empty()) {
-            const int q = stack.back().first;
-            int &a = stack.back().second;
-            bool descended = false;
-            for (; a < net->row_ptr[(size_t)q + 1]; ++a) {
-                const JdArc &arc = net->arcs[(size_t)a];
-                if (!passes(arc) || P[(size_t)arc.to] >= 0) continue;
-                if (open[(size_t)arc.to]) return false;
-                open[(size_t)arc.to] = 1;
-                stack.push_back(std::make_pair(arc.to, net->row_ptr[(size_t)arc.to]));
-                descended = true;
-                break;
-            }
-            if (descended) continue;
-            long long sum = 0;
-            for (int b = net->row_ptr[(size_t)q]; b < net->row_ptr[(size_t)q + 1]; ++b) {
-                const JdArc &arc = net->arcs[(size_t)b];
-                if (passes(arc)) sum += (arc.out != 0 ? 1 : 0) + P[(size_t)arc.to];
-            }
-            P[(size_t)q] = (int)std::min<long long>(sum, 1 << 20);
-            open[(size_t)q] = 0;
-            stack.pop_back();
-        }
-    }
-    return true;
-}
+// (the Path counts behind one arriving token, closure_path_counts: jd_prep.h)
 
 // Diagnostics / tests (host only, no device): the per-state counts of closure_path_counts - what jd_dec_set_partial_interval puts
 // on the device for collectPaths' count trigger - into out[n_states]; *acyclic = 0 when the label-less part of the graph has
@@ -335,11 +293,7 @@ extern "C" int jd_dec_set_partial_interval(jd_dec *d, int32_t interval)
             if (rc) return rc;
             std::vector<int> P;
             if (closure_path_counts(d->net, d->am, P)) {
-                if (!d->state_new.empty()) {                           // (the kernels index it by the decoder's own state numbers)
-                    std::vector<int> Q(P.size());
-                    for (size_t q = 0; q < P.size(); ++q) Q[(size_t)d->state_new[q]] = P[q];
-                    P.swap(Q);
-                }
+                if (!d->state_new.empty()) P = permute_by_state(d->state_new, P);   // (the kernels index it by the decoder's own state numbers)
                 rc = dupload(d, &d->d_pcount, P.data(), P.size());
                 if (rc) return rc;
             }

@@ -23,12 +23,9 @@
 #ifndef JD_LAZY_H
 #define JD_LAZY_H
 
-#ifndef TEE_FLAG
-#define TEE_FLAG 0x40000000          // (jd_search.h)
-#endif
-#ifndef LZ
-#define LZ (-3.402823466e+38f)       // LOG_ZERO (jd_device.hip)
-#endif
+#include "jd_prep.h"                 // TEE_FLAG, LZ
+// Lazily composed arcs never carry SOLE_FLAG: the arcs into a state appear while the search runs, so no arc can be known to be the
+// only one (jd_prep.h: prep_arcs states the invariant the flag stands for; a decoder on a lazy network runs no graph preparation).
 
 enum { LZ_UNKNOWN = 0, LZ_EXPANDING = 1, LZ_EXPANDED = 2, LZ_CLOSED = 3 };
 #define LZ_FLAG 0x80000000u          // the composition filter's flag, in the top bit of the stored C.L state

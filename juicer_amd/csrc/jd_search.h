@@ -46,10 +46,7 @@
 #define SNT (SW * 64)                // threads per search workgroup
 #define MAXW SNT                      // most waves one cluster may have (one thread per wave when the lists are set up)
 #define MAXCW (MAXW / SW)
-#define TEE_FLAG 0x40000000          // bit 30 of the device arc's in-label: the arc's HMM is a tee model
-#define SOLE_FLAG 0x20000000         // bit 29: the arc is the ONLY arc that leads to its destination state (jd_dec_create) - see REC_SOLE
-#define ARC_FLAGS (TEE_FLAG | SOLE_FLAG)
-#define TRP_LDS_MAX 4096             // floats of transition tables cached in LDS (else read from HBM)
+#include "jd_prep.h"                 // TEE_FLAG, SOLE_FLAG, ARC_FLAGS, TRP_LDS_MAX, LZ, XState, xcand: shared with the host-side preparation
 #ifndef TEE_LDS_MAX
 #define TEE_LDS_MAX 2048             // HMMs whose tee log-probability is cached in LDS
 #endif
@@ -130,6 +127,9 @@ template <int NE> struct RecLayout {
                                      // win and reset none in phase X - an atomic, a load and a store less per exit token, each a 64-byte
                                      // sector of a state's words for 8 useful bytes.  Most states of a C.L.G are such states (the inside
                                      // of a word's chain, the nodes of a lexicon tree).  ITEM_SOLE: the same bit on the exit item.
+                                     // Set from SOLE_FLAG, whose invariant - in-degree 1 over ALL arcs of the decoder's table, no tee model - is
+                                     // stated and tested on the host side (jd_prep.h: prep_arcs); nothing on the device checks it, so whatever adds
+                                     // another way into a state (lazily composed arcs, a start token put back) must not meet a flagged arc.
 #define ITEM_SOLE 4
 
 // per-state search state, ONE 32-byte record (half a memory sector): the recombination keys of a state.
@@ -165,21 +165,7 @@ struct __align__(16) SArr { unsigned long long e[2]; };
 #define SREC_E_OFF(C, st, q) ((C).srec_arr + (unsigned)(q) * (C).srec_par + (unsigned)(st) * (C).srec_estride)
 #define SREC_BID(base, C, st) (*(GAS SBid *)((GAS char *)(base) + SREC_BID_OFF(C, st)))
 #define SREC_E(base, C, st, q) (*(GAS unsigned long long *)((GAS char *)(base) + SREC_E_OFF(C, st, q)))
-// per-state STATIC record of the decoder's own copy of the graph (shared by the streams; jd_dec_create).  The decoder keeps the
-// arcs of a state in an order of its own: first the arcs every arrival has to walk (epsilon inputs, tee models: n_always of
-// them), then the arcs that enter a model, by DESCENDING w + tmax (arc weight + the model's largest entry transition) - the
-// quantity phase X's "hopeless candidate" test runs on.  An arrival of score s can only enter the arcs of a PREFIX of that order;
-// k[] samples the order at the positions xcand() so that an item finds an upper bound of its prefix from this one record instead
-// of looking at every arc: the slot kernel (jd_slot.h: phase X) does not walk the arcs behind it at all.  What the walk did for
-// them besides is accounted from here: n_model (arcs that carry a model, tee models included) less the instance flags set in the
-// state's row (StreamDev::live: one byte per arc, a row's flags side by side) gives the arcs entered without an instance, wmax the
-// best entry-token candidate.  (k_search walks every arc, in this order, and does not read this record.)
-#define XNCAND 12
-struct __align__(64) XState { int n_always, n_entry; float wmax; int n_model; float k[XNCAND]; };
-__host__ __device__ __forceinline__ constexpr int xcand(int i)
-{
-    return i == 0 ? 0 : i == 1 ? 1 : i == 2 ? 2 : i == 3 ? 3 : i == 4 ? 4 : i == 5 ? 6 : i == 6 ? 8 : i == 7 ? 12 : i == 8 ? 16 : i == 9 ? 24 : i == 10 ? 32 : 64;
-}
+// (the per-state STATIC record of the decoder's own copy of the graph, XState, and xcand(): jd_prep.h)
 
 // per-stream scalars.  Line 0 is written by the host-side helper kernels and by workgroup 0 of the
 // stream's cluster at the END of a launch (nobody reads it while a launch runs, except at its
