@@ -349,7 +349,12 @@ int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames);
 /* IDecoder::finish() (Decoder.h:28). */
 int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out);
 /* jd_stream_push for several streams at once (each at most once per call): ONE scoring launch and ONE search launch
- * for all of them - the streams may sit at different frames.  Not with partial traces (jd_dec_set_partial_interval). */
+ * for all of them - the streams may sit at different frames.  With partial traces (jd_dec_set_partial_interval > 0) the
+ * rows are still scored once and the streams then advance in rounds: a round is one search launch that ends, stream by
+ * stream, at the frame after which the reference collects (either trigger), one collection launch and one trace launch
+ * (k_partial_many) for all the streams whose collection or trace is due - every stream's collections, traces and lists
+ * are what jd_stream_push calls with the same frames give, and the two calls may be mixed.  A stream that fails on the
+ * device is left out of the later rounds (jd_stream_finish reports it), the others go on. */
 int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, const float *const *frames, const int32_t *n_frames);
 /* max_streams / feature vector size of a decoder */
 int jd_dec_info(const jd_dec *d, int32_t *max_streams, int32_t *vec_size);
@@ -366,7 +371,8 @@ int jd_dec_info(const jd_dec *d, int32_t *max_streams, int32_t *vec_size);
  * stream at its own pace; init, the Path collections and finish are small kernels beside it.  The kernel leaves the
  * device after 3 ms without work and comes back with the next request; while it is there, other search launches on the
  * device (this process: they wait for it; other processes: the file lock) and anything that synchronises the whole
- * device wait for that.  More than 64 clients, a lazily composed network, or JD_BROKER_RESIDENT=0: a worker that turns
+ * device wait for that.  More than 64 clients, a lazily composed network, partial traces
+ * (jd_dec_set_partial_interval > 0 before jd_broker_create; jd_broker_partial), or JD_BROKER_RESIDENT=0: a worker that turns
  * what has been pushed since its last TICK into one scoring launch and one search launch over all the streams concerned
  * (jd_streams_push).  The decoder must not be used directly while a broker owns it; clients may be driven from
  * different threads, one thread per client at a time.  jd_hyp arrays stay valid until the client's next init.
@@ -415,6 +421,9 @@ int jd_broker_get_stats(jd_broker *b, jd_broker_stats *out);
  * an end or word beam, or a lazily composed network, the rule runs on this build's own records - at most
  * the reference's, so it fires no earlier - an approximation.  The schedule decides when a trace is
  * taken, never what a trace at a given frame finds.
+ * jd_streams_push keeps the same schedule for every one of its streams.  Under a broker the interval is set before
+ * jd_broker_create (the decoder is not to be used directly while a broker owns it) and the lists are read with
+ * jd_broker_partial.
  * jd_stream_collect_info: collections of the stream's utterance so far and lastPathCollectFrame.
  * jd_stream_path_counts: nPath and nPathNew as the trigger reads them, *exact = 1 when they are the reference's.
  *
@@ -434,6 +443,21 @@ int jd_stream_path_counts(jd_dec *d, int32_t s, int32_t *n_path, int32_t *n_path
 int jd_debug_closure_path_counts(const jd_net *net, const jd_am *am, int32_t *out, int32_t *acyclic);
 int jd_stream_partial(jd_dec *d, int32_t s, int32_t trace_now, int32_t cap, int32_t *n,
                       int32_t *labels, int32_t *times, int32_t *found);
+/* tracePartialPath now (:824-868) on each of the n listed streams, each at the frame it has reached: jd_stream_partial(s,
+ * trace_now = 1) for a list - ONE kernel launch (a workgroup per stream) and one fetch instead of a launch and three
+ * copies per stream.  found[i] (found may be NULL) = the return value of stream i's trace; the lists are then read with
+ * jd_stream_partial(s, 0, ...).  Each stream may be listed once (JD_EINVAL).  Word level only: JD_ESTATE on a decoder with
+ * JD_OUTPUT_MODELS, where the single-stream calls remain. */
+int jd_streams_trace(jd_dec *d, int32_t n, const int32_t *streams, int32_t *found);
+/* the interval jd_dec_set_partial_interval set (0: off) */
+int jd_dec_get_partial_interval(const jd_dec *d, int32_t *interval);
+/* The partialPaths of a broker's client as of the worker's last tick - after jd_broker_finish the complete list (the
+ * hypothesis, oldest first) - with jd_stream_partial's conventions: *n is the full length, at most cap entries are
+ * written (labels / times may be NULL).  Empty from the client's jd_broker_init on.  The schedule is the interval's
+ * (set with jd_dec_set_partial_interval BEFORE jd_broker_create; such a broker runs the tick worker,
+ * jd_broker_stats.resident = 0): there is no trace_now through a broker.  Only the worker touches the decoder; this call
+ * reads the copy it leaves with the client after every tick. */
+int jd_broker_partial(jd_broker *b, int32_t client, int32_t cap, int32_t *n, int32_t *labels, int32_t *times);
 
 /*
  * DecoderBatchTest::run() inner loop (DecoderBatchTest.cpp:738-771) for a
@@ -523,7 +547,8 @@ typedef struct jd_timing {
                                  flight": announcements two batches ahead, a batch on at most half of the streams) */
     int32_t slot_launches;    /* of search_launches: launches of the slot kernel (csrc/jd_slot.h: one workgroup per stream, two per
                                  CU - batches of more streams than the chip has CUs) */
-    int32_t pad0;
+    int32_t trace_launches;   /* partial-trace kernel launches (k_partial, k_partial_many), cumulative over the streaming calls as
+                                 search_ms is: a jd_streams_push round traces all its due streams with one */
 } jd_timing;
 int jd_dec_last_timing(const jd_dec *d, jd_timing *out);
 

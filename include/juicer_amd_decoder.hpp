@@ -441,11 +441,13 @@ public:
 class GpuDecoderPool {
 public:
     GpuDecoderPool(const jd_net *network, const jd_am *models, float phoneStartPruneWin, float emitPruneWin, float phoneEndPruneWin,
-                   float wordPruneWin, int maxEmitHyps, int nCallers, int device = 0, int blockSize = 5)
+                   float wordPruneWin, int maxEmitHyps, int nCallers, int device = 0, int blockSize = 5, int partialTraceInterval = 0)
         : dec_(0), broker_(0), vecSize_(jd_am_vec_size(models))
     {
         check(jd_dec_create(&dec_, network, models, phoneStartPruneWin, emitPruneWin, phoneEndPruneWin, wordPruneWin, maxEmitHyps, blockSize,
                             device, nCallers));
+        // PARTIAL_DECODING (setPartialDecodeOptions, WFSTDecoderLite.cpp:892-896): before the broker takes the decoder over
+        if (partialTraceInterval > 0) check(jd_dec_set_partial_interval(dec_, partialTraceInterval));
         check(jd_broker_create(&broker_, dec_, nCallers));
     }
     ~GpuDecoderPool() { jd_broker_destroy(broker_); jd_dec_destroy(dec_); }
@@ -522,6 +524,16 @@ public:
         return &hyp_;                               // valid until the next init(), like the reference
     }
     const jd_stats &statistics() const { return stats_; }
+    // PARTIAL_DECODING: the partialPaths list (WFSTDecoderLite.h:199-205) as (output label, frame) pairs, oldest first, as of the
+    // broker's last tick; after finish() the complete list.  The schedule is the pool's partialTraceInterval.
+    void partialPaths(std::vector<int> &labels, std::vector<int> &frames)
+    {
+        int n = 0;
+        GpuDecoderPool::check(jd_broker_partial(b_, client_, 0, &n, 0, 0));
+        labels.assign((size_t)n, 0); frames.assign((size_t)n, 0);
+        // (the worker may have extended the list in between: what fits is written, the list only grows within an utterance)
+        if (n > 0) { int n2 = 0; GpuDecoderPool::check(jd_broker_partial(b_, client_, n, &n2, &labels[0], &frames[0])); }
+    }
 private:
     void flush()
     {

@@ -53,7 +53,7 @@ class Timing(C.Structure):
                 ("gmm_launches", C.c_int32), ("search_launches", C.c_int32),
                 ("relaunches", C.c_int32), ("cluster_wgs", C.c_int32),
                 ("gmm_frames", C.c_int64), ("gmm_states", C.c_int64), ("search_frames", C.c_int64),
-                ("prefetched", C.c_int32), ("ahead_frames", C.c_int32), ("slot_launches", C.c_int32), ("pad0", C.c_int32)]
+                ("prefetched", C.c_int32), ("ahead_frames", C.c_int32), ("slot_launches", C.c_int32), ("trace_launches", C.c_int32)]
 
 
 FLOW_SERIAL, FLOW_TWO_IN_FLIGHT, FLOW_RESIDENT = 0, 1, 3      # jd_dec_set_pipeline
@@ -128,6 +128,7 @@ EXPORTS = [
     "jd_debug_hist_bin", "jd_debug_hist_threshold",
     "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
     "jd_am_hmm_name", "jd_stream_partial_models",
+    "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial",
 ]
 
 _lib = None
@@ -601,6 +602,19 @@ class Decoder:
     def set_partial_interval(self, interval: int):
         _check(lib().jd_dec_set_partial_interval(self.h, C.c_int32(interval)))
 
+    def get_partial_interval(self) -> int:
+        v = C.c_int32(0)
+        _check(lib().jd_dec_get_partial_interval(self.h, C.byref(v)))
+        return v.value
+
+    def streams_trace(self, streams):
+        """tracePartialPath now on each of the listed streams (each once), each at the frame it has reached: one launch and one
+        fetch for all of them (jd_streams_trace).  Returns found per stream; the lists are read with stream_partial(s)."""
+        ss = _i32(list(streams))
+        found = np.zeros(max(1, ss.shape[0]), np.int32)
+        _check(lib().jd_streams_trace(self.h, C.c_int32(ss.shape[0]), _p(ss, C.c_int32), _p(found, C.c_int32)))
+        return [bool(f) for f in found[:ss.shape[0]]]
+
     def stream_collect_info(self, s: int = 0):
         """(collectPaths runs of the stream's utterance so far, lastPathCollectFrame) - counted while PARTIAL_DECODING is on."""
         n, last = C.c_int32(0), C.c_int32(-1)
@@ -765,6 +779,18 @@ class Broker:
         h = CHyp()
         _check(lib().jd_broker_finish(self.h, C.c_int32(client), C.byref(h)))
         return _hyp_from_c(h)
+
+    def partial(self, client: int):
+        """The client's partialPaths as [(label, frame)], oldest first, as of the worker's last tick; after finish the complete
+        list (jd_broker_partial).  The interval is set on the Decoder before the Broker is made."""
+        n, cap = C.c_int32(0), 256
+        while True:
+            lab, tim = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+            _check(lib().jd_broker_partial(self.h, C.c_int32(client), C.c_int32(cap), C.byref(n), _p(lab, C.c_int32), _p(tim, C.c_int32)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        return [(int(lab[i]), int(tim[i])) for i in range(n.value)]
 
     def stats(self) -> dict:
         st = BrokerStats()

@@ -566,8 +566,11 @@ int main(int argc, char **argv)
         // (doc/userman/juicer_userman.tex:584) - through ONE decoder: a GpuWFSTPooledDecoder per thread, the broker behind
         // them (juicer_amd_decoder.hpp)
         if (lazy_cl) { fprintf(stderr, "jd_batch_test: -threads works on a composed network\n"); return 1; }
-        JuicerAmd::GpuDecoderPool pool(net, am, startBeam, mainBeam, endBeam, wordBeam, maxHyps, nThreads, device);
-        struct Res { std::vector<int32_t> lab, tim; std::vector<float> ac, lm; double dt = 0.0; };
+        // (PartialTraceInterval from the environment, as the single-decoder adapter reads it: WFSTDecoderLite.cpp:116-119)
+        const int partialInterval = getenv("PartialTraceInterval") ? atoi(getenv("PartialTraceInterval")) : 0;
+        JuicerAmd::GpuDecoderPool pool(net, am, startBeam, mainBeam, endBeam, wordBeam, maxHyps, nThreads, device, 5,
+                                       partialInterval > 0 ? partialInterval : 0);
+        struct Res { std::vector<int32_t> lab, tim; std::vector<float> ac, lm; double dt = 0.0; std::vector<int> pframes; };
         std::vector<Res> res(files.size());
         std::vector<std::thread> th;
         const auto t_all = std::chrono::steady_clock::now();
@@ -587,6 +590,7 @@ int main(int argc, char **argv)
                     }
                     JuicerAmd::DecHyp *hyp = dec.finish();
                     Res &r = res[u];
+                    if (partialInterval > 0) { std::vector<int> pl; dec.partialPaths(pl, r.pframes); }   // WFSTDecoderLite.cpp:245-258
                     for (JuicerAmd::DecHypHist *h = hyp ? hyp->hist : 0; h; h = h->prev) {
                         r.lab.push_back(h->state); r.tim.push_back(h->time); r.ac.push_back(h->acousticScore); r.lm.push_back(h->lmScore);
                     }
@@ -599,6 +603,11 @@ int main(int argc, char **argv)
             long tot = 0;
             for (size_t u = 0; u < files.size(); ++u) tot += nfr[u];
             fprintf(stderr, "%d harness threads: %ld frames in %.3f s = %.0f frames/s\n", nThreads, tot, wall, wall > 0 ? tot / wall : 0.0);
+        }
+        for (size_t u = 0; u < files.size() && partialInterval > 0; ++u) {   // (in list order, like the results)
+            fprintf(stderr, "Partial paths recovered at frames: ");
+            for (size_t k = 0; k < res[u].pframes.size(); ++k) fprintf(stderr, "%03d ", res[u].pframes[k]);
+            fprintf(stderr, "\n");
         }
         for (size_t u = 0; u < files.size(); ++u)
             print_utt(u, (int)res[u].lab.size(), res[u].lab.data(), res[u].tim.data(), res[u].ac.data(), res[u].lm.data(), res[u].dt);

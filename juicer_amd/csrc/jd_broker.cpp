@@ -9,7 +9,9 @@
 // client with the IDecoder protocol - init, push (processFrame x n), finish - and a worker thread turns whatever has
 // been pushed since its last tick into ONE scoring launch and ONE persistent search launch over all the streams
 // concerned (jd_streams_push).  Clients never touch the decoder: only the worker thread does, so the decoder's
-// single-caller rule holds.  Host code over the C ABI only - nothing here knows about HIP.
+// single-caller rule holds.  PARTIAL_DECODING (an interval set on the decoder before jd_broker_create): the tick worker, whose
+// jd_streams_push keeps every stream's trace schedule, leaves each client's partialPaths with the client after every tick
+// (jd_broker_partial).  Host code over the C ABI only - nothing here knows about HIP.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -46,6 +48,7 @@ struct Client {
     std::chrono::steady_clock::time_point t_post, t_idle;   // (statistics) its last command posted / found through
     bool was_idle = false;
     std::vector<float> taken;                      // frames on their way into a likelihood buffer
+    std::vector<int32_t> plabel, ptime;            // its partialPaths as of the worker's last tick (jd_broker_partial; PARTIAL_DECODING)
 };
 }  // namespace
 
@@ -61,6 +64,7 @@ struct jd_broker {
     bool stop = false;
     std::vector<Client> clients;
     jd_broker_stats stats{};
+    int partial_interval = 0;                      // the decoder's, as jd_broker_create found it: > 0, the worker keeps the clients' lists
     bool resident = false;                         // the worker drives the resident search kernel (jd_res_*) instead of ticks
     int fail_init_of = -1;                         // test hook (JD_DEV=1 JD_BROKER_FAIL_INIT=<client>): that client's inits fail
     // results are fetched by a thread of their own: recognitionFinish's kernel, a synchronisation of the side stream and
@@ -204,8 +208,29 @@ static void broker_loop(jd_broker *b)
             serve_finishes(late);
             finishers.insert(finishers.end(), late.begin(), late.end());
         }
+        // PARTIAL_DECODING: the lists of the clients this tick concerned, copied where jd_broker_partial finds them
+        std::vector<int> listed;
+        std::vector<std::vector<int32_t>> pl, pt;
+        if (b->partial_interval > 0) {
+            for (int i : pushers) if (rc_of[(size_t)i] == JD_OK) listed.push_back(i);
+            for (int i : finishers) if (std::find(listed.begin(), listed.end(), i) == listed.end()) listed.push_back(i);
+            pl.resize(listed.size()); pt.resize(listed.size());
+            for (size_t k = 0; k < listed.size(); ++k) {
+                int32_t np = 0;
+                if (jd_stream_partial(b->dec, listed[k], 0, 0, &np, nullptr, nullptr, nullptr) != JD_OK || np == 0) continue;
+                pl[k].resize((size_t)np); pt[k].resize((size_t)np);
+                (void)jd_stream_partial(b->dec, listed[k], 0, np, &np, pl[k].data(), pt[k].data(), nullptr);
+            }
+        }
         us_finish = us_since(t_mark);
         lk.lock();
+        for (size_t k = 0; k < listed.size(); ++k) {
+            Client &c = b->clients[(size_t)listed[k]];
+            // (an init() that came while the tick ran: the lists are of the utterance it dropped)
+            if (c.want_init && c.init_req != init_seen[(size_t)listed[k]]) continue;
+            if (c.want_init && std::find(inits.begin(), inits.end(), listed[k]) == inits.end()) continue;
+            c.plabel.swap(pl[k]); c.ptime.swap(pt[k]);
+        }
         b->stats.us_init += us_init; b->stats.us_push += us_push; b->stats.us_finish += us_finish;
         b->stats.us_search += us_search;
         if (tick_streams) { b->stats.ticks += 1; b->stats.frames += tick_frames; b->stats.stream_ticks += tick_streams; }
@@ -455,8 +480,10 @@ extern "C" int jd_broker_create(jd_broker **out, jd_dec *dec, int32_t n_clients)
     if (const char *e = jd_dev_env("JD_BROKER_TICK_FRAMES")) { const int v = atoi(e); if (v >= 1 && v <= 65536) b->max_tick_frames = v; }
     if (const char *e = jd_dev_env("JD_BROKER_COALESCE_US")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) b->coalesce_us = v; }
     b->max_pending_frames = 4 * b->max_tick_frames;
+    rc = jd_dec_get_partial_interval(dec, &b->partial_interval);
+    if (rc) { delete b; return rc; }
     // the resident search kernel instead of ticks (JD_BROKER_RESIDENT=0: ticks): not with a lazily composed network or
-    // partial traces - jd_res_start says so and the clients' first calls would fail, so those decoders keep the ticks
+    // partial traces (b->partial_interval > 0) - jd_res_start says so and the clients' first calls would fail, so those decoders keep the ticks
     // (up to 64 clients: the ready list of a scoring launch and the chip's room for clusters and their scoring side by side)
     b->resident = n_clients <= 64;
     if (const char *e = jd_dev_env("JD_BROKER_RESIDENT")) b->resident = atoi(e) != 0;
@@ -517,6 +544,7 @@ extern "C" int jd_broker_init(jd_broker *b, int32_t client)
     c.pending.clear(); c.want_finish = false; c.err = JD_OK; c.failed = false;   // (init() in the middle of an utterance drops it, as the reference does)
     c.want_init = true;
     c.init_req += 1;
+    c.plabel.clear(); c.ptime.clear();
     // nobody waits for the worker here: the stream is initialised at the head of the next tick, in front of whatever
     // frames this client has pushed by then (an error of it comes back with the next call)
     b->cv_work.notify_all();
@@ -556,6 +584,20 @@ extern "C" int jd_broker_finish(jd_broker *b, int32_t client, jd_hyp *out)
     const int rc = client_error(b, c);
     if (rc) return rc;
     *out = c.result;
+    return JD_OK;
+}
+
+extern "C" int jd_broker_partial(jd_broker *b, int32_t client, int32_t cap, int32_t *n, int32_t *labels, int32_t *times)
+{
+    if (!b || client < 0 || client >= b->n_clients || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_broker_partial: bad argument");
+    std::lock_guard<std::mutex> lk(b->mu);
+    const Client &c = b->clients[(size_t)client];
+    if (!c.open) return jd_fail(JD_ESTATE, "jd_broker_partial: client %d is not open", client);
+    *n = (int32_t)c.plabel.size();
+    for (int k = 0; k < std::min<int>(cap, *n); ++k) {
+        if (labels) labels[k] = c.plabel[(size_t)k];
+        if (times) times[k] = c.ptime[(size_t)k];
+    }
     return JD_OK;
 }
 

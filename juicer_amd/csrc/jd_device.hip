@@ -315,6 +315,9 @@ struct jd_dec {
     std::vector<int> n_collect_host;           // collections of the stream's utterance so far (jd_stream_collect_info)
     std::vector<std::vector<int32_t>> partial_label, partial_time;   // partialPaths, oldest first
     int *d_partial_out = nullptr;
+    // ... k_partial_many's buffers (trace_partial_many): [int4 work list][{found, n} heads][staging], for max_streams entries, on the
+    // device and pinned on the host
+    int *d_pmany = nullptr, *h_pmany = nullptr;
     // ... the model-level list of the same traces (jd_stream_partial_models), oldest first, and k_partial's export of it,
     // [model, label, time, score, ac, lm][res_cap] (model-level output only, allocated with d_res_model)
     struct PartialModels { std::vector<int32_t> model, label, time; std::vector<float> score, ac, lm; };
@@ -402,6 +405,7 @@ extern "C" void jd_dec_destroy(jd_dec *d)
     if (d->h_resident) (void)hipHostFree(d->h_resident);
     if (d->d_push) (void)hipFree(d->d_push);
     if (d->h_stage) (void)hipHostFree(d->h_stage);
+    if (d->h_pmany) (void)hipHostFree(d->h_pmany);
     if (d->d_work) (void)hipFree(d->d_work);
     if (d->h_status) (void)hipHostFree(d->h_status);
     if (d->s_gmm) (void)hipStreamDestroy(d->s_gmm);

@@ -350,16 +350,17 @@ __device__ __forceinline__ void jd_for_each_tip(const DecConst &C, const StreamC
 // pm (model-level output, else null): the model-level export of the same trace, [model, label, time, score, ac, lm][res_cap] -
 // every record of the chain from the found word record down to the root, oldest first; out[2] = their count (> res_cap: not
 // written, the host fails the trace)
+// The trace of ONE stream by one 1024-thread workgroup (k_partial, k_partial_many).  Returns the records on the chain from the root to
+// the found one, 0 when none is found - the same value in every thread: every early return depends on the stream's own state and on
+// shared words read behind a barrier only, so the workgroup leaves together (there are barriers behind the returns).
 template <int NE>
-__global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, StreamDev *streams, int s, int last_frame, int *out, int *pm)
+__device__ __forceinline__ int jd_partial_trace(const DecConst &C, const StreamCtl &c, const StreamDev &S, int last_frame, int *out, int *pm)
 {
-    StreamCtl &c = ctl[s];
-    StreamDev &S = streams[s];
     __shared__ int sh_max, sh_bad, sh_cnt, sh_depth, sh_D, sh_nm;
     const int tid = threadIdx.x;
     if (tid == 0) { sh_max = -1; sh_bad = 0; sh_cnt = 0; sh_depth = 0; sh_D = 0; out[0] = 0; out[1] = 0; }
     __syncthreads();
-    if (!c.started || c.needs_init || c.error != 0 || c.lst_nw <= 0) return;
+    if (!c.started || c.needs_init || c.error != 0 || c.lst_nw <= 0) return 0;
     // (model-level output writes records without a word label as well: the trace is of the WORD records - a tip stands for
     // its newest labelled record, a record for its labelled predecessor.  Word mode has no other records.)
     auto word_rec = [&](int q) { while (q >= 0 && S.paths[q].label == 0) q = S.paths[q].prev; return q; };
@@ -372,7 +373,7 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     }
     __syncthreads();
     // an instance none of whose tokens has a Path yet: nothing can be common to all (:850-854)
-    if (sh_cnt == 0 || sh_bad || sh_max < 0) return;
+    if (sh_cnt == 0 || sh_bad || sh_max < 0) return 0;
     int *ch = S.gc_idx;                                                // the chain of the highest tip, newest first
     if (tid == 0) {
         int n = 0;
@@ -397,8 +398,8 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
     }
     __syncthreads();
     const int D0 = sh_D;
-    if (D0 >= depth) return;                                           // no record is common to all
-    if (S.paths[ch[D0]].frame <= last_frame) return;                   // nothing newer than the last traced record (:858)
+    if (D0 >= depth) return 0;                                         // no record is common to all
+    if (S.paths[ch[D0]].frame <= last_frame) return 0;                 // nothing newer than the last traced record (:858)
     const int n = depth - D0;
     for (int k = tid; k < n && k < S.res_cap; k += blockDim.x) {       // traceWinningPaths :874-890, oldest first
         const PathRec pr = S.paths[ch[depth - 1 - k]];
@@ -427,6 +428,41 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
             }
     }
     if (tid == 0) { out[0] = 1; out[1] = n; }
+    return n;
+}
+
+template <int NE>
+__global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, StreamDev *streams, int s, int last_frame, int *out, int *pm)
+{
+    (void)jd_partial_trace<NE>(C, ctl[s], streams[s], last_frame, out, pm);
+}
+
+// ... and of the streams of a work list, one workgroup each: work[i] = {stream, last_frame (the frame of the last record the host
+// has of it, -1: none), have (the records the host has), -}, out[2 i] = {found, n} as k_partial's out[0..1].  The chain goes into the
+// stream's own res_label / res_time and the chain scratch is the stream's own gc_idx: the workgroups share nothing.  Word level only
+// (no model-level export).
+// A trace's list extends the list of the trace before it, so only the records [have, n) are new to the host: they are written, as
+// (label, frame) pairs, into entry i's share of the staging area behind the n_work {found, n} pairs as well - out[2 n_work +
+// 2 PARTIAL_SHARE i ...] - and the host fetches the heads and the staging area of a launch in ONE copy.  PARTIAL_SHARE pairs per
+// entry: a trace follows the one before it by a trace interval, a few hundred frames at most in live use, and a word takes a few
+// frames at least, so 32 new words per trace is more than live speech gives (130 words a copy for a 16-caller tick: 8 KiB); a
+// stream with more (a first explicit trace late in a long utterance) is fetched from its result arrays instead.
+#define PARTIAL_SHARE 32
+template <int NE>
+__global__ __launch_bounds__(1024) void k_partial_many(DecConst C, StreamCtl *ctl, StreamDev *streams, const int4 *work, int n_work, int *out)
+{
+    const int i = blockIdx.x;
+    if (i >= n_work) return;                                           // (uniform)
+    const int4 w = work[i];
+    const StreamDev &S = streams[w.x];
+    const int n = jd_partial_trace<NE>(C, ctl[w.x], S, w.y, out + 2 * i, nullptr);
+    const int have = w.z;
+    if (n <= have || n - have > PARTIAL_SHARE || n > S.res_cap) return;
+    __syncthreads();                                                   // (n is the same in every thread) the chain is in res_label / res_time
+    int *stage = out + 2 * (size_t)n_work + 2 * (size_t)PARTIAL_SHARE * i;
+    for (int k = have + (int)threadIdx.x; k < n; k += blockDim.x) {
+        stage[2 * (k - have)] = S.res_label[k]; stage[2 * (k - have) + 1] = S.res_time[k];
+    }
 }
 
 // recognitionFinish (:230-309): walk the Path chain of bestFinalToken.  res_model (model-level output, else null): the records'

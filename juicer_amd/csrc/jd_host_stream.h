@@ -1,6 +1,7 @@
 // jd_host_stream.h - the IDecoder seam of the C ABI (included by jd_device.hip): jd_stream_init / _push / _finish (IDecoder::init /
 // processFrame / finish, src/Decoder.h:18-30, src/WFSTDecoderLite.cpp:139-372), jd_streams_push (several callers' frames in one launch),
-// PARTIAL_DECODING (jd_dec_set_partial_interval, jd_stream_partial: src/WFSTDecoderLite.cpp:822-896) and the collection bookkeeping.
+// PARTIAL_DECODING (jd_dec_set_partial_interval, jd_stream_partial, jd_streams_trace: src/WFSTDecoderLite.cpp:822-896) for one stream
+// and for a list of them, and the collection bookkeeping.
 #pragma once
 
 extern "C" int jd_stream_init(jd_dec *d, int32_t s)
@@ -51,6 +52,7 @@ static int trace_partial(jd_dec *d, int s, int *found)
         hipLaunchKernelGGL(k_partial<3>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out, pm);
     else hipLaunchKernelGGL(k_partial<6>, dim3(1), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, s, last_frame, d->d_partial_out, pm);
     HIPCHK(hipGetLastError());
+    d->timing.trace_launches += 1;
     int ho[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(ho, d->d_partial_out, (pm ? 3 : 2) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -77,6 +79,58 @@ static int trace_partial(jd_dec *d, int s, int *found)
         P.score.assign(f + 3 * nm, f + 4 * nm); P.ac.assign(f + 4 * nm, f + 5 * nm); P.lm.assign(f + 5 * nm, f + 6 * nm);
     }
     return JD_OK;
+}
+
+// trace_partial for a list of streams (each once; word level), each at the frame it has reached: ONE k_partial_many launch and ONE
+// copy back - the {found, n} heads and, behind them, the records that are new to the host (k_partial_many, jd_gc.h).  found
+// (or null): per entry.  A stream whose trace fails (a chain longer than the result capacity) does not keep the others from
+// theirs; the first such error is returned.
+static int trace_partial_many(jd_dec *d, const std::vector<int> &ss, int32_t *found)
+{
+    const int n = (int)ss.size();
+    if (n == 0) return JD_OK;
+    const size_t M = (size_t)d->max_streams, head_at = 4 * M, per = 2 + 2 * (size_t)PARTIAL_SHARE, words = head_at + per * M;
+    if (!d->d_pmany) { int rc = dmalloc(d, &d->d_pmany, words); if (rc) return rc; }
+    if (!d->h_pmany) HIPCHK(hipHostMalloc((void **)&d->h_pmany, words * sizeof(int)));
+    int4 *hw = (int4 *)d->h_pmany;
+    for (int i = 0; i < n; ++i) {
+        const std::vector<int32_t> &L = d->partial_label[(size_t)ss[(size_t)i]], &Tm = d->partial_time[(size_t)ss[(size_t)i]];
+        hw[i] = make_int4(ss[(size_t)i], Tm.empty() ? -1 : Tm.back(), (int)L.size(), 0);
+    }
+    hipStream_t st = d->s_search;
+    int *d_out = d->d_pmany + head_at, *ho = d->h_pmany + head_at;
+    HIPCHK(hipMemcpyAsync(d->d_pmany, hw, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
+    if (d->am->max_n <= 5)
+        hipLaunchKernelGGL(k_partial_many<3>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmany, n, d_out);
+    else hipLaunchKernelGGL(k_partial_many<6>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmany, n, d_out);
+    HIPCHK(hipGetLastError());
+    d->timing.trace_launches += 1;
+    HIPCHK(hipMemcpyAsync(ho, d_out, per * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int rc_all = JD_OK;
+    for (int i = 0; i < n; ++i) {
+        const int s = ss[(size_t)i], fnd = ho[2 * i], len = ho[2 * i + 1];
+        d->last_trace[(size_t)s] = d->stream_T[(size_t)s] - 1;        // :867
+        if (found) found[i] = fnd;
+        if (!fnd) continue;
+        if (len > d->res_cap) {
+            const int rc = jd_fail(JD_ENOMEM, "stream %d: partial path has %d records (> %d)", s, len, d->res_cap);
+            if (!rc_all) rc_all = rc;
+            continue;
+        }
+        std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
+        const int have = (int)L.size();
+        L.resize((size_t)len); Tm.resize((size_t)len);
+        if (len - have <= PARTIAL_SHARE) {                             // (the records traced before are the chain's prefix)
+            const int *stage = ho + 2 * (size_t)n + 2 * (size_t)PARTIAL_SHARE * i;
+            for (int k = have; k < len; ++k) { L[(size_t)k] = stage[2 * (k - have)]; Tm[(size_t)k] = stage[2 * (k - have) + 1]; }
+        } else {                                                       // more than its share of the staging area: from its result arrays
+            const int *base = d->d_res + (size_t)s * 5 * d->res_cap;
+            HIPCHK(hipMemcpy(L.data(), base, (size_t)len * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(Tm.data(), base + d->res_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return rc_all;
 }
 
 extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames)
@@ -170,11 +224,100 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
 // many IDecoder instances (jd_broker_*, jd_broker.cpp) makes of the pushes that have arrived since its last tick.
 // A call takes any number of frames per stream (the tables are sized for the call).  The streams may sit at
 // different frames: row r of the common table is frame stream_T[s] + (r - first row of s) of stream s.
-// PARTIAL_DECODING rides on single-stream pushes (its traces are taken between launches): not here.
+// PARTIAL_DECODING (jd_dec_set_partial_interval > 0): the rows are scored once and the streams advance in ROUNDS, in each of which
+// every stream is served as jd_stream_push's loop serves its one - streams_push_rounds.
+
+// The search of a jd_streams_push call under PARTIAL_DECODING.  work_all: {stream, likelihood slot} of the streams that brought
+// frames, target: the frame each is to reach.  A round is ONE launch_search that comes back after a collection, one copy of the
+// control blocks, at most one launch_gc (the streams whose frame or count rule fires behind their last frame of the round) and at
+// most one k_partial_many launch (the streams that collected and whose trace is due); a stream's frame limit for the round is
+// the frame rule's frame, so a round is to the stream what a chunk is to jd_stream_push.
+static int streams_push_rounds(jd_dec *d, const std::vector<int2> &work_all, const std::vector<int> &target, hipStream_t st)
+{
+    const bool ne3 = d->am->max_n <= 5, ref = d->C.pcount != nullptr;
+    const long long G = d->am->n_gmm;
+    const size_t nw = work_all.size();
+    std::vector<int> hT((size_t)d->max_streams), limit(nw, 0), gc_list, tr_list;
+    std::vector<char> out(nw, 0);                                      // failed in this call: left out of the later rounds
+    std::vector<size_t> act;
+    std::vector<int2> work;
+    std::vector<double> weight;
+    std::vector<StreamCtl> hc;
+    std::vector<int4> gw;
+    for (;;) {
+        act.clear(); work.clear(); weight.clear();
+        int f_end = 0, s_lo = d->max_streams, s_hi = -1;
+        for (int s = 0; s < d->max_streams; ++s) hT[(size_t)s] = d->stream_T[(size_t)s];
+        for (size_t k = 0; k < nw; ++k) {
+            const int s = work_all[k].x, at = d->stream_T[(size_t)s];
+            if (out[k] || at >= target[k]) continue;
+            // the chunk ends at the frame rule's frame: the first frame f with f - lastPathCollectFrame > 100
+            limit[k] = std::min(target[k], std::max(at + 1, d->last_collect[(size_t)s] + 102));
+            hT[(size_t)s] = limit[k];
+            act.push_back(k); work.push_back(work_all[k]); weight.push_back((double)(limit[k] - at));
+            f_end = std::max(f_end, limit[k]); s_lo = std::min(s_lo, s); s_hi = std::max(s_hi, s);
+        }
+        if (act.empty()) break;
+        HIPCHK(hipMemcpyAsync(d->d_T, hT.data(), hT.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(jd_set_T_kernel, dim3((d->max_streams + 63) / 64), dim3(64), 0, st, d->d_ctl, 0, d->max_streams, d->d_T);
+        HIPCHK(hipGetLastError());
+        // (no re-planning cuts under way: a stream cut short stops at a frame of the launch's choosing, and a rule that fires behind
+        // exactly that frame would go unseen - the kernel looks before every frame of a launch but its first, the host behind a
+        // stream's last frame of the round only)
+        const int rebalance = d->rebalance;
+        d->rebalance = 0; d->return_on_collect = true; d->collected_now = false;
+        int rc = launch_search(d, work, d->d_ll[0], G, 0, f_end, st, &weight);
+        d->rebalance = rebalance; d->return_on_collect = false;
+        if (rc) { (void)hipStreamSynchronize(st); for (const int2 &w : work) d->stream_dirty[(size_t)w.x] = 1; return rc; }
+        hc.resize((size_t)(s_hi - s_lo + 1));
+        HIPCHK(hipMemcpy(hc.data(), d->d_ctl + s_lo, hc.size() * sizeof(StreamCtl), hipMemcpyDeviceToHost));
+        gc_list.clear(); tr_list.clear();
+        std::vector<char> collected(act.size(), 0);
+        for (size_t a = 0; a < act.size(); ++a) {
+            const size_t k = act[a];
+            const int s = work_all[k].x;
+            const StreamCtl &c = hc[(size_t)(s - s_lo)];
+            if (c.error != 0) { d->stream_T[(size_t)s] = target[k]; d->stream_dirty[(size_t)s] = 1; out[k] = 1; continue; }   // (reported by jd_stream_finish)
+            const int at = c.frame - 1;                                // the last frame processed
+            // whether a collection of the reference's ran on THIS stream: its own count (k_gc_remap counts the reference's
+            // collections where the decoder keeps the reference's counts - one that only the arena asked for is none of
+            // them and carries no trace - and every collection where it does not)
+            collected[a] = c.n_collect > d->n_collect_host[(size_t)s];
+            if (!collected[a] && c.frame >= limit[k] && (at - d->last_collect[(size_t)s] > 100 ||
+                                                         path_rule_fires(ref ? c.n_paths_ref : c.n_paths, ref ? c.path_new_ref : c.path_new))) {
+                gc_list.push_back(s);                                  // the rule fires behind the round's last frame
+                collected[a] = 1;
+            }
+            d->stream_T[(size_t)s] = c.frame;
+        }
+        if (!gc_list.empty()) {
+            rc = ensure_work_cap(d, (int)gc_list.size());
+            if (rc) return rc;
+            gw.clear();
+            for (int s : gc_list) gw.push_back(make_int4(s, 0, 0, 0));
+            HIPCHK(hipMemcpyAsync(d->d_work, gw.data(), gw.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+            DecConst Cg = d->C;
+            Cg.gc_threshold = -1;                                      // (every listed stream collects)
+            launch_gc(Cg, d->d_ctl, d->d_streams, d->d_work, (int)gw.size(), 0, ne3, d->n_cus, st);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        for (size_t a = 0; a < act.size(); ++a) {
+            if (!collected[a]) continue;
+            const int s = work_all[act[a]].x, at = d->stream_T[(size_t)s] - 1;
+            d->last_collect[(size_t)s] = at;                           // :746
+            d->n_collect_host[(size_t)s] += 1;
+            if (at - d->last_trace[(size_t)s] > d->partial_interval) tr_list.push_back(s);
+        }
+        rc = trace_partial_many(d, tr_list, nullptr);
+        if (rc) return rc;
+    }
+    return JD_OK;
+}
+
 extern "C" int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, const float *const *frames, const int32_t *n_frames)
 {
     if (!d || n < 0 || (n > 0 && (!streams || !frames || !n_frames))) return jd_fail(JD_EINVAL, "jd_streams_push: bad argument");
-    if (d->partial_interval > 0) return jd_fail(JD_ESTATE, "jd_streams_push: partial traces ride on jd_stream_push");
     int rc = check_device(d->device);
     if (rc) return rc;
     const int D = d->am->D, G = d->am->n_gmm;
@@ -241,9 +384,44 @@ extern "C" int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, con
     HIPCHK(hipGetLastError());
     rc = launch_gmm(d->am, d->amb, d->d_push, d->d_row_src[0], (int)rows, d->d_ll[0], st);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }             // (the staging buffer is the next call's too)
+    if (d->partial_interval > 0) {
+        std::vector<int> target;
+        for (int i = 0; i < n; ++i) if (n_frames[i] > 0) target.push_back(Tnew[(size_t)i]);
+        return streams_push_rounds(d, work, target, st);
+    }
     rc = launch_search(d, work, d->d_ll[0], (long long)G, 0, f_end, st, &weight);
     if (rc) { (void)hipStreamSynchronize(st); for (const int2 &w : work) d->stream_dirty[(size_t)w.x] = 1; return rc; }
     for (int i = 0; i < n; ++i) if (n_frames[i] > 0) d->stream_T[(size_t)streams[i]] = Tnew[(size_t)i];
+    return JD_OK;
+}
+
+// tracePartialPath now on each of the listed streams (jd_stream_partial with trace_now, for a list): one launch, one fetch
+extern "C" int jd_streams_trace(jd_dec *d, int32_t n, const int32_t *streams, int32_t *found)
+{
+    if (!d || n < 0 || (n > 0 && !streams)) return jd_fail(JD_EINVAL, "jd_streams_trace: bad argument");
+    if (d->models) return jd_fail(JD_ESTATE, "jd_streams_trace: word level only (model-level output: jd_stream_partial / jd_stream_partial_models)");
+    std::vector<char> seen((size_t)d->max_streams, 0);
+    std::vector<int> ss, at;
+    for (int i = 0; i < n; ++i) {
+        const int s = streams[i];
+        if (s < 0 || s >= d->max_streams || seen[(size_t)s]) return jd_fail(JD_EINVAL, "jd_streams_trace: bad stream %d (each stream once)", s);
+        if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_streams_trace before jd_stream_init (stream %d)", s);
+        seen[(size_t)s] = 1;
+        if (found) found[i] = 0;
+        if (d->stream_T[(size_t)s] > 0) { ss.push_back(s); at.push_back(i); }   // (nothing to trace before the first frame, as jd_stream_partial)
+    }
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    std::vector<int32_t> fnd(ss.size(), 0);
+    rc = trace_partial_many(d, ss, fnd.data());
+    if (found) for (size_t k = 0; k < ss.size(); ++k) found[at[k]] = fnd[k];
+    return rc;
+}
+
+extern "C" int jd_dec_get_partial_interval(const jd_dec *d, int32_t *interval)
+{
+    if (!d || !interval) return jd_fail(JD_EINVAL, "jd_dec_get_partial_interval: null argument");
+    *interval = d->partial_interval;
     return JD_OK;
 }
 
