@@ -704,6 +704,35 @@ int jd_debug_expf(int32_t device, const float *x, int64_t n, float *out);
  * JD_SCORE_FAST kernel's (device only).  tests/test_logadd.py compares them with the host libm and the CPU oracle. */
 int jd_debug_log1pe(int32_t device, int32_t variant, const float *d, int64_t n, double *out);
 int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const float *y, int64_t n, float *out);
+/* ... and of the scoring kernels' tile loops: launch_gmm (csrc/jd_host_scoring.h) called once with the caller's own arguments, the
+ * way the decoder's paths call it - the batch path with a packed row map and skip_unused, the resident side with a tile list - and
+ * not only the way jd_am_score_frames does.  frames: n_frames x D.  row_src[r] in [-1, n_frames): the frame row r of the table is
+ * scored from, -1 = unused.  skip_unused: a tile whose first row is unused is not scored.  max_blocks > 0 bounds the grid.
+ * used_row_tiles >= 0 stands for the row tiles in the choice between the kernels of 16 and of 64 tied states per tile.  rt_base
+ * (n_rt first rows) or NULL (n_rt = 0): score the 128-row tiles that begin at these rows only.  out: (guard_rows + n_rows +
+ * guard_rows) x n_gmm floats, PREFILLED by the caller; it goes to the device as it is, the table is written behind the first
+ * guard_rows rows, and the whole buffer comes back - whatever the launch did not write still holds the prefill.  *kernel = the
+ * kernel launch_gmm chose (jd_score_kernel), *grid = its workgroups (either may be NULL).
+ * Refused with JD_EINVAL before anything is launched: a row_src entry outside [-1, n_frames); with skip_unused, a scored tile
+ * whose used rows are not a prefix of it (the kernels let the tile's first row decide); a list entry outside [0, n_rows); listed
+ * tiles that overlap; a tile list for hybrid models (launch_gmm would ignore it); and, launch_gmm's own refusal, a tile list for exact
+ * scoring of D != 39.  Tile rows: 128 at D = 39
+ * and with JD_SCORE_FAST, 64 for exact scoring of any other D, none for hybrid models (which ignore skip_unused).
+ * tests/test_gpu_score_rows.py holds every cell of the buffer to tests/score_rows_cases.py. */
+typedef enum jd_score_kernel {
+    JD_KERNEL_NONE = 0,            /* nothing was launched                                  */
+    JD_KERNEL_GMM_GENERIC = 1,     /* jd_gmm_kernel<0>: exact, D != 39, 64-row tiles        */
+    JD_KERNEL_GMM39_16 = 2,        /* jd_gmm_kernel39<16>                                   */
+    JD_KERNEL_GMM39_64 = 3,        /* jd_gmm_kernel39<64>                                   */
+    JD_KERNEL_GMM_FAST39_16 = 4,   /* jd_gmm_fast39<16>                                     */
+    JD_KERNEL_GMM_FAST39_64 = 5,   /* jd_gmm_fast39<64>                                     */
+    JD_KERNEL_GMM_FAST_16 = 6,     /* jd_gmm_fast<16>                                       */
+    JD_KERNEL_GMM_FAST_64 = 7,     /* jd_gmm_fast<64>                                       */
+    JD_KERNEL_HYBRID = 8           /* jd_hybrid_kernel                                      */
+} jd_score_kernel;
+int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                        int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
+                        int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid);
 /* ... and of the histogram pruning (Histogram.cpp:64-100 / 134-158).  jd_debug_hist_bin: the search kernels' bin of s[i]
  * (jd_hist_bin: s rounded half away from zero in double, minus hist_min), -1 when it falls below hist_min, JD_EHIST above
  * hist_max; device -1 runs the host twin; every s[i] must lie in (-2^31, 2^31) (no NaN, no infinity: JD_EINVAL).  jd_debug_hist_threshold: the kernels' one-wave calcThresh (hist_threshold) for

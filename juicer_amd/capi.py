@@ -128,7 +128,7 @@ EXPORTS = [
     "jd_debug_hist_bin", "jd_debug_hist_threshold",
     "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
     "jd_am_hmm_name", "jd_stream_partial_models",
-    "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial",
+    "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial", "jd_debug_score_rows",
 ]
 
 _lib = None
@@ -507,6 +507,33 @@ def debug_log1pe(d, variant: int, device: int = -1):
     _check(lib().jd_debug_log1pe(C.c_int32(device), C.c_int32(variant), _p(d, C.c_float), C.c_int64(d.shape[0]),
                                  _p(out, C.c_double)))
     return out
+
+
+# jd_debug_score_rows: the kernel launch_gmm chose (jd_score_kernel)
+(KERNEL_NONE, KERNEL_GMM_GENERIC, KERNEL_GMM39_16, KERNEL_GMM39_64, KERNEL_GMM_FAST39_16, KERNEL_GMM_FAST39_64, KERNEL_GMM_FAST_16,
+ KERNEL_GMM_FAST_64, KERNEL_HYBRID) = range(9)
+KERNEL_NAMES = ["none", "jd_gmm_kernel<0>", "jd_gmm_kernel39<16>", "jd_gmm_kernel39<64>", "jd_gmm_fast39<16>", "jd_gmm_fast39<64>",
+                "jd_gmm_fast<16>", "jd_gmm_fast<64>", "jd_hybrid_kernel"]
+
+
+def debug_score_rows(models: "Models", frames, row_src, out, mode: int = SCORE_EXACT, skip_unused: int = 0, max_blocks: int = 0,
+                     used_row_tiles: int = -1, rt_base=None, guard_rows: int = 0, device: int = 0):
+    """One launch of the scoring kernels with the decoder's own launch arguments (jd_debug_score_rows): out is the caller's
+    PREFILLED [(guard_rows + n_rows + guard_rows), n_gmm] buffer.  Returns (the buffer as the launch left it - a copy -, the
+    kernel that ran (KERNEL_*), its grid)."""
+    x, src = _f32(frames), _i32(row_src)
+    buf = np.array(out, dtype=np.float32, order="C", copy=True)
+    n_rows = src.shape[0]
+    assert x.ndim == 2 and src.ndim == 1 and buf.shape == (n_rows + 2 * guard_rows, models.n_gmms)
+    assert x.shape[0] == 0 or x.shape[1] == models.vec_size
+    lst = None if rt_base is None else _i32(rt_base)
+    k, g = C.c_int32(0), C.c_int32(0)
+    _check(lib().jd_debug_score_rows(models.h, C.c_int32(device), C.c_int32(mode), _p(x, C.c_float), C.c_int32(x.shape[0]),
+                                     _p(src, C.c_int32), C.c_int32(n_rows), C.c_int32(skip_unused), C.c_int32(max_blocks),
+                                     C.c_int32(used_row_tiles), None if lst is None else _p(lst, C.c_int32),
+                                     C.c_int32(0 if lst is None else lst.shape[0]), C.c_int32(guard_rows), _p(buf, C.c_float),
+                                     C.byref(k), C.byref(g)))
+    return buf, k.value, g.value
 
 
 # jd_debug_hist_bin's sentinel below hist_min (above hist_max it gives JD_EHIST)

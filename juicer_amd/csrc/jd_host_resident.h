@@ -188,6 +188,9 @@ static ResPlanOut res_plan(const jd_dec *d, int n_streams, int rows_per_buf)
 static int res_fill(jd_dec *d, Resident *R, int n_streams, int rows)
 {
     const int D = d->am->D, G = d->am->n_gmm;
+    // (jd_res_stage_many lists a buffer's row tiles by first row, (2 s + buf) rows + 128 t: a buffer of whole tiles - plan_resident
+    // rounds what jd_res_start is given - or a listed tile would write the next buffer's rows)
+    if (rows < 1 || rows % GMM_ROWS2 != 0) return jd_fail(JD_EINVAL, "jd_res_start: %d rows per buffer, not whole scoring tiles of %d", rows, GMM_ROWS2);
     R->n = n_streams; R->rows = rows;
     const size_t tr = (size_t)n_streams * 2 * rows;
     if (hipMalloc(&R->d_mail, (size_t)n_streams * sizeof(ResMail)) != hipSuccess ||

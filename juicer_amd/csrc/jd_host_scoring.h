@@ -91,6 +91,9 @@ static size_t gmm39_lds() { return 130 * sizeof(JdLogTab) + 32 * sizeof(unsigned
 static size_t gmm_fast39_lds() { return (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float); }
 static size_t gmm_fast_lds() { return (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * sizeof(float); }
 
+// which kernel a launch_gmm call ran and on what grid (jd_score_kernel of juicer_amd.h; 0 / 0: nothing was launched)
+struct GmmLaunch { int kernel = JD_KERNEL_NONE; unsigned grid = 0; };
+
 // max_blocks > 0 bounds the grid (the kernel strides over the tiles): next to the search, a
 // chip-filling scoring launch holds every wave slot for milliseconds and the latency-bound search
 // kernels, which need slots for microseconds at a time, all but stop (measured: 25 ms of
@@ -98,16 +101,20 @@ static size_t gmm_fast_lds() { return (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * si
 // skip_unused: row_src marks unused rows with -1 in whole-tile runs (decode_wave's stream slots).
 // used_row_tiles >= 0: the row tiles that are not skipped (else: all of them)
 // rt_base (device, or null) / n_rt_list: score these row tiles (first rows) only - the kernels of 128-row tiles (D = 39; jd_gmm_fast)
+// info (or null): what was launched (jd_debug_score_rows)
 static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows,
                       float *d_ll, hipStream_t st, int max_blocks = 0, int skip_unused = 0, int used_row_tiles = -1,
-                      const int *rt_base = nullptr, int n_rt_list = 0)
+                      const int *rt_base = nullptr, int n_rt_list = 0, GmmLaunch *info = nullptr)
 {
+    if (info) *info = GmmLaunch();
     if (n_rows <= 0) return JD_OK;
-    if (a->hybrid) {
+    if (a->hybrid) {                                                    // (all of rows [0, n_rows), whatever the other arguments say)
         const long long n = (long long)n_rows * a->n_gmm;
-        hipLaunchKernelGGL(jd_hybrid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_feats, d_row_src, n_rows, b.log_prior,
+        const dim3 grid((unsigned)((n + 255) / 256));
+        hipLaunchKernelGGL(jd_hybrid_kernel, grid, dim3(256), 0, st, d_feats, d_row_src, n_rows, b.log_prior,
                            a->n_gmm, d_ll);
         HIPCHK(hipGetLastError());
+        if (info) { info->kernel = JD_KERNEL_HYBRID; info->grid = grid.x; }
         return JD_OK;
     }
     const bool fast_any = a->D != 39 && b.fast && b.par_fast;           // jd_gmm_fast: the D = 39 kernels' tiles
@@ -120,8 +127,10 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
     const bool small_tiles = tiles128 && (used_row_tiles >= 0 ? (long long)used_row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT) : tiles) < 1024;
     if (small_tiles) tiles = row_tiles * ((a->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL);
     dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
+    int kernel;
     if (a->D == 39 && b.fast && b.par_fast) {
         const size_t sm = gmm_fast39_lds();
+        kernel = small_tiles ? JD_KERNEL_GMM_FAST39_16 : JD_KERNEL_GMM_FAST39_64;
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
@@ -131,6 +140,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
     } else if (fast_any) {
         const size_t sm = gmm_fast_lds();
         const int DP = jd_fast_dp(a->D);
+        kernel = small_tiles ? JD_KERNEL_GMM_FAST_16 : JD_KERNEL_GMM_FAST_64;
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_fast<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
@@ -139,6 +149,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
                                b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
     } else if (a->D == 39) {
         const size_t sm = gmm39_lds();
+        kernel = small_tiles ? JD_KERNEL_GMM39_16 : JD_KERNEL_GMM39_64;
         if (small_tiles)
             hipLaunchKernelGGL(jd_gmm_kernel39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
                                b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, b.logtab, rt_base, n_rt_list);
@@ -148,10 +159,12 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
     } else {
         const int dp = a->D | 1;
         const size_t sm = (size_t)(GMM_ROWS * dp + GMM_ROWS * (GMM_GT + 1)) * sizeof(float);
+        kernel = JD_KERNEL_GMM_GENERIC;
         hipLaunchKernelGGL(jd_gmm_kernel<0>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
                            b.n_mix, a->n_gmm, a->max_mix, a->D, d_ll, skip_unused, b.logtab);
     }
     HIPCHK(hipGetLastError());
+    if (info) { info->kernel = kernel; info->grid = grid.x; }
     return JD_OK;
 }
 
@@ -179,6 +192,56 @@ static int check_device(int device)
     return JD_OK;
 }
 
+// What a stand-alone scoring call holds on the device: the model's parameters and the call's own buffers.  Freed when the call is
+// left, whichever way (an early return of HIPCHK included).
+struct ScoreBufs {
+    AmDevBuf b;
+    float *d_x = nullptr, *d_ll = nullptr;
+    int *d_src = nullptr, *d_list = nullptr;
+    ScoreBufs() = default;
+    ScoreBufs(const ScoreBufs &) = delete;
+    ScoreBufs &operator=(const ScoreBufs &) = delete;
+    ~ScoreBufs()
+    {
+        free_am_gmm(b);
+        if (d_x) (void)hipFree(d_x);
+        if (d_ll) (void)hipFree(d_ll);
+        if (d_src) (void)hipFree(d_src);
+        if (d_list) (void)hipFree(d_list);
+    }
+};
+
+// One launch_gmm call on buffers of its own (the device is set): frames [n_frames][D] and row_src [n_rows] go up, with the tile list
+// rt_base [n_rt] (or null) and - prefilled - the caller's out [(guard_rows + n_rows + guard_rows)][G]; the table is written `guard_rows`
+// rows into the buffer, and the whole buffer comes back.  The arguments are the caller's to check (jd_debug_score_rows does).
+static int score_rows_on_device(const jd_am *a, int mode, const float *frames, int n_frames, const int *row_src, int n_rows, int skip_unused,
+                                int max_blocks, int used_row_tiles, const int *rt_base, int n_rt, int guard_rows, bool prefilled, float *out,
+                                GmmLaunch *info)
+{
+    ScoreBufs s;
+    int rc = upload_am_gmm(a, s.b);
+    if (rc) return rc;
+    if (mode == JD_SCORE_FAST) { rc = upload_am_fast(a, s.b); if (rc) return rc; s.b.fast = 1; }
+    const size_t G = (size_t)a->n_gmm, D = (size_t)a->D;
+    const size_t n_x = std::max<size_t>((size_t)n_frames, 1) * D, n_out = ((size_t)n_rows + 2 * (size_t)guard_rows) * G;
+    HIPCHK(hipMalloc(&s.d_x, n_x * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_ll, n_out * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_src, (size_t)n_rows * sizeof(int)));
+    if (n_frames > 0) HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.d_src, row_src, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+    if (prefilled) HIPCHK(hipMemcpy(s.d_ll, out, n_out * sizeof(float), hipMemcpyHostToDevice));
+    if (rt_base) {
+        HIPCHK(hipMalloc(&s.d_list, (size_t)n_rt * sizeof(int)));
+        HIPCHK(hipMemcpy(s.d_list, rt_base, (size_t)n_rt * sizeof(int), hipMemcpyHostToDevice));
+    }
+    rc = launch_gmm(a, s.b, s.d_x, s.d_src, n_rows, s.d_ll + (size_t)guard_rows * G, 0, max_blocks, skip_unused, used_row_tiles, s.d_list,
+                    rt_base ? n_rt : 0, info);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, s.d_ll, n_out * sizeof(float), hipMemcpyDeviceToHost));
+    return JD_OK;
+}
+
 static int score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, float *out);
 extern "C" int jd_am_score_frames(const jd_am *a, int32_t device, const float *frames, int32_t n_frames,
                                   float *out)
@@ -199,24 +262,72 @@ static int score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const
     int rc = check_device(device);
     if (rc) return rc;
     if (n_frames == 0) return JD_OK;
-    AmDevBuf b;
-    rc = upload_am_gmm(a, b);
-    if (rc) return rc;
-    if (mode == JD_SCORE_FAST) { rc = upload_am_fast(a, b); if (rc) return rc; b.fast = 1; }
-    float *d_x = nullptr, *d_ll = nullptr;
-    int *d_src = nullptr;
     std::vector<int> src((size_t)n_frames);
     for (int i = 0; i < n_frames; ++i) src[i] = i;
-    HIPCHK(hipMalloc(&d_x, (size_t)n_frames * a->D * sizeof(float)));
-    HIPCHK(hipMalloc(&d_ll, (size_t)n_frames * a->n_gmm * sizeof(float)));
-    HIPCHK(hipMalloc(&d_src, (size_t)n_frames * sizeof(int)));
-    HIPCHK(hipMemcpy(d_x, frames, (size_t)n_frames * a->D * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_src, src.data(), (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice));
-    rc = launch_gmm(a, b, d_x, d_src, n_frames, d_ll, 0);
+    return score_rows_on_device(a, mode, frames, n_frames, src.data(), n_frames, 0, 0, -1, nullptr, 0, 0, false, out, nullptr);
+}
+
+// The scoring tile's rows of the kernel launch_gmm takes for these models and this mode (0: the hybrid kernel has none)
+static int score_tile_rows(const jd_am *a, int mode) { return a->hybrid ? 0 : (a->D == 39 || mode == JD_SCORE_FAST) ? GMM_ROWS2 : GMM_ROWS; }
+
+// What the kernels take for granted of a launch's rows (host arrays): every row_src entry in [-1, n_frames); a tile list's entries in
+// [0, n_rows) and their tiles apart; with skip_unused, the valid rows of every scored tile a prefix of it (jd_gmm.h: jd_gmm_kernel -
+// the tile's first row decides).  No device is needed.
+static int check_score_rows(const jd_am *a, int mode, int n_frames, const int *row_src, int n_rows, int skip_unused, const int *rt_base, int n_rt)
+{
+    for (int r = 0; r < n_rows; ++r)
+        if (row_src[r] < -1 || row_src[r] >= n_frames)
+            return jd_fail(JD_EINVAL, "jd_debug_score_rows: row_src[%d] = %d outside [-1, %d)", r, row_src[r], n_frames);
+    const int h = score_tile_rows(a, mode);
+    if (h == 0) {                                                      // (launch_gmm scores every row of a hybrid model and would ignore the list)
+        if (rt_base) return jd_fail(JD_EINVAL, "jd_debug_score_rows: tile lists are not for hybrid models (jd_hybrid_kernel has no tiles)");
+        return JD_OK;
+    }
+    std::vector<int> first;                                            // the scored tiles' first rows
+    if (rt_base) {
+        for (int t = 0; t < n_rt; ++t) {
+            if (rt_base[t] < 0 || rt_base[t] >= n_rows) return jd_fail(JD_EINVAL, "jd_debug_score_rows: rt_base[%d] = %d outside [0, %d)", t, rt_base[t], n_rows);
+            first.push_back(rt_base[t]);
+        }
+        std::sort(first.begin(), first.end());
+        for (size_t t = 1; t < first.size(); ++t)
+            if (first[t] - first[t - 1] < h) return jd_fail(JD_EINVAL, "jd_debug_score_rows: the listed tiles at rows %d and %d overlap", first[t - 1], first[t]);
+    } else
+        for (int r0 = 0; r0 < n_rows; r0 += h) first.push_back(r0);
+    if (skip_unused)
+        for (const int r0 : first) {
+            bool hole = false;
+            for (int r = r0; r < std::min(n_rows, r0 + h); ++r) {
+                if (row_src[r] < 0) hole = true;
+                else if (hole) return jd_fail(JD_EINVAL, "jd_debug_score_rows: skip_unused, and row %d is used behind an unused row of its tile (first row %d)", r, r0);
+            }
+        }
+    return JD_OK;
+}
+
+// launch_gmm with a caller's own arguments, as the decoder's paths call it (include/juicer_amd.h)
+extern "C" int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                                   int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
+                                   int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid)
+{
+    if (kernel) *kernel = JD_KERNEL_NONE;
+    if (grid) *grid = 0;
+    if (!a || !out || n_frames < 0 || n_rows < 0 || (n_frames > 0 && !frames) || (n_rows > 0 && !row_src) || max_blocks < 0 || guard_rows < 0 ||
+        (rt_base ? n_rt < 1 : n_rt != 0))
+        return jd_fail(JD_EINVAL, "jd_debug_score_rows: bad argument");
+    if (mode != JD_SCORE_EXACT && mode != JD_SCORE_FAST) return jd_fail(JD_EINVAL, "jd_debug_score_rows: mode %d (JD_SCORE_EXACT or JD_SCORE_FAST)", mode);
+    if (mode == JD_SCORE_FAST && a->hybrid) return jd_fail(JD_EINVAL, "jd_debug_score_rows: JD_SCORE_FAST is for GMM models");
+    if ((long long)n_rows + 2LL * guard_rows > INT32_MAX) return jd_fail(JD_EINVAL, "jd_debug_score_rows: too many rows");
+    int rc = check_score_rows(a, mode, n_frames, row_src, n_rows, skip_unused, rt_base, n_rt);
     if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, d_ll, (size_t)n_frames * a->n_gmm * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_x); (void)hipFree(d_ll); (void)hipFree(d_src);
-    free_am_gmm(b);
+    rc = check_device(device);
+    if (rc) return rc;
+    if (n_rows == 0) return JD_OK;
+    GmmLaunch info;
+    rc = score_rows_on_device(a, mode, frames, n_frames, row_src, n_rows, skip_unused, max_blocks, used_row_tiles, rt_base, n_rt, guard_rows, true,
+                              out, &info);
+    if (rc) return rc;
+    if (kernel) *kernel = info.kernel;
+    if (grid) *grid = (int32_t)info.grid;
     return JD_OK;
 }

@@ -5,8 +5,9 @@ kernels: jd_gmm_kernel39 on both tile widths, the generic jd_gmm_kernel at other
 import numpy as np
 import pytest
 
-from logadd_cases import (CUT, INF, LZ, NAN, cancellation_pairs, d_chunks, divergent_pairs, edge_pairs, first_difference,
-                          random_pairs, same_floats)
+from logadd_cases import (INF, LZ, cancellation_pairs, d_chunks, divergent_pairs, edge_pairs, first_difference, random_pairs,
+                          same_floats)
+from logadd_cases import crafted_model as _crafted_model, table_frames as _frames      # (shared with tests/score_rows_cases.py)
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4                                               # jd_gmm_fast39's, as tests/test_gpu_fastscore.py holds it
@@ -58,64 +59,6 @@ def test_device_fast_log_add_within_tolerance(built, cases):
 
 
 # ---------------------------------------------------------------- crafted tables through the kernels
-
-M_MAX = 24                                                # > 16: a state longer than the 16-mixture chains of the bench models
-
-
-def _crafted_states(rng):
-    """component values (dets) of the states whose cells the test chooses"""
-    above, below = np.nextafter(CUT, np.float32(0)), np.nextafter(CUT, np.float32(-INF))
-    st = []
-    x, y, _ = divergent_pairs()
-    st += [[a, b] for a, b in zip(x, y)]                                        # the divergent pairs, both orders
-    st += [[0.0, CUT], [0.0, above], [0.0, below], [CUT, 0.0], [above, 0.0],    # d at the cut, one float either side
-           [-2.5, -2.5 + CUT], [-2.5 + above, -2.5]]
-    st += [[-3.25, -3.25], [0.0, 0.0], [-70.0, -70.0, -70.0], [-1.0] * 17]      # equal components
-    st += [[LZ, LZ], [LZ, -5.0], [-5.0, LZ], [LZ, -INF], [-INF, -3.0], [-3.0, -INF], [-INF, -INF], [LZ], [-INF],
-           [np.nextafter(LZ, np.float32(0)), LZ]]                               # at or below LOG_ZERO
-    st += [[INF, -1.0], [INF, INF], [-1.0, INF]]                                # +inf components: inf, NaN (inf - inf)
-    cx, cy = cancellation_pairs(per_binade=8, window=4, seed=7)
-    pick = rng.choice(cx.shape[0], 48, replace=False)
-    st += [[a, b] for a, b in zip(cx[pick], cy[pick])]                          # results near 0
-    st += [list(rng.uniform(-4.0, 0.0, n).astype(np.float32)) for n in (17, 20, M_MAX)]   # long chains, close components
-    st += [[0.0], [0.0, 0.0], [0.0] * 5]                                        # det 0: subnormal distances stay visible
-    return [np.asarray(s, np.float32) for s in st]
-
-
-def _crafted_model(D, G, seed):
-    """det / mean / ivar / n_mix of G states: the crafted ones first, then random ones of every length 1..M_MAX; means 0"""
-    rng = np.random.default_rng(seed)
-    st = _crafted_states(rng)
-    assert G >= len(st)
-    n_mix = np.zeros(G, np.int32)
-    det = np.full((G, M_MAX), LZ, np.float32)
-    for g in range(G):
-        n = 1 + g % (M_MAX if g < 4 * M_MAX else 4)                           # (every length, then short: the oracle's time)
-        v = st[g] if g < len(st) else rng.uniform(-60.0, -10.0, n).astype(np.float32)
-        n_mix[g] = v.shape[0]
-        det[g, :v.shape[0]] = v
-    mean = np.zeros((G, M_MAX, D), np.float32)
-    ivar = rng.uniform(0.5, 2.0, (G, M_MAX, D)).astype(np.float32)
-    return det, mean, ivar, n_mix
-
-
-def _frames(D, R, seed):
-    """rows by kind: 0 the means (every cell its det-made value), 1 random, 2 a NaN feature, 3 a feature whose squared distance
-    overflows to inf, 4 every feature 1e-20 (squared distances 1e-40: subnormal; a flushed one would read 0)"""
-    rng = np.random.default_rng(seed + 1)
-    x = np.zeros((R, D), np.float32)
-    for r in range(R):
-        k = r % 5
-        if k == 1:
-            x[r] = rng.normal(0.0, 0.4, D)
-        elif k == 2:
-            x[r, r % D] = NAN
-        elif k == 3:
-            x[r, (3 * r) % D] = 1e30
-        elif k == 4:
-            x[r] = 1e-20
-    return x
-
 
 def _check_table(D, G, R, seed, fast=False):
     from juicer_amd import capi
