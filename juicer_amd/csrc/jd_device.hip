@@ -24,6 +24,10 @@
 //                    atomic-max Viterbi recombination into per-arc keys and
 //                    word-boundary Path records appended to a device arena.
 //
+// The host runtime below asks HIP, calls a pure function, allocates and uploads: what the kernels see of the graph and the
+// models is decided in jd_prep.h, the sizes and the layout of the stream arenas and of a wave's likelihood tables in
+// jd_arena.h, the cluster plan of a launch in jd_plan.h - plain data in, plain data out, each tested on the CPU.
+//
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see build.py).
 #include <hip/hip_runtime.h>
 
@@ -45,11 +49,11 @@
 #include <deque>
 #include <limits>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 #include "jd_internal.h"
 #include "jd_prep.h"            // LZ, the device arc's flags, XState; the graph preparation of jd_dec_create
+#include "jd_arena.h"           // the sizes and the layout of the stream arenas (ensure_arenas), a wave's likelihood tables (WavePlan, plan_wave)
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -201,17 +205,6 @@ struct HostResult {
     float m_tot[3] = {0.0f, 0.0f, 0.0f};
 };
 
-// How one wave of utterances is laid out in likelihood tables (plan_wave): frames per chunk, the rows of every chunk
-// (stream after stream, packed) and the source frame of every row.
-struct WavePlan {
-    int nb = 0, Fc = 128, n_chunks = 1, maxT = 0;
-    std::vector<int> T;                        // frames per stream
-    std::vector<size_t> chunk_row0;            // first entry of chunk c in row_src
-    // [chunk][stream]: first row of the stream in the chunk's table; rows per chunk (a multiple of the scoring tile)
-    std::vector<int> row_off, chunk_rows;
-    std::vector<int> row_src;                  // row -> frame of d_feats (-1: unused)
-    size_t max_rows = 0, n_rows_all = 0;
-};
 // A batch announced with jd_dec_prefetch_scores: scored on the scoring stream WHILE the batch before it is searched
 // (the blocks of the scoring kernel take the CUs that clusters of the persistent search leave as their streams end).
 struct Prefetch {
@@ -671,127 +664,105 @@ static void reset_srec(StateRec *srec, const int *d_row_ptr, int64_t n_states)
     hipLaunchKernelGGL(jd_reset_srec_kernel, dim3((unsigned)((n_states + 255) / 256)), dim3(256), 0, 0, srec, d_row_ptr, (long long)n_states);
 }
 
-static int ensure_slab(jd_dec *d, size_t floats);
-static int ensure_arenas_try(jd_dec *d, double mem_fraction)
+// ---- ensure_arenas, step by step.  How large the arenas are and where each piece lies is decided in jd_arena.h (pure, tested on the
+// CPU: tests/test_arena_cpu.py); the steps below ask HIP for the memory there is, call it, allocate and clear.
+
+// what jd_arena.h has to know of the kernels' structs (the literals: what tests/arena_driver.cpp is run with - a struct that grows
+// fails the build here instead of moving the recorded capacities)
+static ArenaSizes arena_sizes()
 {
-    int rc = check_device(d->device);
-    if (rc) return rc;
-    const int B = d->max_streams, MN = d->am->max_n;
-    const int64_t rec_bytes = (MN <= 5) ? RecLayout<3>::REC_BYTES : RecLayout<6>::REC_BYTES;
-    // a stream's arenas: 256-byte aligned pieces of one block (two uses of the same list: sizes with blk = null, then pointers)
-#define A(p, n) do { const size_t bytes_ = (std::max<size_t>((size_t)(n), 1) * sizeof(*(p)) + 255) & ~(size_t)255; \
-                     if (blk) (p) = (typename std::remove_reference<decltype(p)>::type)(blk + off); off += bytes_; } while (0)
-#define ARENAS() do { \
-        A(S.rec, 2 * d->cap_slots * (rec_bytes / 4)); \
-        A(S.live, d->net->n_arcs); \
-        A(S.srec, d->net->n_states); \
-        A(S.items, 4 * d->cap_items); \
-        A(S.newl, d->cap_new); A(S.dirtyl, 2 * d->cap_new); \
-        A(S.tot, TOT_N * MAXW); A(S.item_end, MAXW); \
-        A(S.paths, d->cap_paths); A(S.paths2, d->cap_paths); A(S.gc_idx, d->cap_paths); A(S.gc_state, sizeof(GcState) / 4); \
-        A(S.hist, 2 * HIST_MAX_BINS); } while (0)
-    const bool auto_slots = d->cap_slots <= 0, auto_items = d->cap_items <= 0, auto_paths = d->cap_paths <= 0;
-    // The slab a previous decoder left on this device (slab_take) is there without waiting for the driver to clear
-    // memory - 5-6 s for the default share of a 288 GB device - but only if this decoder's arenas FIT it, and two
-    // decoders never ask for quite the same: the free memory has moved by a table or a network since.  So when the
-    // sizes come out above the cached slab by a few per cent (up to 6: a smaller Path arena means more collections - the
-    // 14 M-arc bench graph lost 4 % of its throughput to arenas fitted to a slab a fifth short), they are scaled down
-    // to it (second pass).
-    double fit = 1.0;
-    for (int pass = 0; pass < 3; ++pass) {
-    if (pass) { if (auto_slots) d->cap_slots = 0; if (auto_items) d->cap_items = 0; if (auto_paths) d->cap_paths = 0; }
-    {   // Capacities the caller did not set: sized for 288 GB of HBM, not for frugality.  70% of the
-        // free memory is split over the streams; of a stream's share (after its per-arc / per-state
-        // tables) 50% goes to instance records, 20% to frontier items, 30% to Path records - each
-        // between a floor that suits narrow beams and the most the graph can ever need.  Record and
-        // item arenas are addressed with 32-bit byte offsets (buffer descriptors): < 4 GiB each.
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        free_b += slab_cached_bytes(d->device);                        // (the cached slab is this decoder's to take)
-        const double n_arcs = (double)d->net->n_arcs, n_states = (double)d->net->n_states;
-        const double fixed = n_arcs * 1.0 + n_states * (double)sizeof(StateRec) + 2.0 * d->Fc * d->am->n_gmm * sizeof(float);
-        const double budget = std::max(0.0, fit * mem_fraction * (double)free_b / B - fixed);
-        const double rec_b = 2.0 * rec_bytes, item_b = 2.0 * (sizeof(Tok) + sizeof(int4)) + 32.0;
-        const double path_b = 2.0 * sizeof(PathRec) + 4.0;
-        auto pick = [](double share, int64_t lo, int64_t hi) {
-            return std::max<int64_t>(std::min<int64_t>(hi, (int64_t)share), std::min(lo, hi));
-        };
-        const int64_t lim_rec = (0xe0000000LL / (2 * rec_bytes)) & ~63LL, lim_item = 0xe0000000LL / 64;
-        if (d->cap_slots <= 0) {
-            d->cap_slots = pick(0.5 * budget / rec_b, 1 << 19, std::min<int64_t>(d->net->n_arcs + 65536, lim_rec));
-            if (d->slots_hint > d->cap_slots) d->cap_slots = std::min<int64_t>(d->slots_hint, lim_rec);   // setMaxAllocModels: more room, never less
-        }
-        if (d->cap_items <= 0)
-            d->cap_items = pick(0.2 * budget / item_b, 1 << 21, std::min<int64_t>(std::max<int64_t>(2 * d->net->n_arcs + 65536, 1 << 21), lim_item));
-        // (records and items stop at their addressing limits: what they leave of the budget goes to the Path
-        // records - every collection of those is a stop of the stream's launch - up to 16 per arc of the
-        // graph: small graphs do not write more, and tens of GB take seconds to allocate)
-        if (d->cap_paths <= 0)
-            d->cap_paths = pick(std::max(0.3 * budget, budget - (double)d->cap_slots * rec_b - (double)d->cap_items * item_b) / path_b,
-                                1 << 21, std::min<int64_t>(0x40000000LL, std::max<int64_t>(1 << 24, 16 * d->net->n_arcs)));
-        if (d->cap_slots > lim_rec || d->cap_items > lim_item || d->cap_paths > 0x7fffff00LL)
-            return jd_fail(JD_EINVAL, "arena capacity too large (instance records and frontier items are addressed "
-                           "with 32-bit byte offsets: at most %lld / %lld records)", (long long)lim_rec, (long long)lim_item);
-        // every wave of a stream's cluster owns 1/NW of each arena; small arenas limit the cluster
-        // size instead (launch_search), down to one workgroup per stream
-        d->cap_slots = std::max<int64_t>(d->cap_slots, 64 * SW) & ~63LL;
-        d->cap_items = std::max<int64_t>(d->cap_items, 64 * SW);
-        d->cap_new = std::min<int64_t>(4 * d->cap_items, 0x7fffff00LL);
-    }
-    {
-        StreamDev S;
-        char *blk = nullptr;
-        size_t off = 0;
-        ARENAS();
-        const double need = (double)off * B, cached = (double)slab_cached_bytes(d->device);
-        if (cached <= 0.0 || need <= cached || need > 1.06 * cached || !(auto_slots || auto_items || auto_paths)) break;
-        fit *= 0.998 * cached / need;
-    }
-    }
+    static_assert(RecLayout<3>::REC_BYTES == 80 && RecLayout<6>::REC_BYTES == 144, "tests/golden/arena_golden.json: rec_bytes");
+    static_assert(sizeof(PathRec) == 32 && sizeof(Tok) == 16 && sizeof(int4) == 16 && sizeof(StateRec) == 32, "tests/golden/arena_golden.json: sizes");
+    static_assert(sizeof(int2) == 8 && sizeof(GcState) == 4 * 68, "tests/golden/arena_golden.json: newl, gc_words");
+    static_assert(TOT_N == 10 && MAXW == 512 && HIST_MAX_BINS == 2048 && SW == 8, "tests/golden/arena_golden.json: tot_n, maxw, hist_bins, sw");
+    return ArenaSizes{RecLayout<3>::REC_BYTES, RecLayout<6>::REC_BYTES, sizeof(PathRec), sizeof(Tok), sizeof(int4), sizeof(StateRec),
+                      (int)(sizeof(GcState) / 4), TOT_N, MAXW, HIST_MAX_BINS, SW};
+}
+
+// what arena_caps was given and how many fit passes it ran: ensure_arenas' JD_VERBOSE line
+struct ArenaAttempt { ArenaIn in{}; int passes = 0; };
+
+// the capacities of a stream's arenas (arena_caps) from the free memory and the cached slab, into d and d->C
+static int arenas_pick_caps(jd_dec *d, double mem_fraction, ArenaAttempt *att)
+{
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    ArenaIn &in = att->in;
+    in = ArenaIn{free_b, slab_cached_bytes(d->device), mem_fraction, d->max_streams, d->net->n_arcs, d->net->n_states,
+                 d->Fc, d->am->n_gmm, d->am->max_n, d->cap_slots, d->cap_items, d->cap_paths, d->slots_hint, arena_sizes()};
+    ArenaCaps caps;
+    arena_caps(in, &caps);
+    att->passes = caps.passes;
+    d->cap_slots = caps.cap_slots; d->cap_items = caps.cap_items; d->cap_paths = caps.cap_paths;
+    if (caps.status == ARENA_TOO_LARGE)
+        return jd_fail(JD_EINVAL, "arena capacity too large (instance records and frontier items are addressed "
+                       "with 32-bit byte offsets: at most %lld / %lld records)", (long long)caps.lim_rec, (long long)caps.lim_item);
+    d->cap_new = caps.cap_new;
     d->C.cap_slots = (unsigned)d->cap_slots; d->C.cap_items = (unsigned)d->cap_items; d->C.cap_new = (unsigned)d->cap_new;
     d->C.cap_paths = (int)d->cap_paths;
-    // a stream stops for a collection when its Path records pass this mark (checked between frames): half
-    // of a small arena, all but the larger of an eighth / 4 M records of a large one (a frame writes at
-    // most one record per frontier item; running out anyway is the JD_ENOMEM that names the arena)
-    d->C.gc_threshold = (int)std::max<int64_t>(d->cap_paths / 2, d->cap_paths - std::max<int64_t>(d->cap_paths / 8, 4 << 20));
-    d->h_streams.assign((size_t)B, StreamDev());
-    rc = dmalloc(d, &d->d_res, (size_t)B * 5 * d->res_cap);
+    d->C.gc_threshold = (int)caps.gc_threshold;
+    return JD_OK;
+}
+
+// the result arena of all streams (and, for model-level output, the records' models beside it)
+static int arenas_alloc_results(jd_dec *d)
+{
+    const size_t B = (size_t)d->max_streams;
+    int rc = dmalloc(d, &d->d_res, B * 5 * d->res_cap);
     if (rc) return rc;
     if (d->models) {                                                   // (model-level output only; else jd_dec_set_output_level)
-        rc = dmalloc(d, &d->d_res_model, (size_t)B * d->res_cap);
+        rc = dmalloc(d, &d->d_res_model, B * d->res_cap);
         if (rc) return rc;
         rc = dmalloc(d, &d->d_partial_model, (size_t)6 * d->res_cap);
         if (rc) return rc;
     }
-    size_t stream_bytes = 0;                                           // (the same for every stream: known after the first sizing pass)
+    return JD_OK;
+}
+
+// ONE slab for all streams (slab_take: the previous decoder's when there is one), a stream's share carved up into
+// 256-byte aligned pieces (arena_layout).  What a decoder's set-up costs is the BYTES the driver has to clear:
+// 25-60 GB/s (tools/alloc_probe.py), i.e. seconds for the default 70 % of a 288 GB device.
+static int arenas_take_and_carve(jd_dec *d)
+{
+    const int B = d->max_streams;
+    size_t off[AR_N];
+    const ArenaDims dims = {d->cap_slots, d->cap_items, d->cap_paths, d->cap_new, d->net->n_arcs, d->net->n_states, d->am->max_n, arena_sizes()};
+    const size_t stream_bytes = arena_layout(dims, off);               // (the same for every stream)
+    const int rc = slab_take(d->device, stream_bytes * (size_t)B, &d->slab);
+    if (rc) return rc;
+    d->h_streams.assign((size_t)B, StreamDev());
     for (int s = 0; s < B; ++s) {
         StreamDev &S = d->h_streams[(size_t)s];
         memset(&S, 0, sizeof S);
-        // ONE slab for all streams (slab_take: the previous decoder's when there is one), a stream's share carved
-        // up into 256-byte aligned pieces (two passes over the same list: sizes, then pointers).  What a decoder's
-        // set-up costs is the BYTES the driver has to clear: 25-60 GB/s (tools/alloc_probe.py), i.e. seconds for
-        // the default 70 % of a 288 GB device.
-        char *blk = nullptr;
-        size_t off = 0;
-        ARENAS();
-        if (s == 0) {
-            stream_bytes = off;
-            rc = slab_take(d->device, stream_bytes * (size_t)B, &d->slab);
-            if (rc) return rc;
-        }
-        blk = (char *)d->slab.p + (size_t)s * stream_bytes;
-        off = 0;
-        ARENAS();
-        {   // the five result arrays of all streams live in one arena [stream][array][res_cap]:
-            // fetch_results brings a whole wave back with a single strided copy
-            int *base = d->d_res + (size_t)s * 5 * d->res_cap;
-            S.res_label = base; S.res_time = base + d->res_cap;
-            S.res_score = (float *)(base + 2 * (size_t)d->res_cap); S.res_ac = (float *)(base + 3 * (size_t)d->res_cap);
-            S.res_lm = (float *)(base + 4 * (size_t)d->res_cap);
-        }
-#undef ARENAS
-#undef A
+        char *blk = (char *)d->slab.p + (size_t)s * stream_bytes;
+        S.rec = (int *)(blk + off[AR_REC]);
+        S.live = (unsigned char *)(blk + off[AR_LIVE]);
+        S.srec = (StateRec *)(blk + off[AR_SREC]);
+        S.items = (int4 *)(blk + off[AR_ITEMS]);
+        S.newl = (int2 *)(blk + off[AR_NEWL]);
+        S.dirtyl = (int *)(blk + off[AR_DIRTYL]);
+        S.tot = (int *)(blk + off[AR_TOT]);
+        S.item_end = (int *)(blk + off[AR_ITEM_END]);
+        S.paths = (PathRec *)(blk + off[AR_PATHS]);
+        S.paths2 = (PathRec *)(blk + off[AR_PATHS2]);
+        S.gc_idx = (int *)(blk + off[AR_GC_IDX]);
+        S.gc_state = (int *)(blk + off[AR_GC_STATE]);
+        S.hist = (int *)(blk + off[AR_HIST]);
+        // the five result arrays of all streams live in one arena [stream][array][res_cap]:
+        // fetch_results brings a whole wave back with a single strided copy
+        int *base = d->d_res + (size_t)s * 5 * d->res_cap;
+        S.res_label = base; S.res_time = base + d->res_cap;
+        S.res_score = (float *)(base + 2 * (size_t)d->res_cap); S.res_ac = (float *)(base + 3 * (size_t)d->res_cap);
+        S.res_lm = (float *)(base + 4 * (size_t)d->res_cap);
         S.res_cap = d->res_cap;
+    }
+    return JD_OK;
+}
+
+// nothing in the arenas needs to be clear except the per-arc and per-state words and the waves' counts
+static int arenas_clear(jd_dec *d)
+{
+    for (const StreamDev &S : d->h_streams) {
         HIPCHK(hipMemset(S.live, 0, (size_t)d->net->n_arcs));          // per arc: no instance
         reset_srec(S.srec, d->d_row_ptr, d->net->n_states);
         HIPCHK(hipGetLastError());
@@ -799,27 +770,42 @@ static int ensure_arenas_try(jd_dec *d, double mem_fraction)
         HIPCHK(hipMemset(S.tot, 0, TOT_N * MAXW * sizeof(int)));
         HIPCHK(hipMemset(S.item_end, 0, MAXW * sizeof(int)));
     }
-    rc = dmalloc(d, &d->d_streams, (size_t)B);
+    return JD_OK;
+}
+
+// the streams' arena pointers, frame counts and control blocks on the device, and the status words
+static int arenas_alloc_ctl(jd_dec *d)
+{
+    const size_t B = (size_t)d->max_streams;
+    int rc = dmalloc(d, &d->d_streams, B);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(d->d_streams, d->h_streams.data(), (size_t)B * sizeof(StreamDev), hipMemcpyHostToDevice));
-    rc = dmalloc(d, &d->d_T, (size_t)B);
+    HIPCHK(hipMemcpy(d->d_streams, d->h_streams.data(), B * sizeof(StreamDev), hipMemcpyHostToDevice));
+    rc = dmalloc(d, &d->d_T, B);
     if (rc) return rc;
-    rc = dmalloc(d, &d->d_ctl, (size_t)B);
+    rc = dmalloc(d, &d->d_ctl, B);
     if (rc) return rc;
     rc = dmalloc(d, &d->d_status, 8);
     if (rc) return rc;
     HIPCHK(hipMemset(d->d_status, 0, 8 * sizeof(int)));
-    if (rc) return rc;
     HIPCHK(hipHostMalloc((void **)&d->h_status, 8 * sizeof(int)));
-    {
-        std::vector<StreamCtl> hc((size_t)B);
-        memset(hc.data(), 0, hc.size() * sizeof(StreamCtl));
-        for (auto &c : hc) {
-            c.needs_init = 1; c.best_emit = LZ;
-            c.best_final.score = LZ; c.best_final.ac = LZ; c.best_final.lm = LZ; c.best_final.path = -1;
-        }
-        HIPCHK(hipMemcpy(d->d_ctl, hc.data(), hc.size() * sizeof(StreamCtl), hipMemcpyHostToDevice));
+    std::vector<StreamCtl> hc(B);
+    memset(hc.data(), 0, hc.size() * sizeof(StreamCtl));
+    for (auto &c : hc) {
+        c.needs_init = 1; c.best_emit = LZ;
+        c.best_final.score = LZ; c.best_final.ac = LZ; c.best_final.lm = LZ; c.best_final.path = -1;
     }
+    HIPCHK(hipMemcpy(d->d_ctl, hc.data(), hc.size() * sizeof(StreamCtl), hipMemcpyHostToDevice));
+    return JD_OK;
+}
+
+static int ensure_slab(jd_dec *d, size_t floats);
+static int ensure_arenas_try(jd_dec *d, double mem_fraction, ArenaAttempt *att)
+{
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    if ((rc = arenas_pick_caps(d, mem_fraction, att)) || (rc = arenas_alloc_results(d)) || (rc = arenas_take_and_carve(d)) ||
+        (rc = arenas_clear(d)) || (rc = arenas_alloc_ctl(d)))
+        return rc;
     rc = ensure_slab(d, (size_t)d->Fc * d->am->n_gmm);                // streaming API: one stream, one chunk
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
@@ -833,15 +819,18 @@ static int ensure_arenas(jd_dec *d)
 {
     if (d->arenas_ready) return JD_OK;
     const auto t_start = std::chrono::steady_clock::now();
-    struct Report { jd_dec *d; std::chrono::steady_clock::time_point t0;
-        ~Report() { if (getenv("JD_VERBOSE")) fprintf(stderr, "arenas: slots %lld, items %lld, Path records %lld per stream x %d streams in %.3f s\n",
+    ArenaAttempt att;                                                  // (the last attempt's: the one that succeeded, when one did)
+    struct Report { jd_dec *d; const ArenaAttempt *att; std::chrono::steady_clock::time_point t0;
+        ~Report() { if (getenv("JD_VERBOSE")) fprintf(stderr, "arenas: slots %lld, items %lld, Path records %lld per stream x %d streams in %.3f s "
+                                                      "(free %zu, cached %zu bytes, fraction %.17g, %d fit passes)\n",
                                                       (long long)d->cap_slots, (long long)d->cap_items, (long long)d->cap_paths, d->max_streams,
-                                                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } } report{d, t_start};
+                                                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+                                                      att->in.free_bytes, att->in.cached_bytes, att->in.mem_fraction, att->passes); } } report{d, &att, t_start};
     const int64_t u_slots = d->cap_slots, u_items = d->cap_items, u_paths = d->cap_paths;   // <= 0: not set by the caller
     double frac = 0.7;
     for (int attempt = 0;; ++attempt) {
         const size_t mark = d->allocs.size();
-        const int rc = ensure_arenas_try(d, frac);
+        const int rc = ensure_arenas_try(d, frac, &att);
         if (rc == JD_OK) return JD_OK;
         for (size_t i = mark; i < d->allocs.size(); ++i) (void)hipFree(d->allocs[i]);
         d->allocs.resize(mark);
@@ -1030,69 +1019,19 @@ static int fetch_results(jd_dec *d, int s0, int n, jd_hyp *out, int out0, const 
 
 #include "jd_host_launch.h"
 
-// Lay a wave of nb <= max_streams utterances out in likelihood tables.
-// Frames per chunk.  A search launch lasts as long as its slowest stream and streams do not wait
-// for each other inside a launch, so the fewer launches the better: one chunk covers the longest
-// utterance when the likelihood table (frames of the batch x tied states floats, 288 GB of HBM to
-// draw on) fits a quarter of the free memory; otherwise the batch is decoded in several chunks,
-// scored alternately into two tables.  A chunk's table holds the frames the streams really have
-// in it, packed stream after stream (only the last 128-row scoring tile of a chunk is partly empty).
+// Lay a wave of nb <= max_streams utterances out in likelihood tables (jd_arena.h: wave_layout, from the free memory)
 static int plan_wave(jd_dec *d, int nb, const int64_t *ustart, const int64_t *ulen, WavePlan &P)
 {
-    const int G = d->am->n_gmm;
-    P = WavePlan();
-    P.nb = nb;
-    P.T.assign((size_t)nb, 0);
-    long long sumT = 0;
-    for (int u = 0; u < nb; ++u) {
-        const int64_t t = ulen[u];
-        if (t < 0 || t > 0x3fffffff) return jd_fail(JD_EINVAL, "utterance %d: bad frame count", u);
-        P.T[(size_t)u] = (int)t;
-        P.maxT = std::max(P.maxT, (int)t);
-        sumT += t;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const WaveStatus st = wave_layout(WaveIn{nb, ustart, ulen, free_b, d->ll_cap, d->am->n_gmm, d->Fw_env, GMM_ROWS2}, &P);
+    switch (st.code) {
+    case WAVE_OK: return JD_OK;
+    case WAVE_BAD_LENGTH: return jd_fail(JD_EINVAL, "utterance %d: bad frame count", st.utt);
+    case WAVE_CHUNK_ROWS: return jd_fail(JD_EINVAL, "more than 2^31 frames in one chunk");
+    case WAVE_BATCH_FRAMES: return jd_fail(JD_EINVAL, "more than 2^31 frames in one batch");
     }
-    int Fc = std::max(128, (P.maxT + 127) / 128 * 128);
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        // (three tables of one size are kept: ensure_slab)
-        const double have = 0.25 * (double)free_b + 3.0 * (double)d->ll_cap * sizeof(float);
-        const double per_frame = (double)nb * G * sizeof(float);       // (a chunk holds at most nb * Fc rows)
-        if (3.0 * (double)(sumT + 128) * G * sizeof(float) > have && 3.0 * (double)Fc * per_frame > have)
-            Fc = std::max(128, (int)(have / 3.0 / per_frame) / 128 * 128);
-        if (d->Fw_env > 0) Fc = d->Fw_env;
-    }
-    P.Fc = Fc;
-    const int n_chunks = P.n_chunks = std::max(1, (P.maxT + Fc - 1) / Fc);   // chunk 0 also carries recognitionStart
-    // rows of a chunk: stream u's frames [c0, min(T_u, c1)) start at row_off[c][u]
-    P.chunk_row0.assign((size_t)n_chunks + 1, 0);
-    P.row_off.assign((size_t)n_chunks * nb, 0); P.chunk_rows.assign((size_t)n_chunks, 0);
-    for (int c = 0; c < n_chunks; ++c) {
-        long long r = 0;
-        for (int u = 0; u < nb; ++u) {
-            P.row_off[(size_t)c * nb + u] = (int)r;
-            r += std::max(0, std::min(P.T[(size_t)u], (c + 1) * Fc) - c * Fc);
-        }
-        if (r > 0x7fffff00LL) return jd_fail(JD_EINVAL, "more than 2^31 frames in one chunk");
-        P.chunk_rows[(size_t)c] = (int)((r + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2);
-        P.chunk_row0[(size_t)c + 1] = P.chunk_row0[(size_t)c] + (size_t)P.chunk_rows[(size_t)c];
-        P.max_rows = std::max(P.max_rows, (size_t)P.chunk_rows[(size_t)c]);
-    }
-    P.max_rows = std::max<size_t>(P.max_rows, GMM_ROWS2);
-    // row -> source frame table for all chunks
-    P.n_rows_all = std::max<size_t>(P.chunk_row0[(size_t)n_chunks], 1);
-    P.row_src.assign(P.n_rows_all, -1);
-    for (int c = 0; c < n_chunks; ++c)
-        for (int u = 0; u < nb; ++u) {
-            const int n = std::max(0, std::min(P.T[(size_t)u], (c + 1) * Fc) - c * Fc);
-            int *dst = P.row_src.data() + P.chunk_row0[(size_t)c] + (size_t)P.row_off[(size_t)c * nb + u];
-            for (int dt = 0; dt < n; ++dt) {
-                const int64_t src = ustart[u] + (int64_t)c * Fc + dt;
-                if (src > 0x7fffffff) return jd_fail(JD_EINVAL, "more than 2^31 frames in one batch");
-                dst[dt] = (int)src;
-            }
-        }
-    return JD_OK;
+    return jd_fail(JD_EINVAL, "plan_wave: internal error");
 }
 
 // The likelihood tables: THREE of one size in one allocation (a search launch addresses the table of every stream it
