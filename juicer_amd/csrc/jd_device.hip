@@ -54,6 +54,7 @@
 #include "jd_internal.h"
 #include "jd_prep.h"            // LZ, the device arc's flags, XState; the graph preparation of jd_dec_create
 #include "jd_arena.h"           // the sizes and the layout of the stream arenas (ensure_arenas), a wave's likelihood tables (WavePlan, plan_wave)
+#include "jd_ahead.h"           // working ahead: the queue of announced batches, tables and banks, decode_wave's decisions
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -207,16 +208,11 @@ struct HostResult {
 
 // A batch announced with jd_dec_prefetch_scores: scored on the scoring stream WHILE the batch before it is searched
 // (the blocks of the scoring kernel take the CUs that clusters of the persistent search leave as their streams end).
-struct Prefetch {
-    int state = 0;                             // 0 none, 1 announced, 2 scoring enqueued (table d_ll[buf], event ev1)
-    const float *feats = nullptr; int nb = 0;
-    std::vector<int64_t> ustart, ulen;
-    WavePlan plan;
-    int buf = 0;
-    int bank = -1;                             // >= 0: its utterances have been started, on this bank of streams ("two batches in flight")
+// What is decided about it is decided in jd_ahead.h (AheadEntry); here, the events around its scoring (SCORED: the table is d_ll[buf]).
+struct Prefetch : AheadEntry {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void drop_events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); ev0 = ev1 = nullptr; }
-    void drop() { drop_events(); state = 0; feats = nullptr; bank = -1; }
+    void drop() { drop_events(); state = AHEAD_NONE; feats = nullptr; bank = -1; }
 };
 
 struct jd_dec {
@@ -279,7 +275,7 @@ struct jd_dec {
     unsigned *h_park = nullptr; int *d_park = nullptr;   // jd_park_kernel's words (host-mapped state; arrival counts and quotas by XCD)
     // scoring one batch ahead (jd_dec_prefetch_scores): the table of the NEXT batch is scored while this one is searched
     std::deque<Prefetch> pf_q;            // the batches ahead, in the order announced: scored, started ("two batches in flight"), or neither yet
-    int fg_buf = -1;                      // the table(s) the wave being decoded uses (-1: none; -2: tables 0 and 1, in chunks)
+    int fg_buf = FG_NONE;                 // the table(s) the wave being decoded uses (or FG_NONE, FG_BOTH)
     int fg_bank = -1;                     // >= 0: the wave being decoded runs on this bank of streams and the batch behind it may be
                                           // started beside it
     int pipeline = 1;                     // two batches in flight (JD_PIPELINE=0: off)
@@ -1083,29 +1079,15 @@ static void pipe_drain(jd_dec *d);
 static void pf_discard(jd_dec *d)
 {
     pipe_drain(d);
-    bool scoring = false;
-    for (const Prefetch &F : d->pf_q) if (F.state == 2) scoring = true;
-    if (scoring) (void)hipStreamSynchronize(d->s_gmm);
+    if (ahead_any_scored(d->pf_q)) (void)hipStreamSynchronize(d->s_gmm);
     for (Prefetch &F : d->pf_q) F.drop();
     d->pf_q.clear();
 }
 // ... what has been scored ahead only: the announcements stay (they are scored again, beside the next search)
 static void pf_discard_scored(jd_dec *d)
 {
-    bool scoring = false;
-    for (const Prefetch &F : d->pf_q) if (F.state == 2) scoring = true;
-    if (scoring) (void)hipStreamSynchronize(d->s_gmm);
-    for (Prefetch &F : d->pf_q) { F.drop_events(); F.state = 1; F.bank = -1; }
-}
-// a table that neither the running batch (fg_buf, -1: none) nor a batch scored ahead holds; -1: none
-static int free_table(const jd_dec *d, int fg_buf)
-{
-    for (int t = 0; t < 3; ++t) {
-        bool used = t == fg_buf;
-        for (const Prefetch &F : d->pf_q) if (F.state == 2 && F.buf == t) used = true;
-        if (!used) return t;
-    }
-    return -1;
+    if (ahead_any_scored(d->pf_q)) (void)hipStreamSynchronize(d->s_gmm);
+    for (Prefetch &F : d->pf_q) { F.drop_events(); F.state = AHEAD_ANNOUNCED; F.bank = -1; }
 }
 
 // Start the scoring of the batches that have been announced and not scored yet, each into a table nobody holds.  Called
@@ -1114,12 +1096,11 @@ static int free_table(const jd_dec *d, int fg_buf)
 static int pf_launch(jd_dec *d)
 {
     const size_t G = (size_t)d->am->n_gmm;
-    bool any = false;
     for (Prefetch &F : d->pf_q) {
-        if (F.state != 1) continue;
+        if (F.state != AHEAD_ANNOUNCED) continue;
         // Scoring ahead is an optimisation: a batch that cannot be scored now (no table free, a table larger than the
         // slab - which cannot grow while tables are in use) is scored when it is decoded, as ever.
-        const int buf = free_table(d, d->fg_buf);
+        const int buf = ahead_free_table(d->pf_q, d->fg_buf);
         if (buf < 0 || F.plan.max_rows * G > d->ll_cap) break;
         if (ensure_rows(d, buf, F.plan.n_rows_all) != JD_OK) { (void)hipGetLastError(); break; }
         if (hipEventCreate(&F.ev0) != hipSuccess || hipEventCreate(&F.ev1) != hipSuccess) { (void)hipGetLastError(); F.drop_events(); break; }
@@ -1129,45 +1110,30 @@ static int pf_launch(jd_dec *d)
             hipEventRecord(F.ev1, d->s_gmm) != hipSuccess) {
             (void)hipGetLastError(); F.drop_events(); break;
         }
-        F.buf = buf; F.state = 2;
-        any = true;
+        F.buf = buf; F.state = AHEAD_SCORED;
     }
-    (void)any;
     HIPCHK(hipMemsetAsync(d->d_status + 4, 0, sizeof(int), d->s_gmm)); // (behind the scoring, if any: the search may be re-planned again)
     return JD_OK;
 }
-static bool pf_wants_scoring(const jd_dec *d)
-{
-    for (const Prefetch &F : d->pf_q) if (F.state == 1) return free_table(d, d->fg_buf) >= 0 && F.plan.max_rows * (size_t)d->am->n_gmm <= d->ll_cap;
-    return false;
-}
+static bool pf_wants_scoring(const jd_dec *d) { return ahead_wants_scoring(d->pf_q, d->fg_buf, (size_t)d->am->n_gmm, d->ll_cap); }
 static bool pf_scoring_in_flight(const jd_dec *d)
 {
     for (const Prefetch &F : d->pf_q)
-        if (F.state == 2 && F.ev1 && hipEventQuery(F.ev1) != hipSuccess) { (void)hipGetLastError(); return true; }
+        if (F.state == AHEAD_SCORED && F.ev1 && hipEventQuery(F.ev1) != hipSuccess) { (void)hipGetLastError(); return true; }
     return false;
 }
-static double pf_scoring_rows(const jd_dec *d)
-{
-    double rows = 0.0;
-    for (const Prefetch &F : d->pf_q) if (F.state == 1) rows += (double)F.plan.chunk_rows[0];
-    return rows;
-}
 
-// Announce a wave: it joins the queue of batches ahead (at most three; one more is not taken) and is scored beside
-// the next search launch that leaves a table free.  A wave whose table would be cut into chunks is not announced (it
-// is scored when it is decoded, as ever).  front: in front of what the caller announced (the waves of one call).
+// Announce a wave (jd_ahead.h: ahead_admits, ahead_enqueue): it is scored beside the next search launch that leaves a table free.
+// front: in front of what the caller announced (the waves of one call).
 static int pf_announce(jd_dec *d, int nb, const float *d_feats, const int64_t *ustart, const int64_t *ulen, bool front = false)
 {
-    if (nb <= 0 || nb > d->max_streams || d->pf_q.size() >= 3) return JD_OK;
+    if (!ahead_admits(nb, d->max_streams, d->pf_q.size())) return JD_OK;
     Prefetch F;
     F.ustart.assign(ustart, ustart + nb);
     F.ulen.assign(ulen, ulen + nb);
     const int rc = plan_wave(d, nb, F.ustart.data(), F.ulen.data(), F.plan);
     if (rc) return rc;
-    if (F.plan.n_chunks != 1) return JD_OK;
-    F.feats = d_feats; F.nb = nb; F.state = 1;
-    if (front) d->pf_q.push_front(std::move(F)); else d->pf_q.push_back(std::move(F));
+    (void)ahead_enqueue(d->pf_q, std::move(F), d_feats, nb, front);
     return JD_OK;
 }
 
@@ -1186,17 +1152,11 @@ static int pf_announce(jd_dec *d, int nb, const float *d_feats, const int64_t *u
 static int pf_background(jd_dec *d, int fg_bank, const std::vector<StreamHead> *heads, hipStream_t st, std::vector<int2> *work, std::vector<double> *left)
 {
     work->clear(); left->clear();
-    if (d->pf_q.empty() || !d->pipeline || d->C.lazy) return JD_OK;
-    // Searching ahead pays where a frame is a chain of dependent steps and workgroups wait - not where it is bytes: a
-    // stream-frame of several hundred thousand instances keeps every workgroup it can get busy, and a second batch on the
-    // same chip only splits them (measured: the 14 M-arc graph 119 k -> 55 k frames/s, configs[3] 5.3 k -> 0.8 k).  The
-    // decoder knows its load from the batches it has decoded (load_scale: instances + arcs per stream-frame over
-    // configs[1]'s 23.7 k); beyond JD_BG_MAX_LOAD times that the batch behind waits for its turn.
-    if (d->load_scale > d->bg_max_load) return JD_OK;
+    const AheadBg step = ahead_bg_step(d->pf_q, d->pipeline != 0, d->C.lazy != nullptr, d->load_scale, d->bg_max_load, d->max_streams);
+    if (step == AHEAD_BG_NONE || (step == AHEAD_BG_GO_ON && !heads)) return JD_OK;
     Prefetch &F = d->pf_q.front();
     const int B = d->max_streams / 2;
-    if (F.state != 2 || F.nb > B || F.plan.n_chunks != 1) return JD_OK;
-    if (F.bank < 0) {
+    if (step == AHEAD_BG_START) {
         // its table was scored beside the search before this one and is about ready: worth a moment (JD_BG_WAIT_US)
         const auto tq0 = std::chrono::steady_clock::now();
         while (hipEventQuery(F.ev1) != hipSuccess) {
@@ -1212,22 +1172,145 @@ static int pf_background(jd_dec *d, int fg_bank, const std::vector<StreamHead> *
         hipLaunchKernelGGL(jd_set_T_kernel, dim3((F.nb + 63) / 64), dim3(64), 0, st, d->d_ctl, s0, F.nb, d->d_T + s0);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));                              // (plan.T may move with the queue)
-        for (int u = 0; u < F.nb; ++u) {
-            work->push_back(make_int2(s0 + u, (int)(table_row0(d, F.buf) + F.plan.row_off[(size_t)u])));
-            left->push_back((double)F.plan.T[(size_t)u]);
-        }
+        heads = nullptr;                                               // (just started: every utterance, all its frames)
+    }
+    ahead_bg_work(F, F.bank * B, table_row0(d, F.buf), heads, work, left);
+    return JD_OK;
+}
+
+// ---- decode_wave, step by step.  One wave on its way through the steps: what was decided (jd_ahead.h) and what the next steps need.
+struct Wave {
+    int nb; const float *feats; const int64_t *ustart, *ulen;
+    Prefetch me;                               // the announced batch this wave turned out to be (claim.mine); dropped on every way out
+    WavePlan plan_local;
+    AheadClaim claim{}; AheadPlace place{}; AheadNeed need{}; AheadTake take{};
+    int b0 = 0;                                // its table (in chunks: b0 and b0 ^ 1, alternately)
+    std::vector<int> frame0;                   // where its streams stand (a batch started ahead: hundreds of frames in)
+    struct Events {                            // a chunk's scoring, begin and end (destroyed on every way out, error paths included)
+        std::vector<hipEvent_t> v;
+        ~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
+    } gs, ge;
+    const WavePlan &P() const { return claim.mine ? me.plan : plan_local; }
+    ~Wave() { me.drop(); }
+};
+
+// claim: is this wave the one at the head of the batches ahead (jd_dec_prefetch_scores)?  An announcement speaks of a batch
+// BEHIND the decode that follows it (a stream of equal batches announces the very batch it is about to decode).
+static void wave_claim(jd_dec *d, Wave &W)
+{
+    W.claim = ahead_claim(d->pf_q, W.feats, W.nb, W.ustart, W.ulen, d->pf_retry);
+    if (W.claim.mine) { W.me = std::move(d->pf_q.front()); d->pf_q.pop_front(); }
+    if (W.claim.drop) pf_discard(d);
+}
+// place: its bank of streams, and what becomes of a batch ahead that is in its way
+static void wave_place(jd_dec *d, Wave &W)
+{
+    W.place = ahead_place(d->pf_q, W.P().n_chunks, W.nb, d->max_streams, d->pipeline != 0, d->C.lazy != nullptr, W.claim.mine, W.me.bank);
+    if (W.place.discard) pf_discard(d);
+    if (W.place.unbank) for (Prefetch &Q : d->pf_q) Q.bank = -1;
+}
+// tables: a single-chunk wave sits in one of the three - the one it was scored into ahead, or a free one; chunks alternate between 0 and 1
+static int wave_tables(jd_dec *d, Wave &W)
+{
+    const WavePlan &P = W.P();
+    const bool chunked = P.n_chunks > 1;
+    if (W.claim.mine && !chunked) { W.b0 = W.me.buf; return JD_OK; }
+    W.need = ahead_table_need(d->pf_q, P.max_rows, (size_t)d->am->n_gmm, d->ll_cap, chunked);
+    if (W.need.drop_scored) pf_discard_scored(d);
+    const int rc = ensure_slab(d, W.need.floats);
+    if (rc) return rc;
+    W.take = ahead_table_take(d->pf_q, chunked);
+    if (W.take.discard) pf_discard(d);
+    W.b0 = W.take.table;
+    return ensure_rows(d, W.b0, P.n_rows_all);
+}
+// start its streams, or - its utterances have been started beside the batch before - see where they stand
+static int wave_start_or_resume(jd_dec *d, Wave &W)
+{
+    const int nb = W.nb, s0 = W.place.s0;
+    W.frame0.assign((size_t)nb, 0);
+    if (!W.place.resumed) {
+        HIPCHK(hipMemcpyAsync(d->d_T + s0, W.P().T.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, d->s_search));
+        const int rc = mark_init(d, s0, nb, d->s_search);
+        if (rc) return rc;
+        hipLaunchKernelGGL(jd_set_T_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, s0, nb, d->d_T + s0);
+        HIPCHK(hipGetLastError());
         return JD_OK;
     }
-    if (!heads) return JD_OK;
-    const int s0 = F.bank * B;
-    for (int u = 0; u < F.nb; ++u) {
-        const StreamHead &h = (*heads)[(size_t)(s0 + u)];
-        if (h.error == 0 && h.frame < F.plan.T[(size_t)u]) {
-            work->push_back(make_int2(s0 + u, (int)(table_row0(d, F.buf) + F.plan.row_off[(size_t)u])));
-            left->push_back((double)(F.plan.T[(size_t)u] - h.frame));
-        }
-    }
+    std::vector<StreamHead> head;
+    const int rc = read_heads(d, s0, nb, &head, nullptr);
+    if (rc) return rc;
+    for (int u = 0; u < nb; ++u) { W.frame0[(size_t)u] = head[(size_t)u].frame; d->timing.ahead_frames += head[(size_t)u].frame; }
     return JD_OK;
+}
+// Scoring runs one chunk ahead of the search on its own stream.  launch_search returns when its
+// chunk is through (it synchronises to learn whether a stream stopped for garbage collection),
+// so by the time chunk c+1 is scored into buffer (c+1)&1 the search of chunk c-1 has left it.
+static int wave_score_chunk(jd_dec *d, Wave &W, int c)
+{
+    const WavePlan &P = W.P();
+    HIPCHK(hipEventRecord(W.gs.v[(size_t)c], d->s_gmm));
+    // (a later chunk is launched while the previous one is searched: k_search holds every CU's
+    // registers, so its workgroups start as the search's clusters finish - they fill the tail)
+    if (P.chunk_rows[(size_t)c] == 0) { HIPCHK(hipEventRecord(W.ge.v[(size_t)c], d->s_gmm)); return JD_OK; }
+    const int r = launch_gmm(d->am, d->amb, W.feats, d->d_row_src[W.b0] + P.chunk_row0[(size_t)c], P.chunk_rows[(size_t)c], d->d_ll[W.b0 ^ (c & 1)],
+                             d->s_gmm, 0, true);
+    if (r) return r;
+    HIPCHK(hipEventRecord(W.ge.v[(size_t)c], d->s_gmm));
+    return JD_OK;
+}
+// search chunk c, once its scores are there (and the next chunk's scoring is under way)
+static int wave_search_chunk(jd_dec *d, Wave &W, int c, double *waited_ms, long long *frames_here)
+{
+    const WavePlan &P = W.P();
+    const int G = d->am->n_gmm, s0 = W.place.s0, c0 = c * P.Fc, c1 = (c + 1) * P.Fc;
+    auto failed = [&](int rc) { for (int u = 0; u < W.nb; ++u) d->stream_dirty[(size_t)(s0 + u)] = 1; return rc; };   // (nobody looks at the streams' error words)
+    const auto tw0 = std::chrono::steady_clock::now();
+    HIPCHK(hipEventSynchronize(W.ge.v[(size_t)c]));
+    *waited_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+    int rc = JD_OK;
+    if (c + 1 < P.n_chunks) { rc = wave_score_chunk(d, W, c + 1); if (rc) return rc; }
+    std::vector<int2> work;
+    std::vector<double> weight;
+    // (k_search reads row  slot + (f - c0)  of the slab)
+    *frames_here += ahead_chunk_work(P, c, s0, table_row0(d, W.b0 ^ (c & 1)), W.frame0, &work, &weight);
+    const float *ll = d->d_ll_slab;
+    if (ahead_probe_applies(d->load_scale, d->weighted != 0, c, P, W.place.resumed)) {
+        const std::vector<double> wp = ahead_probe_weights(weight);
+        rc = launch_search(d, work, ll, (long long)G, c0, c0 + AHEAD_PROBE_FRAMES, d->s_search, &wp);
+        if (rc) return failed(rc);
+        if (d->load_scale == 1.0) { rc = learn_load(d, work); if (rc) return rc; }
+        ahead_probe_rest(P, c, s0, &work, &weight);
+    }
+    d->pf_armed = P.n_chunks == 1;                                     // batches ahead are scored / started beside this launch
+    d->fg_bank = W.place.pipe ? W.place.bank : -1;
+    rc = launch_search(d, work, ll, (long long)G, c0, c1, d->s_search, &weight);
+    d->pf_armed = false; d->fg_bank = -1;
+    return rc ? failed(rc) : JD_OK;
+}
+// what scoring (on its own) and search cost on this decoder (launch_search's choice when a table is scored ahead), and the counters
+static void wave_timing(jd_dec *d, const Wave &W, double wall_ms, double waited_ms, long long frames_here, double gmm_before, double search_before)
+{
+    const WavePlan &P = W.P();
+    d->timing.total_ms += wall_ms;
+    d->last_wave_ms = wall_ms;
+    long long rows = 0;
+    for (int c = 0; c < P.n_chunks; ++c) {
+        float gms = 0.0f;
+        if (hipEventElapsedTime(&gms, W.gs.v[(size_t)c], W.ge.v[(size_t)c]) == hipSuccess) d->timing.gmm_ms += gms;
+        rows += P.chunk_rows[(size_t)c];
+    }
+    d->timing.gmm_wait_ms += waited_ms;
+    d->timing.gmm_launches += P.n_chunks;
+    d->timing.prefetched += W.claim.mine ? 1 : 0;
+    if (!W.claim.mine && rows > 0 && d->timing.gmm_ms > gmm_before) d->gmm_ms_per_row = (d->timing.gmm_ms - gmm_before) / (double)rows;
+    // (a launch that also advanced the batch behind: its frames are not known here - the estimate stays)
+    if (frames_here > 0 && d->timing.search_ms > search_before && !d->bg_ran)
+        d->search_ms_per_frame = (d->timing.search_ms - search_before) / (double)frames_here;
+    d->bg_ran = false;
+    for (int u = 0; u < W.nb; ++u) d->timing.search_frames += P.T[(size_t)u];
+    d->timing.gmm_frames = d->timing.search_frames;
+    d->timing.gmm_states = d->am->n_gmm;
 }
 
 // Decode one wave of nb <= max_streams utterances held in device memory.
@@ -1235,198 +1318,52 @@ static int pf_background(jd_dec *d, int fg_bank, const std::vector<StreamHead> *
 static int decode_wave(jd_dec *d, int nb, const float *d_feats, const int64_t *ustart, const int64_t *ulen,
                        hipStream_t user_stream, int *s0_out)
 {
-    const int G = d->am->n_gmm;
     const double gmm_before = d->timing.gmm_ms, search_before = d->timing.search_ms;
-    // is this wave the one at the head of the batches ahead (jd_dec_prefetch_scores)?  An announcement speaks of a batch
-    // BEHIND the decode that follows it (a stream of equal batches announces the very batch it is about to decode):
-    // only a batch whose table has been scored ahead - beside an earlier decode - can be the one decoded now.
-    Prefetch me;
-    bool mine = false;
-    if (!d->pf_q.empty()) {
-        Prefetch &F = d->pf_q.front();
-        mine = F.state == 2 && F.feats == d_feats && F.nb == nb && std::equal(ustart, ustart + nb, F.ustart.begin()) &&
-               std::equal(ulen, ulen + nb, F.ulen.begin());
-        if (mine) { me = std::move(F); d->pf_q.pop_front(); }
-        else {
-            // not the batch that was announced: what has been scored (or searched) ahead is for a batch that is not
-            // coming now - dropped; announcements nothing has been done for yet stay (they are batches BEHIND this one)
-            // (a wave that is decoded a second time - the retry of jd_decode_batch_device - finds the waves behind it there)
-            bool worked = false;
-            for (const Prefetch &Q : d->pf_q) if (Q.state == 2 || Q.bank >= 0) worked = true;
-            if (worked && !d->pf_retry) pf_discard(d);
-        }
-    }
-    struct MeGuard { Prefetch &p; ~MeGuard() { p.drop(); } } me_guard{me};
-    const bool prefetched = mine;
-    WavePlan plan_local;
+    const bool verbose = getenv("JD_VERBOSE") != nullptr;
+    const std::string q_before = verbose ? ahead_describe(d->pf_q, d_feats, nb, ustart, ulen) : std::string();
+    const size_t cap_before = d->ll_cap;
+    Wave W{nb, d_feats, ustart, ulen};
+    wave_claim(d, W);
     int rc = JD_OK;
-    if (!mine) { rc = plan_wave(d, nb, ustart, ulen, plan_local); if (rc) return rc; }
-    const WavePlan &P = mine ? me.plan : plan_local;
-    const std::vector<int> &T = P.T;
-    const int Fc = P.Fc, n_chunks = P.n_chunks, maxT = P.maxT;
-    // stream bank: the utterances of a batch that fills at most half of the streams run on one of two banks, so that
-    // the batch behind it can be started beside it (pf_background)
-    const int B = d->max_streams / 2;
-    const bool pipe = d->pipeline && B > 0 && nb <= B && n_chunks == 1 && !d->C.lazy;
-    {
-        bool scored = false, started = false;
-        for (const Prefetch &Q : d->pf_q) { if (Q.state == 2) scored = true; if (Q.bank >= 0) started = true; }
-        // a wave in chunks needs tables 0 and 1: nothing scored ahead survives it
-        if (n_chunks > 1 && (scored || started)) pf_discard(d);
-        // a wave outside the banks takes the streams a batch behind it has been started on: that batch starts again when
-        // its turn comes (its table stays)
-        else if (!pipe && started) for (Prefetch &Q : d->pf_q) Q.bank = -1;
-    }
-    const bool resumed = prefetched && pipe && me.bank >= 0;           // its utterances have been started beside the batch before
-    int bank = 0;
-    if (pipe) {
-        bank = resumed ? me.bank : 0;
-        if (!resumed) for (const Prefetch &Q : d->pf_q) if (Q.bank == bank) bank ^= 1;   // (at most one batch ahead holds a bank)
-    }
-    const int s0 = pipe ? bank * B : 0;
-    if (s0_out) *s0_out = s0;
-    // tables: a single-chunk wave sits in one of the three; chunks alternate between tables 0 and 1
-    int b0 = 0;
-    if (n_chunks == 1) {
-        if (prefetched) b0 = me.buf;
-        else {
-            // the three tables are of one size: this wave's, or what a batch announced behind it needs if that is more
-            // (with some room: a slab that has to grow loses whatever was scored ahead)
-            size_t need = P.max_rows * (size_t)G;
-            for (const Prefetch &Q : d->pf_q) need = std::max(need, Q.plan.max_rows * (size_t)G);
-            if (need > d->ll_cap) { pf_discard_scored(d); need += need / 8; }
-            rc = ensure_slab(d, need);
-            if (rc) return rc;
-            b0 = free_table(d, -1);
-            if (b0 < 0) { pf_discard(d); b0 = 0; }
-            rc = ensure_rows(d, b0, P.n_rows_all);
-            if (rc) return rc;
-        }
-    } else {
-        rc = ensure_slab(d, P.max_rows * (size_t)G);
-        if (rc) return rc;
-        for (int i = 0; i < 2; ++i) { rc = ensure_rows(d, i, i == 0 ? P.n_rows_all : 0); if (rc) return rc; }
-    }
-    d->fg_buf = n_chunks == 1 ? b0 : -2;                               // (-2: both of tables 0 / 1 - nothing is scored ahead meanwhile)
-    struct FgGuard { jd_dec *d; ~FgGuard() { d->fg_buf = -1; } } fg_guard{d};
+    if (!W.claim.mine) { rc = plan_wave(d, nb, ustart, ulen, W.plan_local); if (rc) return rc; }
+    const WavePlan &P = W.P();
+    const int n_chunks = P.n_chunks;
+    wave_place(d, W);
+    if (s0_out) *s0_out = W.place.s0;
+    rc = wave_tables(d, W);
+    if (verbose)                                                       // (tests/test_gpu_ahead_inputs.py reads it)
+        fprintf(stderr, "ahead: q %s retry %d nb %d n_chunks %d max_rows %zu streams %d pipeline %d lazy %d G %d ll_cap %zu -> mine %d drop %d pipe %d "
+                "resumed %d discard %d unbank %d bank %d s0 %d need %zu drop_scored %d table %d none_free %d\n", q_before.c_str(), d->pf_retry ? 1 : 0,
+                nb, n_chunks, P.max_rows, d->max_streams, d->pipeline != 0, d->C.lazy != nullptr, d->am->n_gmm, cap_before, W.claim.mine, W.claim.drop,
+                W.place.pipe, W.place.resumed, W.place.discard, W.place.unbank, W.place.bank, W.place.s0, W.need.floats, W.need.drop_scored, W.b0,
+                W.take.discard);
+    if (rc) return rc;
+    d->fg_buf = n_chunks == 1 ? W.b0 : FG_BOTH;
+    struct FgGuard { jd_dec *d; ~FgGuard() { d->fg_buf = FG_NONE; } } fg_guard{d};
     // the caller's features may have been produced asynchronously on its stream (NULL = the
     // default stream): the decoder's own streams are non-blocking, so order against it explicitly
     HIPCHK(hipStreamSynchronize(user_stream));
-    if (!prefetched)
-        HIPCHK(hipMemcpyAsync(d->d_row_src[b0], P.row_src.data(), P.n_rows_all * sizeof(int), hipMemcpyHostToDevice, d->s_gmm));
-    std::vector<int> frame0((size_t)nb, 0);                            // where the streams stand (a batch started ahead: hundreds of frames in)
-    if (!resumed) {
-        HIPCHK(hipMemcpyAsync(d->d_T + s0, T.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, d->s_search));
-        rc = mark_init(d, s0, nb, d->s_search);
-        if (rc) return rc;
-        hipLaunchKernelGGL(jd_set_T_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, s0, nb, d->d_T + s0);
-        HIPCHK(hipGetLastError());
-    } else {
-        std::vector<StreamHead> head;
-        rc = read_heads(d, s0, nb, &head, nullptr);
-        if (rc) return rc;
-        for (int u = 0; u < nb; ++u) { frame0[(size_t)u] = head[(size_t)u].frame; d->timing.ahead_frames += head[(size_t)u].frame; }
-    }
-
-    struct Events {                                                    // (destroyed on every way out, error paths included)
-        std::vector<hipEvent_t> v;
-        ~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
-    } ev_gs, ev_ge;
-    ev_gs.v.assign((size_t)n_chunks, nullptr); ev_ge.v.assign((size_t)n_chunks, nullptr);
-    std::vector<hipEvent_t> &gs = ev_gs.v, &ge = ev_ge.v;
-    if (prefetched) {                                                  // the scoring's own events (Events destroys them)
-        gs[0] = me.ev0; ge[0] = me.ev1;
-        me.ev0 = me.ev1 = nullptr;
+    if (!W.claim.mine)
+        HIPCHK(hipMemcpyAsync(d->d_row_src[W.b0], P.row_src.data(), P.n_rows_all * sizeof(int), hipMemcpyHostToDevice, d->s_gmm));
+    rc = wave_start_or_resume(d, W);
+    if (rc) return rc;
+    W.gs.v.assign((size_t)n_chunks, nullptr); W.ge.v.assign((size_t)n_chunks, nullptr);
+    if (W.claim.mine) {                                                // the scoring's own events (Events destroys them)
+        W.gs.v[0] = W.me.ev0; W.ge.v[0] = W.me.ev1;
+        W.me.ev0 = W.me.ev1 = nullptr;
     } else
-        for (int c = 0; c < n_chunks; ++c) { HIPCHK(hipEventCreate(&gs[(size_t)c])); HIPCHK(hipEventCreate(&ge[(size_t)c])); }
-    auto w0 = std::chrono::steady_clock::now();
-    // Scoring runs one chunk ahead of the search on its own stream.  launch_search returns when its
-    // chunk is through (it synchronises to learn whether a stream stopped for garbage collection),
-    // so by the time chunk c+1 is scored into buffer (c+1)&1 the search of chunk c-1 has left it.
-    auto score_chunk = [&](int c) -> int {
-        HIPCHK(hipEventRecord(gs[(size_t)c], d->s_gmm));
-        // (a later chunk is launched while the previous one is searched: k_search holds every CU's
-        // registers, so its workgroups start as the search's clusters finish - they fill the tail)
-        if (P.chunk_rows[(size_t)c] == 0) { HIPCHK(hipEventRecord(ge[(size_t)c], d->s_gmm)); return JD_OK; }
-        int r = launch_gmm(d->am, d->amb, d_feats, d->d_row_src[b0] + P.chunk_row0[(size_t)c], P.chunk_rows[(size_t)c], d->d_ll[b0 ^ (c & 1)], d->s_gmm,
-                           0, true);
-        if (r) return r;
-        HIPCHK(hipEventRecord(ge[(size_t)c], d->s_gmm));
-        return JD_OK;
-    };
-    if (!prefetched) { rc = score_chunk(0); if (rc) return rc; }
+        for (int c = 0; c < n_chunks; ++c) { HIPCHK(hipEventCreate(&W.gs.v[(size_t)c])); HIPCHK(hipEventCreate(&W.ge.v[(size_t)c])); }
+    const auto w0 = std::chrono::steady_clock::now();
+    if (!W.claim.mine) { rc = wave_score_chunk(d, W, 0); if (rc) return rc; }
     double waited_ms = 0.0;
-    std::vector<int2> work;
-    std::vector<double> weight;
     long long frames_here = 0;
-    for (int c = 0; c < n_chunks; ++c) {
-        const auto tw0 = std::chrono::steady_clock::now();
-        HIPCHK(hipEventSynchronize(ge[(size_t)c]));                    // scores of this chunk are there
-        waited_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-        if (c + 1 < n_chunks) { rc = score_chunk(c + 1); if (rc) return rc; }
-        // a launch lasts as long as its slowest stream: the clusters are sized by the frames ahead of each
-        const int c0 = c * Fc, c1 = (c + 1) * Fc;
-        const long long row0 = table_row0(d, b0 ^ (c & 1));            // (k_search reads row  slot + (f - c0)  of the slab)
-        work.clear(); weight.clear();
-        for (int u = 0; u < nb; ++u)
-            if ((c == 0 && frame0[(size_t)u] == 0) || T[(size_t)u] > std::max(c0, frame0[(size_t)u])) {
-                work.push_back(make_int2(s0 + u, (int)(row0 + P.row_off[(size_t)c * nb + u])));   // {stream, its first row in the chunk's table}
-                weight.push_back((double)(std::min(T[(size_t)u], c1) - std::max(c0, frame0[(size_t)u])));
-                frames_here += std::min(T[(size_t)u], c1) - std::max(c0, frame0[(size_t)u]);
-            }
-        const float *ll = d->d_ll_slab;
-        if (d->load_scale == 1.0 && d->weighted && c == 0 && nb > 1 && std::min(maxT, c1) - c0 > 128 && !resumed) {
-            // the decoder's very first batch: nothing is known about the load yet, and the cluster sizes depend
-            // on it (a frame of 2 M instances is not a frame of 12 k) - a short launch finds out
-            const int c_mid = c0 + 32;
-            std::vector<double> wp(weight.size());
-            for (size_t i = 0; i < wp.size(); ++i) wp[i] = std::min(weight[i], 32.0);
-            rc = launch_search(d, work, ll, (long long)G, c0, c_mid, d->s_search, &wp);
-            if (rc) { for (int u = 0; u < nb; ++u) d->stream_dirty[(size_t)(s0 + u)] = 1; return rc; }
-            if (d->load_scale == 1.0) { rc = learn_load(d, work); if (rc) return rc; }
-            std::vector<int2> w2; std::vector<double> wt2;
-            for (size_t i = 0; i < work.size(); ++i) {
-                const int u = work[i].x - s0;
-                if (T[(size_t)u] > c_mid) { w2.push_back(work[i]); wt2.push_back((double)(std::min(T[(size_t)u], c1) - c_mid)); }
-            }
-            work.swap(w2); weight.swap(wt2);
-        }
-        d->pf_armed = n_chunks == 1;                                   // batches ahead are scored / started beside this launch
-        d->fg_bank = pipe ? bank : -1;
-        rc = launch_search(d, work, ll, (long long)G, c0, c1, d->s_search, &weight);
-        d->pf_armed = false; d->fg_bank = -1;
-        if (rc) { for (int u = 0; u < nb; ++u) d->stream_dirty[(size_t)(s0 + u)] = 1; return rc; }   // (nobody looks at the streams' error words)
-    }
-    hipLaunchKernelGGL(jd_finish_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, s0, nb, res_model_of(d));
+    for (int c = 0; c < n_chunks; ++c) { rc = wave_search_chunk(d, W, c, &waited_ms, &frames_here); if (rc) return rc; }
+    hipLaunchKernelGGL(jd_finish_kernel, dim3((nb + 63) / 64), dim3(64), 0, d->s_search, d->d_ctl, d->d_streams, W.place.s0, nb, res_model_of(d));
     HIPCHK(hipGetLastError());
-    {   // (a table being scored ahead is waited for by the wave that uses it)
-        bool scoring = false;
-        for (const Prefetch &Q : d->pf_q) if (Q.state == 2) scoring = true;
-        if (!scoring) HIPCHK(hipStreamSynchronize(d->s_gmm));
-    }
+    if (!ahead_any_scored(d->pf_q)) HIPCHK(hipStreamSynchronize(d->s_gmm));   // (a table being scored ahead is waited for by the wave that uses it)
     HIPCHK(hipStreamSynchronize(d->s_search));
-    auto w1 = std::chrono::steady_clock::now();
-    d->timing.total_ms += std::chrono::duration<double, std::milli>(w1 - w0).count();
-    d->last_wave_ms = std::chrono::duration<double, std::milli>(w1 - w0).count();
-    for (int c = 0; c < n_chunks; ++c) {
-        float gms = 0.0f;
-        if (hipEventElapsedTime(&gms, gs[(size_t)c], ge[(size_t)c]) == hipSuccess) d->timing.gmm_ms += gms;
-    }
-    d->timing.gmm_wait_ms += waited_ms;
-    d->timing.gmm_launches += n_chunks;
-    d->timing.prefetched += prefetched ? 1 : 0;
-    {   // what scoring (on its own) and search cost on this decoder: launch_search's choice when a table is scored ahead
-        long long rows = 0;
-        for (int c = 0; c < n_chunks; ++c) rows += P.chunk_rows[(size_t)c];
-        if (!prefetched && rows > 0 && d->timing.gmm_ms > gmm_before) d->gmm_ms_per_row = (d->timing.gmm_ms - gmm_before) / (double)rows;
-        // (a launch that also advanced the batch behind: its frames are not known here - the estimate stays)
-        if (frames_here > 0 && d->timing.search_ms > search_before && !d->bg_ran)
-            d->search_ms_per_frame = (d->timing.search_ms - search_before) / (double)frames_here;
-        d->bg_ran = false;
-    }
-    for (int u = 0; u < nb; ++u) d->timing.search_frames += T[(size_t)u];
-    d->timing.gmm_frames = d->timing.search_frames;
-    d->timing.gmm_states = G;
+    const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    wave_timing(d, W, wall_ms, waited_ms, frames_here, gmm_before, search_before);
     return JD_OK;
 }
 
@@ -1458,13 +1395,8 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
     if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);
     d->timing = jd_timing();
     int first_err = JD_OK;
-    // More utterances than streams: successive waves.  A wave lasts as long as its longest
-    // utterance, so the waves are formed from the utterances sorted by length (results do not
-    // depend on which utterances share a wave).
-    std::vector<int> order((size_t)n_utts);
-    std::iota(order.begin(), order.end(), 0);
-    if (n_utts > d->max_streams)
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return offs[a + 1] - offs[a] > offs[b + 1] - offs[b]; });
+    // More utterances than streams: successive waves, formed from the utterances sorted by length (jd_ahead.h)
+    const std::vector<int> order = ahead_wave_order(offs, n_utts, d->max_streams);
     std::vector<int64_t> ustart((size_t)d->max_streams), ulen((size_t)d->max_streams);
     std::vector<int64_t> nstart((size_t)d->max_streams), nlen((size_t)d->max_streams);
     // the batch takes every stream over: utterances of the streaming interface that were never finished leave the
@@ -1480,9 +1412,7 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
     std::deque<Prefetch> callers;
     if (waves) {
         // (a batch of several waves is never itself one of the announced ones: what has been worked ahead goes)
-        bool worked = false;
-        for (const Prefetch &Q : d->pf_q) if (Q.state == 2 || Q.bank >= 0) worked = true;
-        if (worked) pf_discard(d);
+        if (ahead_any_worked(d->pf_q)) pf_discard(d);
         callers.swap(d->pf_q);
     }
     // (on an error way out nothing scored or announced ahead survives: the caller may free the features next)
@@ -1491,17 +1421,9 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
         ~Restore() { for (Prefetch &F : p) F.drop(); if (!ok) pf_discard(d); }
     } callers_guard{d, callers, false};
     for (int u0 = 0; u0 < n_utts; u0 += d->max_streams) {
-        const int nb = std::min(d->max_streams, n_utts - u0);
-        for (int i = 0; i < nb; ++i) {
-            const int u = order[(size_t)(u0 + i)];
-            ustart[(size_t)i] = offs[u]; ulen[(size_t)i] = offs[u + 1] - offs[u];
-        }
-        if (waves && u0 + nb < n_utts) {
-            const int nn = std::min(d->max_streams, n_utts - (u0 + nb));
-            for (int i = 0; i < nn; ++i) {
-                const int u = order[(size_t)(u0 + nb + i)];
-                nstart[(size_t)i] = offs[u]; nlen[(size_t)i] = offs[u + 1] - offs[u];
-            }
+        const int nb = ahead_wave_slice(offs, order, u0, d->max_streams, ustart.data(), ulen.data());
+        const int nn = waves ? ahead_wave_slice(offs, order, u0 + nb, d->max_streams, nstart.data(), nlen.data()) : 0;
+        if (nn > 0) {
             rc = pf_announce(d, nn, d_feats, nstart.data(), nlen.data());
             if (rc) return rc;
         } else if (waves) {
@@ -1541,11 +1463,8 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
             break;
         }
     }
-    if (d->load_frames > 0.0) {                                        // the load this batch had -> the next batch's cluster sizes
-        const double scale = std::min(1e5, std::max(0.25, d->load_sum / d->load_frames / 23700.0));
-        d->load_scale = (d->load_scale == 1.0) ? scale : 0.5 * (d->load_scale + scale);
-        d->load_sum = d->load_frames = 0.0;
-    }
+    d->load_scale = ahead_load_update(d->load_scale, d->load_sum, d->load_frames);   // the load this batch had -> the next batch's cluster sizes
+    if (d->load_frames > 0.0) d->load_sum = d->load_frames = 0.0;
     callers_guard.ok = true;
     return first_err;
 }

@@ -42,7 +42,7 @@ static int learn_load(jd_dec *d, const std::vector<int2> &work_in)
         work += (double)st[(size_t)w.x * ST_N + ST_INSTS] + (double)st[(size_t)w.x * ST_N + ST_ARCS];
         frames += (double)head[(size_t)w.x].frame;
     }
-    if (frames > 0.0) d->load_scale = std::min(1e5, std::max(0.25, work / frames / 23700.0));
+    if (frames > 0.0) d->load_scale = ahead_load(work, frames);
     return JD_OK;
 }
 
@@ -84,7 +84,6 @@ static std::unique_lock<std::mutex> lock_search(size_t dev_i)
 
 static int pf_launch(jd_dec *d);
 static bool pf_wants_scoring(const jd_dec *d);
-static double pf_scoring_rows(const jd_dec *d);
 static bool pf_scoring_in_flight(const jd_dec *d);
 static int pf_background(jd_dec *d, int fg_bank, const std::vector<StreamHead> *heads, hipStream_t st, std::vector<int2> *work, std::vector<double> *left);
 static int mark_init(jd_dec *d, int s0, int n, hipStream_t st);
@@ -104,17 +103,11 @@ static int ensure_work_cap(jd_dec *d, int n)
 // Two batches in flight: the plan makes the clusters of this batch finish together and the utterances of the
 // batch behind fill what is left - nothing idles, and the scoring of the table after that, which lives on idle CUs,
 // would finish long after the launch (and the batch behind the next one start late).  So the scoring gets CUs of its
-// own: as many as carry its cost over a launch as long as the last wave was (a multiple of eight: the XCD-local
-// numbering), a third of the chip at most; the search is planned on the rest.
+// own (jd_ahead.h: ahead_reserve); the search is planned on the rest.
 static int scoring_reserve(jd_dec *d, bool planned, bool first_launch, int nwg_all)
 {
     if (!(d->fg_bank >= 0 && d->pf_armed && planned && (pf_wants_scoring(d) || pf_scoring_in_flight(d)))) return 0;
-    if (first_launch) {
-        d->reserve_now = d->score_reserve;
-        if (d->reserve_now < 0) d->reserve_now = (d->gmm_ms_per_row > 0.0 && d->last_wave_ms > 0.0)
-                                               ? (int)std::ceil(d->gmm_ms_per_row * pf_scoring_rows(d) * nwg_all / d->last_wave_ms) : 0;
-        d->reserve_now = std::min((d->reserve_now + 7) & ~7, (nwg_all / 3) & ~7);
-    }
+    if (first_launch) d->reserve_now = ahead_reserve(d->score_reserve, d->gmm_ms_per_row, d->last_wave_ms, ahead_scoring_rows(d->pf_q), nwg_all);
     return d->reserve_now;                                             // (the legs of a re-planned launch leave the same CUs alone)
 }
 
@@ -126,7 +119,7 @@ static int fetch_background(jd_dec *d, hipStream_t st, int n_work, int nwg_all, 
     if (started) { const int hr = read_heads(d, 0, d->max_streams, &heads, nullptr); if (hr) return hr; }
     const int br = pf_background(d, d->fg_bank, started ? &heads : nullptr, st, bg, bg_left);
     if (br) return br;
-    if ((int)bg->size() > nwg_all / 4 || nwg_all - (int)bg->size() < 2 * n_work) { bg->clear(); bg_left->clear(); }
+    if (ahead_bg_clipped((int)bg->size(), n_work, nwg_all)) { bg->clear(); bg_left->clear(); }
     return JD_OK;
 }
 
@@ -145,7 +138,7 @@ static PlanOut plan_launch(const jd_dec *d, const std::vector<double> *weight, i
     in.weighted = d->weighted != 0; in.plan_mode = d->plan_mode; in.plan_min_cw = d->plan_min_cw;
     in.a_us = d->model_a_us; in.b_us = d->model_b_us; in.a2_us = d->model2_a_us; in.b2_us = d->model2_b_us; in.load_scale = d->load_scale;
     in.gmm_cu_us = (d->plan_mode == 1 && d->pf_armed && pf_wants_scoring(d))
-                 ? d->pf_gmm_weight * 1e3 * d->gmm_ms_per_row * pf_scoring_rows(d) * (nwg_all - in.n_bg) : 0.0;
+                 ? d->pf_gmm_weight * 1e3 * d->gmm_ms_per_row * ahead_scoring_rows(d->pf_q) * (nwg_all - in.n_bg) : 0.0;
     in.xl_ok = d->xl_ok; in.xl_slack = d->xl_slack;
     in.rebalance = d->rebalance != 0; in.bg_rebalance = d->bg_rebalance != 0;
     in.rebalance_frac = d->rebalance_frac; in.rebalance_min_us = d->rebalance_min_us;
@@ -183,9 +176,7 @@ static bool hold_replan_for_scoring(const jd_dec *d, const std::vector<double> *
     if (!(d->pf_armed && pf_wants_scoring(d))) return false;
     double frames_now = 0.0;
     if (weight) for (double w : *weight) frames_now += w;
-    const double est_gmm = d->gmm_ms_per_row * pf_scoring_rows(d);
-    const double est_search = d->search_ms_per_frame * frames_now;
-    return d->pf_rebalance == 0 || (d->pf_rebalance < 0 && est_gmm > 0.0 && est_search > 0.0 && est_gmm >= 0.1 * est_search);
+    return ahead_hold_replan(d->pf_rebalance, d->gmm_ms_per_row, ahead_scoring_rows(d->pf_q), d->search_ms_per_frame, frames_now);
 }
 
 // More streams than the chip has CUs, one workgroup each: the slot kernel as a plain launch (jd_slot.h: k_slot_batch) - a
