@@ -55,6 +55,7 @@
 #include "jd_prep.h"            // LZ, the device arc's flags, XState; the graph preparation of jd_dec_create
 #include "jd_arena.h"           // the sizes and the layout of the stream arenas (ensure_arenas), a wave's likelihood tables (WavePlan, plan_wave)
 #include "jd_ahead.h"           // working ahead: the queue of announced batches, tables and banks, decode_wave's decisions
+#include "jd_pipe.h"            // batches through the resident slot kernel: the mailbox record, the slot pipeline's bookkeeping and pump decisions
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)

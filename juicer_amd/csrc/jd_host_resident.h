@@ -5,7 +5,9 @@
 //     stream, reports, the host heartbeat) - jd_res_start / _stop / _post / _poll / _collect / _finish, driven by jd_broker.cpp; the
 //     kernel's geometry is jd_plan.h's plan_resident, jd_res_start the steps that bring it onto the device;
 //   * Pipe: batches through the resident slot kernel utterance by utterance (jd_dec_set_pipeline: JD_FLOW_RESIDENT) - pipe_announce,
-//     pipe_pump, pipe_decode, jd_dec_quiesce, jd_dec_pipeline_stats;
+//     pipe_pump, pipe_decode, jd_dec_quiesce, jd_dec_pipeline_stats.  What they DECIDE - the record of a stream's mailbox, which slot
+//     takes which utterance, the commands, the ready numbers, the scoring pieces, the watchdog, the drain - is jd_pipe.h (no HIP,
+//     tested on the CPU); here are the launches, event queries, mailbox accesses and statistics those decisions ask for;
 //   * at the end, the setters that drop what the pipeline holds: jd_dec_set_output_level / _get_output_level, jd_dec_model_result,
 //     jd_dec_set_scoring.
 // The launch-per-call paths (one batch, two batches in flight, re-planning, the streaming calls) stay in jd_device.hip.
@@ -17,23 +19,7 @@
 // allocates or frees device memory or synchronises the device - either would wait for the kernel.
 #define RES_RING 256
 #define RES_RING_W 2048
-struct ResStream {                                     // the protocol as the host sees it, for one stream
-    unsigned seq;                                      // last sequence number posted
-    unsigned rid;                                      // the last ready number enqueued for it (Resident::d_ready: how far the side stream has come)
-    int T_posted, T_done, err_done;
-    int slot_posted, vslot_posted;                     // (vslot_posted: ResPost::vslot of the command, -1 none)
-    bool exported;                                     // the last report says the slot has exported its utterance (ResDone::exported)
-    bool busy;                                         // a command is posted and its report not yet taken
-    bool init_pending;                                 // ... and it begins an utterance (ResPost::init): a re-post must say so again
-    // The kernel starts: the numbers of both sides begin again.  What the host knows of a stream beyond them - where it stands, a
-    // report not yet taken, an init that a re-post has to repeat - survives a restart; a new record (T_now: where the decoder's
-    // stream stands) is idle there.
-    void reset(const int *T_now)
-    {
-        seq = rid = 0u;
-        if (T_now) { T_posted = T_done = *T_now; err_done = slot_posted = 0; vslot_posted = -1; exported = busy = init_pending = false; }
-    }
-};
+// (ResStream, the protocol as the host sees it for one stream, and its two transitions - a command, a report: jd_pipe.h)
 struct Resident {
     bool on = false;
     int n = 0, Cw = 0, rows = 0;                       // streams [0, n), workgroups per cluster, rows per likelihood buffer
@@ -105,19 +91,17 @@ static bool res_harvest(jd_dec *d, int s)
     Resident *R = d->res;
     ResStream &S = R->stream[s];
     if (!S.busy) return true;
-    if (__atomic_load_n(&R->h_done[s].seq, __ATOMIC_ACQUIRE) != S.seq) return false;
+    if (!res_stream_answered(S, __atomic_load_n(&R->h_done[s].seq, __ATOMIC_ACQUIRE))) return false;
+    const int advanced = res_stream_report(S, R->h_done[s].frame, R->h_done[s].error, R->h_done[s].exported);
     if (d->pipe_on) {                                                  // (jd_dec_pipeline_stats: frames the slot has advanced)
-        d->pipe_frames_searched += std::max(0, R->h_done[s].frame - S.T_done);
+        d->pipe_frames_searched += advanced;
         d->pipe_busy_ticks += R->h_done[s].run_ticks;
     }
-    S.T_done = R->h_done[s].frame; S.err_done = R->h_done[s].error; S.exported = R->h_done[s].exported != 0;
     // (a stream that failed on the device - an arena overflow, a lost workgroup - may hold anything: wiped before its next init,
     // whether or not anybody fetches its result)
     if (S.err_done != 0) d->stream_dirty[(size_t)s] = 1;
     R->run_ticks += R->h_done[s].run_ticks;
-    S.init_pending = false;
     d->stream_T[(size_t)s] = S.T_done;
-    S.busy = false;
     return true;
 }
 
@@ -515,18 +499,14 @@ int jd_res_stage_many(jd_dec *d, int n, const int *streams, const int *bufs, con
 // init: the command begins an utterance.  vslot (the pipeline's slots): the command ends one - ResPost::vslot.
 static void res_command(Resident *R, int s, int T, int slot, bool init, int vslot = -1)
 {
-    ResStream &S = R->stream[s];
-    S.seq += 1;
-    S.busy = true;
-    S.T_posted = T; S.slot_posted = slot; S.vslot_posted = vslot; S.exported = false;
-    if (init) S.init_pending = true;
+    const ResCommand C = res_stream_command(R->stream[s], T, slot, init, vslot);
     __atomic_fetch_add(R->h_beat, 1u, __ATOMIC_RELAXED);               // (a sign of life: k_resident's `beat`)
     ResPost &P = R->h_post[s];
-    P.T = T;
-    P.init = init ? 1 : 0;
-    P.vslot = vslot;
-    P.ready_id = S.rid;
-    __atomic_store_n(&P.word, ((unsigned long long)S.seq << 32) | (unsigned)slot, __ATOMIC_RELEASE);
+    P.T = C.T;
+    P.init = C.init;
+    P.vslot = C.vslot;
+    P.ready_id = C.ready_id;
+    __atomic_store_n(&P.word, C.word, __ATOMIC_RELEASE);
 }
 
 // The command "frames up to T + n_frames are scored in buffer buf" for stream s (idle), behind what has been staged
@@ -611,44 +591,17 @@ int jd_res_finish(jd_dec *d, int s, jd_hyp *out)
 // that no workgroup waits for anybody.  jd_decode_batch_device of the OLDEST announced batch waits until its utterances are
 // through and hands them back; it is also what keeps the slots fed (the pump runs inside the calls - no thread).  Results
 // are those of any other path; what changes is that a batch takes as long as its longest utterance on one workgroup.
-struct PipeUtt { int state = 0, slot = -1, T = 0; long long row0 = 0; };      // state: 0 queued, 1 running, 2 through
-#define PIPE_PIECE_ROWS0 6144            // rows per scoring launch where nothing is planned (JD_PIPE_DECOUPLE=0)
-#define PIPE_CHUNK 128                  // frames per command: what a slot runs before it looks at its mailbox again (jd_dec_quiesce waits that long)
-struct PipeBatch {
-    const float *feats = nullptr; int n = 0; int table = 0; int next = 0, n_done = 0;
-    size_t rows = 0, rows_scored = 0;                  // rows of its table, and how many of them have a scoring launch enqueued
-    int n_kexport = 0;                                 // utterances of it exported by jd_finish_export_kernel (on the side stream)
-    bool scored = false;                               // its table is scored to the last row (Pipe::ev_batch of its table has completed)
-    std::vector<int64_t> offs;
-    std::vector<PipeUtt> u;
-    std::vector<int> order;                            // its utterances by length, longest first: the order in which slots take them
-};
-struct Pipe {
+// What is decided about them is decided in jd_pipe.h (PipeState: the queue of batches, the slots, the pieces); here, what is on the device.
+static_assert(sizeof(ExportList().slot) / sizeof(int) == PIPE_EXPORTS, "pipe_export_add fills jd_gc.h's ExportList");
+struct Pipe : PipeState {
     bool on = false;
-    int K = 0, max_batch = 0, n_slots = 0;
-    size_t table_rows = 0;
     float *d_ll = nullptr;                             // K tables
     int *d_ident = nullptr;                            // row r is frame r of the batch's features
     StreamCtl *d_vctl = nullptr; int *d_vresn = nullptr, *d_vres = nullptr;   // K x max_batch virtual result slots
     int *d_vres_model = nullptr;                       // ... their models (model-level output)
-    std::deque<PipeBatch> q;
-    std::vector<char> table_used;
-    std::vector<int> slot_batch_id, slot_utt;          // per slot: the batch (its serial number) and utterance it runs, -1: free
-    std::vector<char> slot_dirty;
-    long long serial0 = 0;                             // serial number of q.front()
-    int chunk = PIPE_CHUNK;
     std::chrono::steady_clock::time_point t_on;        // (statistics)
-    long long frames_done = 0;
-    // Scoring launches, a piece at a time (pump_score): up to max_out of them enqueued - one running, one behind it - each with
-    // its event; the oldest is ev_piece[piece_turn].
-    hipEvent_t ev_piece[2] = { nullptr, nullptr };
-    int piece_out = 0, piece_turn = 0, max_out = 2;
-    size_t piece_rows = PIPE_PIECE_ROWS0;              // rows per scoring launch (plan_piece_rows, or JD_PIPE_PIECE)
+    hipEvent_t ev_piece[2] = { nullptr, nullptr };     // behind the scoring pieces that are out; the oldest is ev_piece[piece_turn]
     std::vector<hipEvent_t> ev_batch;                  // per table: behind the last piece of the batch that has it
-    std::vector<char> slot_kexport;                    // per slot: its last utterance went out by jd_finish_export_kernel (side stream)
-    // JD_PIPE_DECOUPLE=0 (development) clears it: every export by the kernel on the side stream, a ready number with every
-    // utterance, one piece of PIPE_PIECE_ROWS0 rows in flight
-    bool decouple = true;
 };
 static ExportDst pipe_export_dst(const jd_dec *d)
 {
@@ -687,15 +640,9 @@ static void pipe_drain(jd_dec *d)
                 wall_us / 1e3, 100.0 * (double)(d->res->run_ticks / 100) / (wall_us * P->n_slots), P->frames_done,
                 P->frames_done ? (double)(d->res->run_ticks / 100) / (double)P->frames_done : 0.0);
     }
-    P->on = false; d->pipe_on = false; P->piece_out = 0;              // (jd_res_stop has synchronised the side stream)
-    P->q.clear();
-    std::fill(P->table_used.begin(), P->table_used.end(), 0);
-    std::fill(P->slot_batch_id.begin(), P->slot_batch_id.end(), -1);
+    P->on = false; d->pipe_on = false;                                 // (jd_res_stop has synchronised the side stream)
     d->res_ll = nullptr;
-    for (int s = 0; s < P->n_slots; ++s) {                             // (streams left in the middle of an utterance, or failed)
-        if (P->slot_dirty[(size_t)s]) d->stream_dirty[(size_t)s] = 1;
-        P->slot_dirty[(size_t)s] = 0; P->slot_kexport[(size_t)s] = 0;
-    }
+    pipe_drain_reset(*P, &d->stream_dirty);                            // (streams left in the middle of an utterance, or failed: dirty)
 }
 
 // the results of the slots in EL to their virtual result slots (jd_finish_export_kernel, on the side stream); EL is empty afterwards
@@ -710,106 +657,77 @@ static int pipe_export(jd_dec *d, ExportList *EL)
     return JD_OK;
 }
 
-// The pump, step 1: the reports that are in.  A slot that stopped for a Path collection collects and goes on, one in the middle
-// of its utterance gets its next frames, one whose utterance is through is free: its result is in its virtual result slot already
-// (the report says "exported": k_slot), or goes there by jd_finish_export_kernel - after an error, and wherever the slot did not.
+// The pump's steps, pipe_announce, pipe_decode and pipe_drain have a twin in tests/pipe_driver.cpp - the same calls into jd_pipe.h in the
+// same order, the device replaced by a model - which is what tests/test_pipe_cpu.py holds to the recorded behaviour: a change to the order
+// or the arguments of the calls here is made there too.
+// The pump, step 1 (jd_pipe.h: pipe_harvest): the reports that are in - a collection, the next frames, or the utterance is through
 static int pump_harvest(jd_dec *d)
 {
     Pipe *P = d->pipe;
     Resident *R = d->res;
     ExportList EL; EL.n = 0;
     for (int s = 0; s < P->n_slots; ++s) {
-        if (P->slot_batch_id[(size_t)s] < 0) continue;
-        if (!res_harvest(d, s)) continue;
+        if (!pipe_slot_occupied(*P, s) || !res_harvest(d, s)) continue;
         const ResStream &S = R->stream[s];
-        const int er = S.err_done, fr = S.T_done;
-        PipeBatch &B = P->q[(size_t)(P->slot_batch_id[(size_t)s] - P->serial0)];
+        PipeBatch &B = pipe_slot_batch(*P, s);
         const int ui = P->slot_utt[(size_t)s];
-        const PipeUtt &U = B.u[(size_t)ui];
-        if (er == 0 && fr < S.T_posted) {                              // stopped for a Path collection: collect, go on
+        const PipeHarvest h = pipe_harvest(S, B.u[(size_t)ui], pipe_vslot(*P, B, ui), P->chunk, P->decouple);
+        if (h.act == PIPE_COLLECT) {
             const int rc = jd_res_collect(d, s);
             if (rc) return rc;
-            continue;
+        } else if (h.act == PIPE_NEXT) {
+            res_command(R, s, h.T, h.row_slot, false, h.vslot);
+            B.n_commands += 1;
+        } else {
+            if (h.kexport) {
+                pipe_harvest_kexport(*P, s);
+                if (pipe_export_add(&EL, s, pipe_vslot(*P, B, ui))) { const int rc = pipe_export(d, &EL); if (rc) return rc; }
+            }
+            pipe_harvest_through(*P, s, h, S.T_done);
+            d->pipe_utts_through += 1;
         }
-        const int vslot = B.table * P->max_batch + ui;
-        if (er == 0 && fr < U.T) {                                     // its next frames (the command that ends the utterance names its result slot)
-            const int T = std::min(U.T, fr + P->chunk);
-            res_command(R, s, T, (int)U.row0, false, (P->decouple && T == U.T) ? vslot : -1);
-            continue;
-        }
-        if (!(S.exported && er == 0)) {
-            EL.slot[EL.n] = s; EL.vslot[EL.n] = vslot; EL.n += 1;
-            P->slot_kexport[(size_t)s] = 1;                            // (the slot's next utterance waits for it: pump_refill)
-            B.n_kexport += 1;
-            if (EL.n == 64) { const int rc = pipe_export(d, &EL); if (rc) return rc; }
-        }
-        B.u[(size_t)ui].state = 2; B.n_done += 1; P->frames_done += fr; d->pipe_utts_through += 1;
-        if (er) P->slot_dirty[(size_t)s] = 1;                          // (its arenas may be inconsistent: out of the game until the pipeline stops)
-        P->slot_batch_id[(size_t)s] = -1;
     }
     return pipe_export(d, &EL);
 }
 
-// The pump, step 3: scoring, a piece at a time.  A batch's table in ONE launch holds the side stream for ~20 ms, and whatever a
-// slot waits for on that stream - a kernel export, a ready number - queues up behind it.  Up to max_out pieces are enqueued, one
-// running and one behind it, so that the stream has no gap between them; the ready numbers this pump call enqueued (steps 1
-// and 2) are in front of the new piece.  Behind a batch's last piece, the event that tells pump_refill its table is scored.
+// The pump, step 3 (jd_pipe.h: pipe_piece_next): the pieces that are through, then the next ones - each with its event, and behind a
+// batch's last piece the event of its table.  The ready numbers this pump call enqueued (steps 1 and 2) are in front of the new piece.
 static int pump_score(jd_dec *d)
 {
     Pipe *P = d->pipe;
-    while (P->piece_out > 0 && hipEventQuery(P->ev_piece[P->piece_turn]) == hipSuccess) { P->piece_out -= 1; P->piece_turn ^= 1; }
-    for (PipeBatch &B : P->q) {
-        while (B.rows_scored < B.rows && P->piece_out < P->max_out) {
-            const size_t n = std::min(P->piece_rows, B.rows - B.rows_scored);
-            const size_t base = (size_t)B.table * P->table_rows + B.rows_scored;
-            const int rc = launch_gmm(d->am, d->amb, B.feats + ((size_t)B.offs[0] + B.rows_scored) * (size_t)d->am->D, P->d_ident, (int)n,
-                                      P->d_ll + base * (size_t)d->am->n_gmm, d->s_gmm);
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(P->ev_piece[P->piece_turn ^ (P->piece_out & 1)], d->s_gmm));
-            B.rows_scored += n; P->piece_out += 1; d->pipe_rows_scored += (long long)n;
-            if (B.rows_scored >= B.rows) HIPCHK(hipEventRecord(P->ev_batch[(size_t)B.table], d->s_gmm));
-        }
-        if (P->piece_out >= P->max_out) break;
+    pipe_pieces_retire(*P, [&](int e) { return hipEventQuery(P->ev_piece[e]) == hipSuccess; });
+    for (PipePiece p = pipe_piece_next(*P); p.batch >= 0; p = pipe_piece_next(*P)) {
+        const float *feats = P->q[(size_t)p.batch].feats;
+        const int rc = launch_gmm(d->am, d->amb, feats + p.feat_row * (size_t)d->am->D, P->d_ident, (int)p.rows, P->d_ll + p.base_row * (size_t)d->am->n_gmm,
+                                  d->s_gmm);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(P->ev_piece[p.event], d->s_gmm));
+        pipe_piece_launched(*P, p); d->pipe_rows_scored += (long long)p.rows;
+        if (p.last) HIPCHK(hipEventRecord(P->ev_batch[(size_t)p.table], d->s_gmm));
     }
     return JD_OK;
 }
 
-// The pump, step 2: free slots take the next queued utterances, from batches whose scoring is enqueued to the last row.  Where
-// the host knows that the table is scored (the batch's event) and the slot's last result went out without the side stream, the
-// command carries the ready number the slot has: nothing to wait for.  Otherwise a new ready number, counted up behind the kernel
-// export and every scoring launch enqueued so far.
+// The pump, step 2 (jd_pipe.h: pipe_refill): free slots take the next queued utterances - new ready numbers where they are needed
+// (behind the exports and every scoring launch enqueued so far), then each utterance's first command
 static int pump_refill(jd_dec *d)
 {
     Pipe *P = d->pipe;
     Resident *R = d->res;
-    std::vector<int> who, bump;
-    std::vector<std::pair<int, int>> what;                             // (batch index in q, utterance)
-    size_t bi = 0;
-    for (int s = 0; s < P->n_slots; ++s) {
-        if (P->slot_batch_id[(size_t)s] >= 0 || P->slot_dirty[(size_t)s]) continue;
-        while (bi < P->q.size() && P->q[bi].next >= P->q[bi].n) ++bi;
-        if (bi >= P->q.size() || P->q[bi].rows_scored < P->q[bi].rows) break;
-        PipeBatch &B = P->q[bi];
-        if (P->decouple && !B.scored && hipEventQuery(P->ev_batch[(size_t)B.table]) == hipSuccess) B.scored = true;
-        const int ui = B.order[(size_t)B.next++];                      // (longest first: a batch is handed back when its LAST utterance is through)
-        B.u[(size_t)ui].state = 1; B.u[(size_t)ui].slot = s;
-        P->slot_batch_id[(size_t)s] = (int)(P->serial0 + (long long)bi); P->slot_utt[(size_t)s] = ui;
-        who.push_back(s); what.push_back(std::make_pair((int)bi, ui));
-        if (!B.scored || P->slot_kexport[(size_t)s]) bump.push_back(s);
-        P->slot_kexport[(size_t)s] = 0;
-    }
+    std::vector<PipeAssign> who;
+    std::vector<int> bump;
+    pipe_refill(*P, [&](int t) { return hipEventQuery(P->ev_batch[(size_t)t]) == hipSuccess; }, &who);
     if (who.empty()) return JD_OK;
+    for (const PipeAssign &a : who) if (a.bump) bump.push_back(a.slot);
     if (!bump.empty()) {
-        const int rc = res_bump(d, (int)bump.size(), bump.data());     // (behind the exports and every scoring launch enqueued so far)
+        const int rc = res_bump(d, (int)bump.size(), bump.data());
         if (rc) return rc;
     }
-    for (size_t k = 0; k < who.size(); ++k) {
-        const int s = who[k];
-        const PipeBatch &B = P->q[(size_t)what[k].first];
-        const PipeUtt &U = B.u[(size_t)what[k].second];
-        const int T = std::min(U.T, P->chunk);
-        R->stream[s].T_done = 0; R->stream[s].err_done = 0;
-        res_command(R, s, T, (int)U.row0, true, (P->decouple && T == U.T) ? B.table * P->max_batch + what[k].second : -1);
+    for (const PipeAssign &a : who) {
+        const PipeFirst c = pipe_refill_command(*P, a);
+        res_stream_begin(R->stream[a.slot]);
+        res_command(R, a.slot, c.T, c.row_slot, true, c.vslot);
+        P->q[(size_t)a.batch].n_commands += 1;
     }
     return JD_OK;
 }
@@ -857,18 +775,14 @@ extern "C" int jd_dec_set_pipeline(jd_dec *d, int32_t mode, int32_t depth, int32
     if (mode != JD_FLOW_SERIAL && mode != JD_FLOW_TWO_IN_FLIGHT && mode != JD_FLOW_RESIDENT)
         return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: mode %d (JD_FLOW_SERIAL, JD_FLOW_TWO_IN_FLIGHT or JD_FLOW_RESIDENT)", mode);
     if (mode == JD_FLOW_RESIDENT) {
-        if (slots == 0) slots = d->max_streams;
-        // (batches in the slots + the one being handed back + what is being scored: 256 slots and batches of 64 need ten - a batch
-        // is handed back when its longest utterance is through, ~150 ms after it was taken up at 130 us per frame)
-        if (depth == 0) depth = std::min(32, std::max(8, slots / 32 + 2));
-        if (depth < 2 || depth > 32) return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: depth %d (2..32 batches announced and not handed back)", depth);
-        if (slots < 1 || slots > d->max_streams) return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: %d slots, the decoder has %d streams", slots, d->max_streams);
-        // the slots are workgroups of a mailbox kernel: ALL of them have to be on the device at once (SLOT_WG_PER_CU per CU at most) -
-        // a workgroup that never gets a CU never answers, and the batch whose utterance was posted to it never comes back
-        if (slots > d->n_cus * SLOT_WG_PER_CU)
+        const PipeSetting S = pipe_setting(depth, slots, d->max_streams, d->n_cus, SLOT_WG_PER_CU, d->net->lazy_dev ? true : false, d->am->hybrid ? true : false);
+        depth = S.depth; slots = S.slots;
+        if (S.verdict == PIPE_SET_DEPTH) return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: depth %d (2..32 batches announced and not handed back)", depth);
+        if (S.verdict == PIPE_SET_SLOTS) return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: %d slots, the decoder has %d streams", slots, d->max_streams);
+        if (S.verdict == PIPE_SET_DEVICE)
             return jd_fail(JD_EINVAL, "jd_dec_set_pipeline: %d slots, but the device holds %d at once (%d CUs x %d workgroups of the slot kernel); "
                            "one per CU (%d) is what leaves the scoring room beside them", slots, d->n_cus * SLOT_WG_PER_CU, d->n_cus, SLOT_WG_PER_CU, d->n_cus);
-        if (d->net->lazy_dev || d->am->hybrid)
+        if (S.verdict == PIPE_SET_NOT_WITH)
             return jd_fail(JD_ESTATE, "jd_dec_set_pipeline: JD_FLOW_RESIDENT not with a lazily composed network / hybrid scoring");
     }
     if (d->res && d->res->on && !d->pipe_on) return jd_fail(JD_ESTATE, "jd_dec_set_pipeline: a broker drives this decoder's resident kernel");
@@ -900,11 +814,11 @@ extern "C" int jd_dec_pipeline_stats(const jd_dec *d, jd_pipe_stats *out)
     return JD_OK;
 }
 
-// Rows per scoring launch (jd_plan.h: plan_piece_rows): the piece between 4096 and 8192 rows - DESIGN.md 3.4's sweep: shorter
-// ones pay per launch, longer ones hold what waits behind them - whose last round of workgroups is fullest, with what the runtime
-// says of the slot kernel and of the scoring kernel on a CU.  (The kernels of 128-row tiles; the others keep PIPE_PIECE_ROWS0.)
+// Rows per scoring launch (jd_plan.h: plan_piece_rows, between jd_pipe.h's pipe_piece_bounds): the piece whose last round of
+// workgroups is fullest, with what the runtime says of the slot kernel and of the scoring kernel on a CU.  (The kernels of 128-row
+// tiles; the others plan nothing: PIPE_PIECE_ROWS0.)
 static_assert(PLAN_PIECE_TILE == GMM_ROWS2, "plan_piece_rows counts the scoring kernels' row tiles");
-static int pipe_plan_piece(const jd_dec *d, Pipe *P)
+static int pipe_plan_piece(const jd_dec *d, const Pipe *P, size_t *planned)
 {
     int occ_gmm = 0, occ_slot = 0;
     const int rc = gmm_tiles128_occupancy(d->am, d->amb, &occ_gmm);
@@ -912,34 +826,32 @@ static int pipe_plan_piece(const jd_dec *d, Pipe *P)
     if (occ_gmm <= 0) return JD_OK;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_slot, (const void *)slot_mailbox_kernel(d->am->max_n <= 5, d->models), SNT, 0));
     const int wgs = plan_resident_scoring_wgs(d->n_cus, P->n_slots, occ_slot, occ_gmm);
-    int lo = 4096, hi = 8192;
-    int groups = (d->am->n_gmm + GMM_GT - 1) / GMM_GT;
-    // (launch_gmm: a launch of fewer than 1024 tiles is one of 16-state tiles)
-    if ((long long)(hi / GMM_ROWS2) * groups < 1024) groups = (d->am->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL;
-    else lo = std::max(lo, (1024 + groups - 1) / groups * GMM_ROWS2);
-    P->piece_rows = (size_t)plan_piece_rows(groups, wgs, lo, hi);
+    const PipePieceBounds b = pipe_piece_bounds(d->am->n_gmm, GMM_GT, GMM_GT_SMALL, GMM_ROWS2);
+    *planned = (size_t)plan_piece_rows(b.groups, wgs, b.lo, b.hi);
     if (getenv("JD_VERBOSE"))
         fprintf(stderr, "pipeline: pieces of %zu rows (%d state groups, %d scoring workgroups resident beside %d slots: %d + %d per CU alone)\n",
-                P->piece_rows, groups, wgs, P->n_slots, occ_slot, occ_gmm);
+                *planned, b.groups, wgs, P->n_slots, occ_slot, occ_gmm);
     return JD_OK;
 }
 
+// sized (jd_pipe.h: pipe_size, pipe_size_piece), then its events, tables and virtual result slots
 static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
 {
     const int G = d->am->n_gmm;
-    // (tables and result slots for batches up to twice this one: a larger one later starts the pipeline again, with larger ones)
-    P->K = d->pipe_depth; P->max_batch = 2 * n_utts;
-    P->n_slots = (d->pipe_slots > 0 && d->pipe_slots <= d->max_streams) ? d->pipe_slots : d->max_streams;
-    if (const char *e = jd_dev_env("JD_PIPE_CHUNK")) { const int v = atoi(e); if (v >= 16) P->chunk = v; }   // development
-    if (const char *e = jd_dev_env("JD_PIPE_DECOUPLE")) P->decouple = atoi(e) != 0;                         // development
-    P->max_out = P->decouple ? 2 : 1;
-    if (P->decouple) { const int rc = pipe_plan_piece(d, P); if (rc) return rc; }
-    if (const char *e = jd_dev_env("JD_PIPE_PIECE")) { const int v = atoi(e); if (v >= 128) P->piece_rows = (size_t)v / GMM_ROWS2 * GMM_ROWS2; }
+    const PipeSizeIn in{d->pipe_depth, d->pipe_slots, d->max_streams, n_utts, rows, GMM_ROWS2, res_knob("JD_PIPE_CHUNK"), res_knob("JD_PIPE_DECOUPLE")};
+    const size_t V = pipe_size(*P, in);
+    size_t planned = 0;
+    if (P->decouple) { const int rc = pipe_plan_piece(d, P, &planned); if (rc) return rc; }
+    const int piece_knob = res_knob("JD_PIPE_PIECE");
+    P->piece_rows = pipe_size_piece(planned, piece_knob, GMM_ROWS2);
+    if (getenv("JD_VERBOSE"))
+        fprintf(stderr, "pipe: size depth %d slots %d streams %d utts %d rows %zu tile %d chunk %d decouple %d planned %zu piece %d -> K %d max_batch %d "
+                "n_slots %d chunk %d decouple %d max_out %d piece_rows %zu table_rows %zu vslots %zu\n", in.depth, in.pipe_slots, in.max_streams, in.n_utts,
+                in.rows, in.tile, in.chunk_knob, in.decouple_knob, planned, piece_knob, P->K, P->max_batch, P->n_slots, P->chunk, (int)P->decouple,
+                P->max_out, P->piece_rows, P->table_rows, V);
     P->ev_batch.assign((size_t)P->K, nullptr);
     for (hipEvent_t &e : P->ev_piece) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
     for (hipEvent_t &e : P->ev_batch) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return jd_fail(JD_EHIP, "hipEventCreate failed");
-    P->table_rows = ((2 * rows + 1024) + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
-    const size_t V = (size_t)P->K * P->max_batch;
     if (hipMalloc(&P->d_ll, (size_t)P->K * P->table_rows * G * sizeof(float)) != hipSuccess ||
         hipMalloc(&P->d_ident, P->table_rows * sizeof(int)) != hipSuccess ||
         hipMalloc(&P->d_vctl, V * sizeof(StreamCtl)) != hipSuccess || hipMalloc(&P->d_vresn, V * sizeof(int)) != hipSuccess ||
@@ -951,9 +863,6 @@ static int pipe_fill(jd_dec *d, Pipe *P, int n_utts, size_t rows)
     std::vector<int> ident(P->table_rows);
     for (size_t r = 0; r < P->table_rows; ++r) ident[r] = (int)r;
     HIPCHK(hipMemcpy(P->d_ident, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
-    P->table_used.assign((size_t)P->K, 0);
-    P->slot_batch_id.assign((size_t)P->n_slots, -1); P->slot_utt.assign((size_t)P->n_slots, -1); P->slot_dirty.assign((size_t)P->n_slots, 0);
-    P->slot_kexport.assign((size_t)P->n_slots, 0);
     return JD_OK;
 }
 
@@ -970,9 +879,9 @@ static int pipe_alloc(jd_dec *d, int n_utts, size_t rows)
 static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int64_t *offs, int *taken)
 {
     *taken = 0;
-    if (!d->pipe_mode || d->net->lazy_dev || d->partial_interval > 0 || d->am->hybrid || n_utts < 1) return JD_OK;
+    if (!pipe_takes(d->pipe_mode, d->net->lazy_dev ? true : false, d->partial_interval > 0, d->am->hybrid ? true : false, n_utts)) return JD_OK;
     const size_t rows = (size_t)(offs[n_utts] - offs[0]);
-    if (d->pipe && (n_utts > d->pipe->max_batch || rows > d->pipe->table_rows)) {   // a larger batch than the tables were made for: not this way
+    if (d->pipe && pipe_outgrown(*d->pipe, n_utts, rows)) {            // a larger batch than the tables were made for: the pipeline starts again
         pipe_drain(d);
         pipe_free(d);
     }
@@ -986,7 +895,7 @@ static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int6
         if (rc) return rc;
     }
     Pipe *P = d->pipe;
-    if ((int)P->q.size() >= P->K)
+    if (pipe_full(*P))
         return jd_fail(JD_ESTATE, "jd_dec_prefetch_scores: %d batches are announced and not decoded - the pipeline is %d deep (JD_PIPE_DEPTH)",
                        (int)P->q.size(), P->K);
     if (!P->on) {
@@ -997,21 +906,15 @@ static int pipe_announce(jd_dec *d, int n_utts, const float *d_feats, const int6
         rc = jd_res_start(d, P->n_slots, GMM_ROWS2);
         if (rc) { d->res_ll = nullptr; return rc; }
         P->on = true; d->pipe_on = true;
-        P->serial0 = 0; P->t_on = std::chrono::steady_clock::now(); P->frames_done = 0; d->res->run_ticks = 0;
+        pipe_started(*P); P->t_on = std::chrono::steady_clock::now(); d->res->run_ticks = 0;
     }
-    PipeBatch B;
-    B.feats = d_feats; B.n = n_utts; B.offs.assign(offs, offs + n_utts + 1);
-    int t = 0;
-    while (t < P->K && P->table_used[(size_t)t]) ++t;
-    B.table = t; P->table_used[(size_t)t] = 1;
-    B.u.resize((size_t)n_utts);
-    const long long base = (long long)t * (long long)P->table_rows;
-    for (int u = 0; u < n_utts; ++u) { B.u[(size_t)u].T = (int)(offs[u + 1] - offs[u]); B.u[(size_t)u].row0 = base + (offs[u] - offs[0]); }
-    B.order.resize((size_t)n_utts);
-    std::iota(B.order.begin(), B.order.end(), 0);
-    std::stable_sort(B.order.begin(), B.order.end(), [&](int a, int b) { return B.u[(size_t)a].T > B.u[(size_t)b].T; });
-    B.rows = rows; B.rows_scored = 0;                                  // (scored by the pump, a piece at a time, on the CUs the slots leave)
-    P->q.push_back(std::move(B));
+    const bool verbose = getenv("JD_VERBOSE") != nullptr;
+    const std::string used = verbose ? pipe_list(P->K, [&](int t) { return P->table_used[(size_t)t]; }) : std::string();
+    const PipeBatch &B = pipe_enqueue(*P, d_feats, n_utts, offs);
+    if (verbose)
+        fprintf(stderr, "pipe: announce K %d table_rows %zu used %s T %s -> table %d row0 %s order %s\n", P->K, P->table_rows, used.c_str(),
+                pipe_list(B.n, [&](int u) { return B.u[(size_t)u].T; }).c_str(), B.table, pipe_list(B.n, [&](int u) { return B.u[(size_t)u].row0; }).c_str(),
+                pipe_list(B.n, [&](int k) { return B.order[(size_t)k]; }).c_str());
     *taken = 1;
     return pipe_pump(d);
 }
@@ -1022,33 +925,22 @@ static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_
     *handled = 0;
     Pipe *P = d->pipe;
     if (!P || !P->on || P->q.empty()) return JD_OK;
-    {
-        const PipeBatch &F = P->q.front();
-        bool same = F.feats == d_feats && F.n == n_utts;
-        for (int u = 0; same && u <= n_utts; ++u) same = F.offs[(size_t)u] == offs[u];
-        if (!same) { pipe_drain(d); return JD_OK; }                    // not the announced one: as if nothing had been announced
-    }
+    if (!pipe_is_head(*P, d_feats, n_utts, offs)) { pipe_drain(d); return JD_OK; }   // not the announced one: as if nothing had been announced
     const auto w0 = std::chrono::steady_clock::now();
-    int restarts = 0;
-    long long seen_frames = -1;
-    auto t_progress = w0;
+    PipeWatch W;
     for (;;) {
         const int rc = pipe_pump(d);
         if (rc) { pipe_drain(d); return rc; }
-        if (P->q.front().n_done == P->q.front().n) break;
-        {   // (no utterance through for 30 s: something is stuck - better an error, and the other paths, than a caller that waits for ever)
-            const auto now = std::chrono::steady_clock::now();
-            if (P->frames_done != seen_frames) { seen_frames = P->frames_done; t_progress = now; }
-            else if (std::chrono::duration<double>(now - t_progress).count() > 30.0) {
-                pipe_drain(d);
-                return jd_fail(JD_EHIP, "the batch pipeline has not finished an utterance for 30 s");
-            }
+        if (pipe_head_done(*P)) break;
+        if (pipe_watch_stuck(W, P->frames_done, std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count())) {
+            pipe_drain(d);
+            return jd_fail(JD_EHIP, "the batch pipeline has not finished an utterance for 30 s");
         }
         if (d->res->on && res_any_left(d->res, P->n_slots)) {
             // the kernel has gone by itself: nobody gave it a command for 5 s (a caller that was away between two calls) - the
             // reports are taken and it comes back like behind jd_dec_quiesce; a command that was never answered is a lost workgroup
             const int rs = jd_res_stop(d);
-            if (rs || ++restarts > 3) {
+            if (rs || pipe_watch_gives_up(W)) {
                 pipe_drain(d);
                 return rs ? rs : jd_fail(JD_EHIP, "the resident search kernel keeps ending under a batch");
             }
@@ -1056,26 +948,23 @@ static int pipe_decode(jd_dec *d, int n_utts, const float *d_feats, const int64_
         }
         std::this_thread::sleep_for(std::chrono::microseconds(20));
     }
-    PipeBatch &F = P->q.front();
-    // (the kernel's exports.  What the slots exported themselves is in memory since their reports: nothing to wait for, and the
-    // side stream has pieces of later batches on it)
-    if (F.n_kexport > 0) HIPCHK(hipStreamSynchronize(d->s_gmm));
-    std::vector<int> slot_of((size_t)n_utts);
-    for (int u = 0; u < n_utts; ++u) slot_of[(size_t)u] = F.u[(size_t)u].slot;
+    const PipeBatch &F = P->q.front();
+    if (pipe_head_needs_sync(*P)) HIPCHK(hipStreamSynchronize(d->s_gmm));      // (the kernel's exports)
+    std::vector<int> slot_of;
+    pipe_head_slots(*P, &slot_of);
     if ((size_t)n_utts > d->results.size()) d->results.resize((size_t)n_utts);
     d->timing = jd_timing();
-    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), F.table * P->max_batch, n_utts, out, 0, nullptr,
+    const int rc = fetch_results_from(d, P->d_vctl, P->d_vresn, P->d_vres, slot_of.data(), pipe_vslot(*P, F, 0), n_utts, out, 0, nullptr,
                                       P->d_vres_model);
     for (int u = 0; u < n_utts; ++u) d->timing.search_frames += F.u[(size_t)u].T;
     d->timing.gmm_frames = d->timing.search_frames; d->timing.gmm_states = d->am->n_gmm;
     d->timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
     d->timing.search_ms = d->timing.total_ms; d->timing.search_launches = 0; d->timing.cluster_wgs = 1; d->timing.prefetched = 1;
     d->load_sum = d->load_frames = 0.0;
-    P->table_used[(size_t)F.table] = 0;
-    P->q.pop_front();
+    if (getenv("JD_VERBOSE"))
+        fprintf(stderr, "pipe: back serial %lld table %d utts %d commands %d pieces %d -> %d\n", P->serial0, F.table, F.n, F.n_commands, F.n_pieces, rc);
     d->pipe_batches_back += 1;
-    P->serial0 += 1;
-    if (P->q.empty()) pipe_drain(d);                                   // nothing announced behind it: the kernel leaves the device
+    if (pipe_pop(*P)) pipe_drain(d);                                   // nothing announced behind it: the kernel leaves the device
     *handled = 1;
     return rc;
 }
