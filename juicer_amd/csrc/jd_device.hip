@@ -56,6 +56,7 @@
 #include "jd_arena.h"           // the sizes and the layout of the stream arenas (ensure_arenas), a wave's likelihood tables (WavePlan, plan_wave)
 #include "jd_ahead.h"           // working ahead: the queue of announced batches, tables and banks, decode_wave's decisions
 #include "jd_pipe.h"            // batches through the resident slot kernel: the mailbox record, the slot pipeline's bookkeeping and pump decisions
+#include "jd_push.h"            // the streaming interface: a stream's record, argument checks, PARTIAL_DECODING's schedule, packing, k_partial_many's layout
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -295,23 +296,16 @@ struct jd_dec {
                                           // JD_PF_REBALANCE=0: never while the scoring runs, =1: like any other launch
     double gmm_ms_per_row = 0.0, search_ms_per_frame = 0.0;   // measured on this decoder's last waves (scoring on its own / search)
     int *h_resident = nullptr, *d_resident = nullptr; int launch_seq = 0;   // host-mapped word: k_search's last workgroup has started
-    // streaming API state
-    std::vector<int> stream_T;                 // frames pushed so far
-    std::vector<int> stream_started;
-    std::vector<int> stream_open;            // frames pushed since the stream's init, not finished yet (jd_dec_set_output_level)
+    // streaming API state: a record per stream (jd_push.h)
+    std::vector<PushStream> push;
     // PARTIAL_DECODING (WFSTDecoderLite.h:199-205), streaming API
     int partial_interval = 0;                  // partialTraceInterval
-    std::vector<int> last_collect, last_trace; // lastPathCollectFrame, lastPartialTraceFrame
-    std::vector<int> n_collect_host;           // collections of the stream's utterance so far (jd_stream_collect_info)
-    std::vector<std::vector<int32_t>> partial_label, partial_time;   // partialPaths, oldest first
     int *d_partial_out = nullptr;
     // ... k_partial_many's buffers (trace_partial_many): [int4 work list][{found, n} heads][staging], for max_streams entries, on the
     // device and pinned on the host
     int *d_pmany = nullptr, *h_pmany = nullptr;
-    // ... the model-level list of the same traces (jd_stream_partial_models), oldest first, and k_partial's export of it,
+    // ... k_partial's export of the model-level list of the same traces (PushStream::partial_m, jd_stream_partial_models),
     // [model, label, time, score, ac, lm][res_cap] (model-level output only, allocated with d_res_model)
-    struct PartialModels { std::vector<int32_t> model, label, time; std::vector<float> score, ac, lm; };
-    std::vector<PartialModels> partial_m;
     int *d_partial_model = nullptr;
     bool return_on_collect = false, collected_now = false;   // jd_stream_push: launch_search comes back after a collection by the count rule
     float *d_push = nullptr; size_t push_cap = 0;
@@ -365,6 +359,19 @@ static int dupload(jd_dec *d, T **p, const T *src, size_t n)
     int rc = dmalloc(d, p, n);
     if (rc) return rc;
     HIPCHK(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return JD_OK;
+}
+
+// A buffer that is replaced by a larger one of n elements (what it held is not kept; pinned: host memory): free, forget pointer and
+// capacity, allocate, remember the capacity - a failed allocation leaves no pointer behind
+template <typename T>
+static int dregrow(T **p, size_t *cap, size_t n, bool pinned)
+{
+    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr; *cap = 0;
+    if (pinned) HIPCHK(hipHostMalloc((void **)p, n * sizeof(T)));
+    else HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
+    *cap = n;
     return JD_OK;
 }
 
@@ -566,17 +573,9 @@ static int dec_create_streams(jd_dec *d)
         return jd_fail(JD_EHIP, "hipHostMalloc failed: %s", hipGetErrorString(e));
     *d->h_resident = 0;
     const size_t n = (size_t)d->max_streams;
-    d->stream_T.assign(n, 0);
-    d->stream_started.assign(n, 0);
-    d->stream_open.assign(n, 0);
+    d->push.assign(n, PushStream());
     d->lazy_in.assign(n, 0);
     d->stream_dirty.assign(n, 0);
-    d->last_collect.assign(n, -1);
-    d->n_collect_host.assign(n, 0);
-    d->last_trace.assign(n, -1);
-    d->partial_label.resize(n);
-    d->partial_time.resize(n);
-    d->partial_m.resize(n);
     d->results.resize(n);
     return JD_OK;
 }
@@ -1404,7 +1403,7 @@ extern "C" int jd_decode_batch_device(jd_dec *d, int32_t n_utts, const float *d_
     // (lazily composed) network now - before the first jd_lazy_enter, which starts a new arena generation only when
     // nobody is inside, or a full network would fail this call and, the release below never reached, every later one
     for (int s = 0; s < d->max_streams; ++s) {
-        d->stream_started[(size_t)s] = 0; d->stream_T[(size_t)s] = 0; d->stream_open[(size_t)s] = 0;
+        d->push[(size_t)s].taken_over();
         if (d->lazy_in[(size_t)s]) { d->lazy_in[(size_t)s] = 0; jd_lazy_leave(d->net, 1); }
     }
     // Scoring ahead inside the batch: every wave but the last announces the wave behind it, whose table is then scored

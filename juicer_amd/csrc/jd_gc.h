@@ -447,7 +447,7 @@ __global__ __launch_bounds__(1024) void k_partial(DecConst C, StreamCtl *ctl, St
 // entry: a trace follows the one before it by a trace interval, a few hundred frames at most in live use, and a word takes a few
 // frames at least, so 32 new words per trace is more than live speech gives (130 words a copy for a 16-caller tick: 8 KiB); a
 // stream with more (a first explicit trace late in a long utterance) is fetched from its result arrays instead.
-#define PARTIAL_SHARE 32
+// (PARTIAL_SHARE: jd_prep.h; the host's reading of this layout: partial_many_layout, partial_many_reply, jd_push.h)
 template <int NE>
 __global__ __launch_bounds__(1024) void k_partial_many(DecConst C, StreamCtl *ctl, StreamDev *streams, const int4 *work, int n_work, int *out)
 {
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(1024) void k_partial_many(DecConst C, StreamCtl *ct
     const int have = w.z;
     if (n <= have || n - have > PARTIAL_SHARE || n > S.res_cap) return;
     __syncthreads();                                                   // (n is the same in every thread) the chain is in res_label / res_time
-    int *stage = out + 2 * (size_t)n_work + 2 * (size_t)PARTIAL_SHARE * i;
+    int *stage = out + 2 * (size_t)n_work + 2 * (size_t)PARTIAL_SHARE * i;          // (the host: partial_many_stage_at, jd_push.h)
     for (int k = have + (int)threadIdx.x; k < n; k += blockDim.x) {
         stage[2 * (k - have)] = S.res_label[k]; stage[2 * (k - have) + 1] = S.res_time[k];
     }

@@ -101,7 +101,7 @@ static bool res_harvest(jd_dec *d, int s)
     // whether or not anybody fetches its result)
     if (S.err_done != 0) d->stream_dirty[(size_t)s] = 1;
     R->run_ticks += R->h_done[s].run_ticks;
-    d->stream_T[(size_t)s] = S.T_done;
+    d->push[(size_t)s].T = S.T_done;
     return true;
 }
 
@@ -190,7 +190,7 @@ static int res_fill(jd_dec *d, Resident *R, int n_streams, int rows)
         return jd_fail(JD_ENOMEM, "jd_res_start: no memory for %d streams x 2 x %d rows", n_streams, rows);
     *R->h_beat = 0u;
     R->stream.resize((size_t)n_streams);
-    for (int t = 0; t < n_streams; ++t) R->stream[t].reset(&d->stream_T[(size_t)t]);
+    for (int t = 0; t < n_streams; ++t) R->stream[t].reset(&d->push[(size_t)t].T);
     std::vector<int> ident(tr);            // the row table of every scoring launch: row r of the table is row r of the features
     for (size_t r = 0; r < tr; ++r) ident[r] = (int)r;
     HIPCHK(hipMemcpy(R->d_src, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -454,7 +454,7 @@ int jd_res_init(jd_dec *d, int s)
     }
     hipLaunchKernelGGL(jd_mark_init_kernel, dim3(1), dim3(64), 0, d->s_gmm, d->d_ctl, s, 1);
     HIPCHK(hipGetLastError());
-    d->stream_T[(size_t)s] = 0; d->stream_started[(size_t)s] = 1; d->stream_open[(size_t)s] = 0;
+    d->push[(size_t)s].begin();
     R->stream[s].T_posted = 0; R->stream[s].T_done = 0; R->stream[s].err_done = 0;
     return res_bump(d, 1, &s);
 }
@@ -986,7 +986,7 @@ extern "C" int jd_dec_set_output_level(jd_dec *d, int32_t level)
         return jd_fail(JD_EINVAL, "jd_dec_set_output_level: partial traces (jd_dec_set_partial_interval) are not available with model-level output");
     // (an utterance under way keeps the records of the level it began with: its result would mix the two)
     for (int s = 0; s < d->max_streams; ++s)
-        if (d->stream_started[(size_t)s] && d->stream_open[(size_t)s])
+        if (d->push[(size_t)s].started && d->push[(size_t)s].open)
             return jd_fail(JD_ESTATE, "jd_dec_set_output_level: stream %d has an utterance under way (frames pushed since its jd_stream_init, "
                            "no jd_stream_finish yet) - between utterances only", s);
     int rc = check_device(d->device);

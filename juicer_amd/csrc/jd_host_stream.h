@@ -1,7 +1,9 @@
 // jd_host_stream.h - the IDecoder seam of the C ABI (included by jd_device.hip): jd_stream_init / _push / _finish (IDecoder::init /
 // processFrame / finish, src/Decoder.h:18-30, src/WFSTDecoderLite.cpp:139-372), jd_streams_push (several callers' frames in one launch),
 // PARTIAL_DECODING (jd_dec_set_partial_interval, jd_stream_partial, jd_streams_trace: src/WFSTDecoderLite.cpp:822-896) for one stream
-// and for a list of them, and the collection bookkeeping.
+// and for a list of them, and the collection bookkeeping.  What is DECIDED here - the stream's record, the argument checks, where a
+// chunk or a round ends and what the control words behind a launch mean, the packing of a call, k_partial_many's layout - is jd_push.h
+// (plain functions, tested on the CPU); this file makes the copies, launches and synchronisations between those steps.
 #pragma once
 
 extern "C" int jd_stream_init(jd_dec *d, int32_t s)
@@ -27,14 +29,34 @@ extern "C" int jd_stream_init(jd_dec *d, int32_t s)
     rc = mark_init(d, s, 1, d->s_search);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(d->s_search));
-    d->stream_T[(size_t)s] = 0;
-    d->stream_started[(size_t)s] = 1;
-    d->stream_open[(size_t)s] = 0;
-    d->last_collect[(size_t)s] = -1; d->last_trace[(size_t)s] = -1;    // WFSTDecoderLite.cpp:179-181, 202-206
-    d->n_collect_host[(size_t)s] = 0;
-    d->partial_label[(size_t)s].clear(); d->partial_time[(size_t)s].clear();
-    d->partial_m[(size_t)s] = jd_dec::PartialModels();
+    d->push[(size_t)s].init();
     return JD_OK;
+}
+
+// (JD_VERBOSE) "push:" lines: what jd_push.h's schedule was given -> what it returned (tests/test_gpu_push_inputs.py)
+static bool push_verbose() { return getenv("JD_VERBOSE") != nullptr; }
+// the control words of a stream that jd_push.h reads; ref: the decoder keeps the reference's counts
+static PushCtl push_ctl(const StreamCtl &c, bool ref)
+{
+    return PushCtl{c.error, c.frame, c.n_collect, ref ? c.n_paths_ref : c.n_paths, ref ? c.path_new_ref : c.path_new};
+}
+static PushAfter push_after_launch(int s, const PushStream &P, const PushCtl &c, int limit, int fail_T, bool by_flag, bool flag, bool verbose)
+{
+    const PushAfter a = push_after(P, c, limit, fail_T, by_flag, flag);
+    if (verbose)
+        fprintf(stderr, "push: after stream %d error %d frame %d n_collect %d n_path %d n_path_new %d limit %d fail_T %d by_flag %d flag %d host_n_collect %d "
+                "last_collect %d -> failed %d at %d collected %d host_collects %d T %d\n", s, c.error, c.frame, c.n_collect, c.n_path, c.n_path_new, limit, fail_T,
+                (int)by_flag, (int)flag, P.n_collect, P.last_collect, (int)a.failed, a.at, (int)a.collected, (int)a.host_collects, a.T);
+    return a;
+}
+static bool push_book(int s, PushStream &P, int at, int interval, bool verbose)
+{
+    const int last_trace = P.last_trace;
+    const bool due = push_book_collection(P, at, interval);
+    if (verbose)
+        fprintf(stderr, "push: book stream %d at %d last_trace %d interval %d -> due %d last_collect %d n_collect %d\n", s, at, last_trace, interval, (int)due,
+                P.last_collect, P.n_collect);
+    return due;
 }
 
 // tracePartialPath (:824-868) on stream s at the frame it has reached; extends the stream's
@@ -44,7 +66,8 @@ static int trace_partial(jd_dec *d, int s, int *found)
 {
     if (!d->d_partial_out) { int rc = dmalloc(d, &d->d_partial_out, 3); if (rc) return rc; }
     if (d->models && !d->d_partial_model) { int rc = dmalloc(d, &d->d_partial_model, (size_t)6 * d->res_cap); if (rc) return rc; }
-    std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
+    PushStream &S = d->push[(size_t)s];
+    std::vector<int32_t> &L = S.partial_label, &Tm = S.partial_time;
     const int last_frame = Tm.empty() ? -1 : Tm.back();
     int *pm = d->models ? d->d_partial_model : nullptr;
     hipStream_t st = d->s_search;
@@ -56,7 +79,7 @@ static int trace_partial(jd_dec *d, int s, int *found)
     int ho[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(ho, d->d_partial_out, (pm ? 3 : 2) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    d->last_trace[(size_t)s] = d->stream_T[(size_t)s] - 1;             // :867
+    S.last_trace = S.T - 1;                                            // :867
     if (found) *found = ho[0];
     if (!ho[0]) return JD_OK;
     if (ho[1] > d->res_cap) return jd_fail(JD_ENOMEM, "stream %d: partial path has %d records (> %d)", s, ho[1], d->res_cap);
@@ -72,7 +95,7 @@ static int trace_partial(jd_dec *d, int s, int *found)
         std::vector<int32_t> h(6 * nm);
         if (nm)
             HIPCHK(hipMemcpy2D(h.data(), nm * 4, pm, (size_t)d->res_cap * 4, nm * 4, 6, hipMemcpyDeviceToHost));
-        jd_dec::PartialModels &P = d->partial_m[(size_t)s];
+        PushModels &P = S.partial_m;
         const float *f = (const float *)h.data();
         P.model.assign(h.begin(), h.begin() + nm); P.label.assign(h.begin() + nm, h.begin() + 2 * nm);
         P.time.assign(h.begin() + 2 * nm, h.begin() + 3 * nm);
@@ -82,52 +105,49 @@ static int trace_partial(jd_dec *d, int s, int *found)
 }
 
 // trace_partial for a list of streams (each once; word level), each at the frame it has reached: ONE k_partial_many launch and ONE
-// copy back - the {found, n} heads and, behind them, the records that are new to the host (k_partial_many, jd_gc.h).  found
-// (or null): per entry.  A stream whose trace fails (a chain longer than the result capacity) does not keep the others from
-// theirs; the first such error is returned.
+// copy back - the {found, n} heads and, behind them, the records that are new to the host (k_partial_many, jd_gc.h; the layout and
+// what a reply means: jd_push.h).  found (or null): per entry.  A stream whose trace fails (a chain longer than the result capacity)
+// does not keep the others from theirs; the first such error is returned.
+static_assert(sizeof(PartialRequest) == sizeof(int4), "k_partial_many's work list is int4");
 static int trace_partial_many(jd_dec *d, const std::vector<int> &ss, int32_t *found)
 {
     const int n = (int)ss.size();
     if (n == 0) return JD_OK;
-    const size_t M = (size_t)d->max_streams, head_at = 4 * M, per = 2 + 2 * (size_t)PARTIAL_SHARE, words = head_at + per * M;
-    if (!d->d_pmany) { int rc = dmalloc(d, &d->d_pmany, words); if (rc) return rc; }
-    if (!d->h_pmany) HIPCHK(hipHostMalloc((void **)&d->h_pmany, words * sizeof(int)));
-    int4 *hw = (int4 *)d->h_pmany;
-    for (int i = 0; i < n; ++i) {
-        const std::vector<int32_t> &L = d->partial_label[(size_t)ss[(size_t)i]], &Tm = d->partial_time[(size_t)ss[(size_t)i]];
-        hw[i] = make_int4(ss[(size_t)i], Tm.empty() ? -1 : Tm.back(), (int)L.size(), 0);
-    }
+    const PartialManyLayout Y = partial_many_layout(d->max_streams);
+    if (!d->d_pmany) { int rc = dmalloc(d, &d->d_pmany, Y.words); if (rc) return rc; }
+    if (!d->h_pmany) HIPCHK(hipHostMalloc((void **)&d->h_pmany, Y.words * sizeof(int)));
+    PartialRequest *hw = (PartialRequest *)d->h_pmany;
+    for (int i = 0; i < n; ++i) hw[i] = partial_many_request(d->push[(size_t)ss[(size_t)i]], ss[(size_t)i]);
     hipStream_t st = d->s_search;
-    int *d_out = d->d_pmany + head_at, *ho = d->h_pmany + head_at;
+    int *d_out = d->d_pmany + Y.head_at, *ho = d->h_pmany + Y.head_at;
     HIPCHK(hipMemcpyAsync(d->d_pmany, hw, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
     if (d->am->max_n <= 5)
         hipLaunchKernelGGL(k_partial_many<3>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmany, n, d_out);
     else hipLaunchKernelGGL(k_partial_many<6>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmany, n, d_out);
     HIPCHK(hipGetLastError());
     d->timing.trace_launches += 1;
-    HIPCHK(hipMemcpyAsync(ho, d_out, per * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ho, d_out, Y.reply_words(n) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     int rc_all = JD_OK;
     for (int i = 0; i < n; ++i) {
         const int s = ss[(size_t)i], fnd = ho[2 * i], len = ho[2 * i + 1];
-        d->last_trace[(size_t)s] = d->stream_T[(size_t)s] - 1;        // :867
+        PushStream &S = d->push[(size_t)s];
+        S.last_trace = S.T - 1;                                        // :867
         if (found) found[i] = fnd;
-        if (!fnd) continue;
-        if (len > d->res_cap) {
+        const int have = (int)S.partial_label.size();
+        const PartialReply reply = partial_many_reply(fnd, len, have, d->res_cap);
+        if (reply == PARTIAL_NOT_FOUND) continue;
+        if (reply == PARTIAL_TOO_LONG) {
             const int rc = jd_fail(JD_ENOMEM, "stream %d: partial path has %d records (> %d)", s, len, d->res_cap);
             if (!rc_all) rc_all = rc;
             continue;
         }
-        std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
-        const int have = (int)L.size();
-        L.resize((size_t)len); Tm.resize((size_t)len);
-        if (len - have <= PARTIAL_SHARE) {                             // (the records traced before are the chain's prefix)
-            const int *stage = ho + 2 * (size_t)n + 2 * (size_t)PARTIAL_SHARE * i;
-            for (int k = have; k < len; ++k) { L[(size_t)k] = stage[2 * (k - have)]; Tm[(size_t)k] = stage[2 * (k - have) + 1]; }
-        } else {                                                       // more than its share of the staging area: from its result arrays
+        S.partial_label.resize((size_t)len); S.partial_time.resize((size_t)len);
+        if (reply == PARTIAL_FROM_STAGE) partial_many_take(S, have, len, ho + partial_many_stage_at(n, i));
+        else {
             const int *base = d->d_res + (size_t)s * 5 * d->res_cap;
-            HIPCHK(hipMemcpy(L.data(), base, (size_t)len * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(Tm.data(), base + d->res_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(S.partial_label.data(), base, (size_t)len * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(S.partial_time.data(), base + d->res_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
         }
     }
     return rc_all;
@@ -135,38 +155,31 @@ static int trace_partial_many(jd_dec *d, const std::vector<int> &ss, int32_t *fo
 
 extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames)
 {
-    if (!d || s < 0 || s >= d->max_streams || n_frames < 0 || (n_frames > 0 && !frames))
-        return jd_fail(JD_EINVAL, "jd_stream_push: bad argument");
-    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_push before jd_stream_init");
+    const PushCheck chk = push_check_one(d ? &d->push : nullptr, s, frames != nullptr, n_frames);
+    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_stream_push before jd_stream_init");
+    if (chk.verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_stream_push: bad argument");
     int rc = check_device(d->device);
     if (rc) return rc;
-    if (n_frames > 0) d->stream_open[(size_t)s] = 1;
+    PushStream &P = d->push[(size_t)s];
+    if (n_frames > 0) P.open = 1;
     const int D = d->am->D, G = d->am->n_gmm, Fc = d->Fc;
+    const bool verbose = push_verbose();
     hipStream_t st = d->s_search;
     pf_discard(d);                                                     // (the streaming path scores into table 0)
     for (int done = 0, n = 0; done < n_frames; done += n) {
-        n = std::min(Fc, n_frames - done);
         // PARTIAL_DECODING rides on the path collection (:362-368): a chunk ends at the frame rule's frame
-        // (the first frame f with f - lastPathCollectFrame > 100)
-        const int f_collect = d->last_collect[(size_t)s] + 101;
-        if (d->partial_interval > 0) n = std::min(n, std::max(1, f_collect + 1 - d->stream_T[(size_t)s]));
-        if ((size_t)n * D > d->push_cap) {
-            if (d->d_push) (void)hipFree(d->d_push);
-            HIPCHK(hipMalloc(&d->d_push, (size_t)Fc * D * sizeof(float)));
-            d->push_cap = (size_t)Fc * D;
-        }
+        n = push_chunk_frames(Fc, n_frames - done, d->partial_interval, P.last_collect, P.T);
+        if (verbose)
+            fprintf(stderr, "push: chunk stream %d Fc %d left %d interval %d last_collect %d T %d -> n %d\n", s, Fc, n_frames - done, d->partial_interval,
+                    P.last_collect, P.T, n);
+        if ((size_t)n * D > d->push_cap) { rc = dregrow(&d->d_push, &d->push_cap, (size_t)Fc * D, false); if (rc) return rc; }
         HIPCHK(hipMemcpyAsync(d->d_push, frames + (size_t)done * D, (size_t)n * D * sizeof(float),
                               hipMemcpyHostToDevice, st));
         std::vector<int> src((size_t)Fc, -1);
         for (int i = 0; i < n; ++i) src[(size_t)i] = i;
-        if ((size_t)Fc > d->row_src_cap[0]) {
-            if (d->d_row_src[0]) (void)hipFree(d->d_row_src[0]);
-            d->d_row_src[0] = nullptr; d->row_src_cap[0] = 0;
-            HIPCHK(hipMalloc(&d->d_row_src[0], (size_t)Fc * sizeof(int)));
-            d->row_src_cap[0] = (size_t)Fc;
-        }
+        if ((size_t)Fc > d->row_src_cap[0]) { rc = dregrow(&d->d_row_src[0], &d->row_src_cap[0], (size_t)Fc, false); if (rc) return rc; }
         HIPCHK(hipMemcpyAsync(d->d_row_src[0], src.data(), (size_t)Fc * sizeof(int), hipMemcpyHostToDevice, st));
-        const int f0 = d->stream_T[(size_t)s];
+        const int f0 = P.T;
         const int Tnew = f0 + n;
         HIPCHK(hipMemcpyAsync(d->d_T + s, &Tnew, sizeof(int), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(jd_set_T_kernel, dim3(1), dim3(64), 0, st, d->d_ctl, s, 1, d->d_T + s);
@@ -175,7 +188,7 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
         if (d->partial_interval <= 0) {
             rc = launch_search(d, std::vector<int2>(1, make_int2(s, 0)), d->d_ll[0], (long long)Fc * G, f0, Tnew, st);
             if (rc) { d->stream_dirty[(size_t)s] = 1; return rc; }
-            d->stream_T[(size_t)s] = Tnew;
+            P.T = Tnew;
             continue;
         }
         // PARTIAL_DECODING: collectPaths runs after a frame when the count rule fires (path_rule_fires, evaluated by
@@ -188,32 +201,25 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
             if (rc) { d->stream_dirty[(size_t)s] = 1; return rc; }
             StreamCtl hc;
             HIPCHK(hipMemcpy(&hc, d->d_ctl + s, sizeof hc, hipMemcpyDeviceToHost));
-            if (hc.error != 0) { d->stream_T[(size_t)s] = Tnew; d->stream_dirty[(size_t)s] = 1; break; }   // (reported by jd_stream_finish)
-            const int at = hc.frame - 1;                               // the last frame processed
             // (with the reference's counts a collection that only the arena asked for is none of the reference's: it neither
-            // counts nor carries a trace, and the launch goes on behind it)
+            // counts nor carries a trace, and the launch goes on behind it - so the launch's own flag serves without them only)
             const bool ref = d->C.pcount != nullptr;
-            bool collected = ref ? hc.n_collect > d->n_collect_host[(size_t)s] : d->collected_now;
-            if (!collected && hc.frame >= Tnew && (at - d->last_collect[(size_t)s] > 100 ||
-                                                   path_rule_fires(ref ? hc.n_paths_ref : hc.n_paths, ref ? hc.path_new_ref : hc.path_new))) {
+            const PushAfter a = push_after_launch(s, P, push_ctl(hc, ref), Tnew, Tnew, !ref, d->collected_now, verbose);
+            if (a.failed) { P.T = a.T; d->stream_dirty[(size_t)s] = 1; break; }   // (reported by jd_stream_finish)
+            if (a.host_collects) {
                 // the rule fires behind the chunk's last frame (the kernel looks before a frame, not after the last one)
                 DecConst Cg = d->C;
                 Cg.gc_threshold = -1;                                  // (every started stream collects)
                 launch_gc(Cg, d->d_ctl, d->d_streams, nullptr, 1, s, d->am->max_n <= 5, d->n_cus, st);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));
-                collected = true;
             }
-            d->stream_T[(size_t)s] = hc.frame;
-            if (collected) {
-                d->last_collect[(size_t)s] = at;                       // :746
-                d->n_collect_host[(size_t)s] += 1;
-                if (at - d->last_trace[(size_t)s] > d->partial_interval) {
-                    rc = trace_partial(d, s, nullptr);
-                    if (rc) return rc;
-                }
+            P.T = a.T;
+            if (a.collected && push_book(s, P, a.at, d->partial_interval, verbose)) {
+                rc = trace_partial(d, s, nullptr);
+                if (rc) return rc;
             }
-            if (hc.frame >= Tnew) break;
+            if (a.T >= Tnew) break;
         }
     }
     return JD_OK;
@@ -223,7 +229,7 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
 // kernel and searched by ONE persistent launch, every stream a cluster of its own - what a broker that serves
 // many IDecoder instances (jd_broker_*, jd_broker.cpp) makes of the pushes that have arrived since its last tick.
 // A call takes any number of frames per stream (the tables are sized for the call).  The streams may sit at
-// different frames: row r of the common table is frame stream_T[s] + (r - first row of s) of stream s.
+// different frames: row r of the common table is frame T + (r - first row of s) of stream s (push_pack).
 // PARTIAL_DECODING (jd_dec_set_partial_interval > 0): the rows are scored once and the streams advance in ROUNDS, in each of which
 // every stream is served as jd_stream_push's loop serves its one - streams_push_rounds.
 
@@ -231,34 +237,34 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
 // frames, target: the frame each is to reach.  A round is ONE launch_search that comes back after a collection, one copy of the
 // control blocks, at most one launch_gc (the streams whose frame or count rule fires behind their last frame of the round) and at
 // most one k_partial_many launch (the streams that collected and whose trace is due); a stream's frame limit for the round is
-// the frame rule's frame, so a round is to the stream what a chunk is to jd_stream_push.
+// the frame rule's frame, so a round is to the stream what a chunk is to jd_stream_push (push_round_plan, push_after).
 static int streams_push_rounds(jd_dec *d, const std::vector<int2> &work_all, const std::vector<int> &target, hipStream_t st)
 {
-    const bool ne3 = d->am->max_n <= 5, ref = d->C.pcount != nullptr;
+    const bool ne3 = d->am->max_n <= 5, ref = d->C.pcount != nullptr, verbose = push_verbose();
     const long long G = d->am->n_gmm;
     const size_t nw = work_all.size();
-    std::vector<int> hT((size_t)d->max_streams), limit(nw, 0), gc_list, tr_list;
+    std::vector<int> ws(nw), gc_list, tr_list;
+    for (size_t k = 0; k < nw; ++k) ws[k] = work_all[k].x;
     std::vector<char> out(nw, 0);                                      // failed in this call: left out of the later rounds
-    std::vector<size_t> act;
+    PushRound R;
     std::vector<int2> work;
-    std::vector<double> weight;
     std::vector<StreamCtl> hc;
+    std::vector<PushAfter> after;
     std::vector<int4> gw;
     for (;;) {
-        act.clear(); work.clear(); weight.clear();
-        int f_end = 0, s_lo = d->max_streams, s_hi = -1;
-        for (int s = 0; s < d->max_streams; ++s) hT[(size_t)s] = d->stream_T[(size_t)s];
-        for (size_t k = 0; k < nw; ++k) {
-            const int s = work_all[k].x, at = d->stream_T[(size_t)s];
-            if (out[k] || at >= target[k]) continue;
-            // the chunk ends at the frame rule's frame: the first frame f with f - lastPathCollectFrame > 100
-            limit[k] = std::min(target[k], std::max(at + 1, d->last_collect[(size_t)s] + 102));
-            hT[(size_t)s] = limit[k];
-            act.push_back(k); work.push_back(work_all[k]); weight.push_back((double)(limit[k] - at));
-            f_end = std::max(f_end, limit[k]); s_lo = std::min(s_lo, s); s_hi = std::max(s_hi, s);
-        }
-        if (act.empty()) break;
-        HIPCHK(hipMemcpyAsync(d->d_T, hT.data(), hT.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        push_round_plan(d->push, ws, target, out, &R);
+        if (verbose)
+            fprintf(stderr, "push: round T %s last_collect %s work %s target %s out %s -> act %s limit %s hT %s f_end %d s_lo %d s_hi %d\n",
+                    pipe_list(d->max_streams, [&](int s) { return d->push[(size_t)s].T; }).c_str(),
+                    pipe_list(d->max_streams, [&](int s) { return d->push[(size_t)s].last_collect; }).c_str(), pipe_list((int)nw, [&](int k) { return ws[(size_t)k]; }).c_str(),
+                    pipe_list((int)nw, [&](int k) { return target[(size_t)k]; }).c_str(), pipe_list((int)nw, [&](int k) { return out[(size_t)k]; }).c_str(),
+                    pipe_list((int)R.act.size(), [&](int a) { return R.act[(size_t)a]; }).c_str(),
+                    pipe_list((int)R.act.size(), [&](int a) { return R.limit[R.act[(size_t)a]]; }).c_str(),
+                    pipe_list(d->max_streams, [&](int s) { return R.hT[(size_t)s]; }).c_str(), R.f_end, R.s_lo, R.s_hi);
+        if (R.act.empty()) break;
+        work.clear();
+        for (size_t k : R.act) work.push_back(work_all[k]);
+        HIPCHK(hipMemcpyAsync(d->d_T, R.hT.data(), R.hT.size() * sizeof(int), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(jd_set_T_kernel, dim3((d->max_streams + 63) / 64), dim3(64), 0, st, d->d_ctl, 0, d->max_streams, d->d_T);
         HIPCHK(hipGetLastError());
         // (no re-planning cuts under way: a stream cut short stops at a frame of the launch's choosing, and a rule that fires behind
@@ -266,29 +272,21 @@ static int streams_push_rounds(jd_dec *d, const std::vector<int2> &work_all, con
         // stream's last frame of the round only)
         const int rebalance = d->rebalance;
         d->rebalance = 0; d->return_on_collect = true; d->collected_now = false;
-        int rc = launch_search(d, work, d->d_ll[0], G, 0, f_end, st, &weight);
+        int rc = launch_search(d, work, d->d_ll[0], G, 0, R.f_end, st, &R.weight);
         d->rebalance = rebalance; d->return_on_collect = false;
         if (rc) { (void)hipStreamSynchronize(st); for (const int2 &w : work) d->stream_dirty[(size_t)w.x] = 1; return rc; }
-        hc.resize((size_t)(s_hi - s_lo + 1));
-        HIPCHK(hipMemcpy(hc.data(), d->d_ctl + s_lo, hc.size() * sizeof(StreamCtl), hipMemcpyDeviceToHost));
-        gc_list.clear(); tr_list.clear();
-        std::vector<char> collected(act.size(), 0);
-        for (size_t a = 0; a < act.size(); ++a) {
-            const size_t k = act[a];
-            const int s = work_all[k].x;
-            const StreamCtl &c = hc[(size_t)(s - s_lo)];
-            if (c.error != 0) { d->stream_T[(size_t)s] = target[k]; d->stream_dirty[(size_t)s] = 1; out[k] = 1; continue; }   // (reported by jd_stream_finish)
-            const int at = c.frame - 1;                                // the last frame processed
-            // whether a collection of the reference's ran on THIS stream: its own count (k_gc_remap counts the reference's
-            // collections where the decoder keeps the reference's counts - one that only the arena asked for is none of
-            // them and carries no trace - and every collection where it does not)
-            collected[a] = c.n_collect > d->n_collect_host[(size_t)s];
-            if (!collected[a] && c.frame >= limit[k] && (at - d->last_collect[(size_t)s] > 100 ||
-                                                         path_rule_fires(ref ? c.n_paths_ref : c.n_paths, ref ? c.path_new_ref : c.path_new))) {
-                gc_list.push_back(s);                                  // the rule fires behind the round's last frame
-                collected[a] = 1;
-            }
-            d->stream_T[(size_t)s] = c.frame;
+        hc.resize((size_t)(R.s_hi - R.s_lo + 1));
+        HIPCHK(hipMemcpy(hc.data(), d->d_ctl + R.s_lo, hc.size() * sizeof(StreamCtl), hipMemcpyDeviceToHost));
+        gc_list.clear(); tr_list.clear(); after.clear();
+        for (size_t k : R.act) {
+            const int s = ws[k];
+            PushStream &P = d->push[(size_t)s];
+            // whether a collection of the reference's ran on THIS stream: its own count, never the launch's flag
+            const PushAfter a = push_after_launch(s, P, push_ctl(hc[(size_t)(s - R.s_lo)], ref), R.limit[k], target[k], false, false, verbose);
+            after.push_back(a);
+            P.T = a.T;
+            if (a.failed) { d->stream_dirty[(size_t)s] = 1; out[k] = 1; }   // (reported by jd_stream_finish)
+            else if (a.host_collects) gc_list.push_back(s);            // the rule fires behind the round's last frame
         }
         if (!gc_list.empty()) {
             rc = ensure_work_cap(d, (int)gc_list.size());
@@ -302,12 +300,9 @@ static int streams_push_rounds(jd_dec *d, const std::vector<int2> &work_all, con
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
         }
-        for (size_t a = 0; a < act.size(); ++a) {
-            if (!collected[a]) continue;
-            const int s = work_all[act[a]].x, at = d->stream_T[(size_t)s] - 1;
-            d->last_collect[(size_t)s] = at;                           // :746
-            d->n_collect_host[(size_t)s] += 1;
-            if (at - d->last_trace[(size_t)s] > d->partial_interval) tr_list.push_back(s);
+        for (size_t a = 0; a < R.act.size(); ++a) {
+            const int s = ws[R.act[a]];
+            if (after[a].collected && push_book(s, d->push[(size_t)s], after[a].at, d->partial_interval, verbose)) tr_list.push_back(s);
         }
         rc = trace_partial_many(d, tr_list, nullptr);
         if (rc) return rc;
@@ -317,99 +312,58 @@ static int streams_push_rounds(jd_dec *d, const std::vector<int2> &work_all, con
 
 extern "C" int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, const float *const *frames, const int32_t *n_frames)
 {
-    if (!d || n < 0 || (n > 0 && (!streams || !frames || !n_frames))) return jd_fail(JD_EINVAL, "jd_streams_push: bad argument");
+    if (push_check_call(d != nullptr, n, streams && frames && n_frames).verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_streams_push: bad argument");
     int rc = check_device(d->device);
     if (rc) return rc;
     const int D = d->am->D, G = d->am->n_gmm;
-    std::vector<char> seen((size_t)d->max_streams, 0);
     long long rows = 0;
-    for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= d->max_streams || n_frames[i] < 0 || (n_frames[i] > 0 && !frames[i]) || seen[(size_t)s])
-            return jd_fail(JD_EINVAL, "jd_streams_push: bad stream %d (each stream once)", s);
-        if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_streams_push before jd_stream_init (stream %d)", s);
-        seen[(size_t)s] = 1;
-        if (n_frames[i] > 0) d->stream_open[(size_t)s] = 1;
-        rows += n_frames[i];
-    }
+    const PushCheck chk = push_check_entries(d->push, n, streams, frames, n_frames, &rows);
+    if (chk.verdict == PUSH_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_push: bad stream %d (each stream once)", chk.stream);
+    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_push before jd_stream_init (stream %d)", chk.stream);
     if (rows == 0) return JD_OK;
-    if (rows > 0x7fffff00LL) return jd_fail(JD_EINVAL, "jd_streams_push: more than 2^31 frames in one call");
+    if (chk.verdict == PUSH_ARG_TOO_MANY_ROWS) return jd_fail(JD_EINVAL, "jd_streams_push: more than 2^31 frames in one call");
     hipStream_t st = d->s_search;
     pf_discard(d);                                                     // (the streaming path scores into table 0)
-    const size_t tile_rows = ((size_t)rows + GMM_ROWS2 - 1) / GMM_ROWS2 * GMM_ROWS2;
-    rc = ensure_table(d, 0, tile_rows * (size_t)G, tile_rows);
-    if (rc) return rc;
-    if ((size_t)rows * D > d->push_cap) {
-        if (d->d_push) (void)hipFree(d->d_push);
-        d->d_push = nullptr; d->push_cap = 0;
-        HIPCHK(hipMalloc(&d->d_push, tile_rows * D * sizeof(float)));
-        d->push_cap = tile_rows * D;
-    }
     // rows: stream after stream, packed; row_src is the identity (the frames are packed the same way).  Everything the
     // launch needs from the host - frames, row table, frames available per stream - goes through ONE pinned staging
     // buffer: a tick of the broker is sixteen callers' frames, and sixteen copies from pageable memory were a tenth of it.
-    const size_t need = (size_t)rows * D * sizeof(float) + tile_rows * sizeof(int) + (size_t)d->max_streams * sizeof(int);
-    if (need > d->stage_cap) {
-        if (d->h_stage) (void)hipHostFree(d->h_stage);
-        d->h_stage = nullptr; d->stage_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&d->h_stage, need + need / 2));
-        d->stage_cap = need + need / 2;
-    }
+    PushPack K;
+    push_pack(d->push, n, streams, n_frames, rows, D, GMM_ROWS2, &K);
+    rc = ensure_table(d, 0, K.tile_rows * (size_t)G, K.tile_rows);
+    if (rc) return rc;
+    if ((size_t)rows * D > d->push_cap) { rc = dregrow(&d->d_push, &d->push_cap, K.tile_rows * D, false); if (rc) return rc; }
+    if (K.need > d->stage_cap) { rc = dregrow(&d->h_stage, &d->stage_cap, push_grown(K.need), true); if (rc) return rc; }
     float *h_frames = (float *)d->h_stage;
-    int *h_src = (int *)(d->h_stage + (size_t)rows * D * sizeof(float));
-    int *h_T = h_src + tile_rows;
-    std::vector<int> Tnew((size_t)n);
+    int *h_src = (int *)(d->h_stage + K.src_at), *h_T = (int *)(d->h_stage + K.T_at);
     std::vector<int2> work;
-    std::vector<double> weight;
-    size_t r0 = 0;
-    int f_end = 0;
-    for (int s = 0; s < d->max_streams; ++s) h_T[s] = d->stream_T[(size_t)s];     // (the other streams keep theirs)
-    for (int i = 0; i < n; ++i) {
-        if (n_frames[i] == 0) continue;
-        const int s = streams[i];
-        memcpy(h_frames + r0 * D, frames[i], (size_t)n_frames[i] * D * sizeof(float));
-        Tnew[(size_t)i] = d->stream_T[(size_t)s] + n_frames[i];
-        h_T[s] = Tnew[(size_t)i];
-        // (k_search reads row  slot + (f - f0)  with f0 = 0: the slot is the stream's first row minus its first frame)
-        work.push_back(make_int2(s, (int)((long long)r0 - d->stream_T[(size_t)s])));
-        weight.push_back((double)n_frames[i]);
-        f_end = std::max(f_end, Tnew[(size_t)i]);
-        r0 += (size_t)n_frames[i];
+    for (size_t w = 0; w < K.work.size(); ++w) {
+        memcpy(h_frames + K.row0[w] * D, frames[K.entry[w]], (size_t)n_frames[K.entry[w]] * D * sizeof(float));
+        work.push_back(make_int2(K.work[w].stream, K.work[w].slot));
     }
-    for (size_t r = 0; r < tile_rows; ++r) h_src[r] = r < (size_t)rows ? (int)r : -1;
+    push_pack_fill(d->push, K, h_src, h_T);
     HIPCHK(hipMemcpyAsync(d->d_push, h_frames, (size_t)rows * D * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d->d_row_src[0], h_src, tile_rows * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_row_src[0], h_src, K.tile_rows * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d->d_T, h_T, (size_t)d->max_streams * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(jd_set_T_kernel, dim3((d->max_streams + 63) / 64), dim3(64), 0, st, d->d_ctl, 0, d->max_streams, d->d_T);
     HIPCHK(hipGetLastError());
     rc = launch_gmm(d->am, d->amb, d->d_push, d->d_row_src[0], (int)rows, d->d_ll[0], st);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }             // (the staging buffer is the next call's too)
-    if (d->partial_interval > 0) {
-        std::vector<int> target;
-        for (int i = 0; i < n; ++i) if (n_frames[i] > 0) target.push_back(Tnew[(size_t)i]);
-        return streams_push_rounds(d, work, target, st);
-    }
-    rc = launch_search(d, work, d->d_ll[0], (long long)G, 0, f_end, st, &weight);
+    if (d->partial_interval > 0) return streams_push_rounds(d, work, K.target, st);
+    rc = launch_search(d, work, d->d_ll[0], (long long)G, 0, K.f_end, st, &K.weight);
     if (rc) { (void)hipStreamSynchronize(st); for (const int2 &w : work) d->stream_dirty[(size_t)w.x] = 1; return rc; }
-    for (int i = 0; i < n; ++i) if (n_frames[i] > 0) d->stream_T[(size_t)streams[i]] = Tnew[(size_t)i];
+    for (size_t w = 0; w < K.work.size(); ++w) d->push[(size_t)K.work[w].stream].T = K.target[w];
     return JD_OK;
 }
 
 // tracePartialPath now on each of the listed streams (jd_stream_partial with trace_now, for a list): one launch, one fetch
 extern "C" int jd_streams_trace(jd_dec *d, int32_t n, const int32_t *streams, int32_t *found)
 {
-    if (!d || n < 0 || (n > 0 && !streams)) return jd_fail(JD_EINVAL, "jd_streams_trace: bad argument");
+    if (push_check_call(d != nullptr, n, streams != nullptr).verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_streams_trace: bad argument");
     if (d->models) return jd_fail(JD_ESTATE, "jd_streams_trace: word level only (model-level output: jd_stream_partial / jd_stream_partial_models)");
-    std::vector<char> seen((size_t)d->max_streams, 0);
     std::vector<int> ss, at;
-    for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= d->max_streams || seen[(size_t)s]) return jd_fail(JD_EINVAL, "jd_streams_trace: bad stream %d (each stream once)", s);
-        if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_streams_trace before jd_stream_init (stream %d)", s);
-        seen[(size_t)s] = 1;
-        if (found) found[i] = 0;
-        if (d->stream_T[(size_t)s] > 0) { ss.push_back(s); at.push_back(i); }   // (nothing to trace before the first frame, as jd_stream_partial)
-    }
+    const PushCheck chk = push_check_trace(d->push, n, streams, found, &ss, &at);
+    if (chk.verdict == PUSH_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_trace: bad stream %d (each stream once)", chk.stream);
+    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_trace before jd_stream_init (stream %d)", chk.stream);
     int rc = check_device(d->device);
     if (rc) return rc;
     std::vector<int32_t> fnd(ss.size(), 0);
@@ -433,8 +387,8 @@ extern "C" int jd_dec_get_partial_interval(const jd_dec *d, int32_t *interval)
 extern "C" int jd_stream_collect_info(jd_dec *d, int32_t s, int32_t *n_collections, int32_t *last_collect_frame)
 {
     if (!d || s < 0 || s >= d->max_streams) return jd_fail(JD_EINVAL, "jd_stream_collect_info: bad argument");
-    if (n_collections) *n_collections = d->n_collect_host[(size_t)s];
-    if (last_collect_frame) *last_collect_frame = d->last_collect[(size_t)s];
+    if (n_collections) *n_collections = d->push[(size_t)s].n_collect;
+    if (last_collect_frame) *last_collect_frame = d->push[(size_t)s].last_collect;
     return JD_OK;
 }
 
@@ -486,14 +440,15 @@ extern "C" int jd_dec_set_partial_interval(jd_dec *d, int32_t interval)
 extern "C" int jd_stream_path_counts(jd_dec *d, int32_t s, int32_t *n_path, int32_t *n_path_new, int32_t *exact)
 {
     if (!d || s < 0 || s >= d->max_streams) return jd_fail(JD_EINVAL, "jd_stream_path_counts: bad argument");
-    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_path_counts before jd_stream_init");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_path_counts before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
     StreamCtl hc;
     HIPCHK(hipMemcpy(&hc, d->d_ctl + s, sizeof hc, hipMemcpyDeviceToHost));
     const bool ref = d->C.pcount != nullptr;
-    if (n_path) *n_path = ref ? hc.n_paths_ref : hc.n_paths;
-    if (n_path_new) *n_path_new = ref ? hc.path_new_ref : hc.path_new;
+    const PushCtl c = push_ctl(hc, ref);
+    if (n_path) *n_path = c.n_path;
+    if (n_path_new) *n_path_new = c.n_path_new;
     if (exact) *exact = ref ? 1 : 0;
     return JD_OK;
 }
@@ -502,15 +457,16 @@ extern "C" int jd_stream_partial(jd_dec *d, int32_t s, int32_t trace_now, int32_
                                  int32_t *times, int32_t *found)
 {
     if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_partial: bad argument");
-    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_partial before jd_stream_init");
+    const PushStream &S = d->push[(size_t)s];
+    if (!S.started) return jd_fail(JD_ESTATE, "jd_stream_partial before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
     int fnd = 0;
-    if (trace_now && d->stream_T[(size_t)s] > 0) {
+    if (trace_now && S.T > 0) {
         rc = trace_partial(d, s, &fnd);
         if (rc) return rc;
     }
-    const std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
+    const std::vector<int32_t> &L = S.partial_label, &Tm = S.partial_time;
     *n = (int32_t)L.size();
     for (int k = 0; k < std::min<int>(cap, *n); ++k) {
         if (labels) labels[k] = L[(size_t)k];
@@ -525,15 +481,15 @@ extern "C" int jd_stream_partial_models(jd_dec *d, int32_t s, int32_t trace_now,
 {
     if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_partial_models: bad argument");
     if (!d->models) return jd_fail(JD_ESTATE, "jd_stream_partial_models: the decoder's output level is JD_OUTPUT_WORDS");
-    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_partial_models before jd_stream_init");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_partial_models before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
     int fnd = 0;
-    if (trace_now && d->stream_T[(size_t)s] > 0) {
+    if (trace_now && d->push[(size_t)s].T > 0) {
         rc = trace_partial(d, s, &fnd);
         if (rc) return rc;
     }
-    const jd_dec::PartialModels &P = d->partial_m[(size_t)s];
+    const PushModels &P = d->push[(size_t)s].partial_m;
     *n = (int32_t)P.model.size();
     const size_t k = (size_t)std::min<int>(cap, *n);
     if (k) {
@@ -551,10 +507,10 @@ extern "C" int jd_stream_partial_models(jd_dec *d, int32_t s, int32_t trace_now,
 extern "C" int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out)
 {
     if (!d || s < 0 || s >= d->max_streams || !out) return jd_fail(JD_EINVAL, "jd_stream_finish: bad argument");
-    if (!d->stream_started[(size_t)s]) return jd_fail(JD_ESTATE, "jd_stream_finish before jd_stream_init");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_finish before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
-    if (d->stream_T[(size_t)s] == 0) {                                 // init() directly followed by finish(): recognitionStart only
+    if (d->push[(size_t)s].T == 0) {                                   // init() directly followed by finish(): recognitionStart only
         rc = launch_search(d, std::vector<int2>(1, make_int2(s, 0)), d->d_ll[0], 0, 0, 0, d->s_search);
         if (rc) return rc;
     }
@@ -565,12 +521,7 @@ extern "C" int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out)
     std::vector<jd_hyp> tmp((size_t)d->max_streams);
     rc = fetch_results(d, s, 1, tmp.data(), s);
     *out = tmp[(size_t)s];
-    d->stream_open[(size_t)s] = 0;
     if (d->lazy_in[(size_t)s]) { d->lazy_in[(size_t)s] = 0; jd_lazy_leave(d->net, 1); }   // the utterance has left the network
-    if (d->partial_interval > 0 && out->n >= 0) {                      // :245-251 one more trace, from the best token
-        std::vector<int32_t> &L = d->partial_label[(size_t)s], &Tm = d->partial_time[(size_t)s];
-        L.resize((size_t)out->n); Tm.resize((size_t)out->n);
-        for (int k = 0; k < out->n; ++k) { L[(size_t)k] = out->label[out->n - 1 - k]; Tm[(size_t)k] = out->time[out->n - 1 - k]; }
-    }
+    d->push[(size_t)s].finish(d->partial_interval > 0, out->n, out->label, out->time);     // :245-251 one more trace, from the best token
     return rc;
 }

@@ -40,6 +40,18 @@ JD_HD constexpr int xcand(int i)
 {
     return i == 0 ? 0 : i == 1 ? 1 : i == 2 ? 2 : i == 3 ? 3 : i == 4 ? 4 : i == 5 ? 6 : i == 6 ? 8 : i == 7 ? 12 : i == 8 ? 16 : i == 9 ? 24 : i == 10 ? 32 : 64;
 }
+// collectPaths' count trigger (WFSTDecoderLite.cpp:360-362): nPath / nPathNew > 12 and nPath > 10000, with the IEEE float
+// division of the reference (nPathNew = 0 before the first collection: the ratio is +inf).  The counts are this
+// reference's where DecConst::pcount is there (n_paths_ref / path_new_ref: a Path per labelled propagateToken call, winner
+// or not, and what collectPaths keeps), else this build's own records - at most the reference's, which also creates
+// records for tokens that lose their state's recombination.  The kernels ask it before a frame, the host behind a stream's
+// last frame of a launch (jd_push.h).
+JD_HD bool path_rule_fires(int n_path, int n_path_new)
+{
+    return n_path > 10000 && (float)n_path / (float)n_path_new > 12.0f;
+}
+// k_partial_many's staging share: (label, frame) pairs per entry of a launch (jd_gc.h says why 32; the host's side: jd_push.h)
+#define PARTIAL_SHARE 32
 // Only rows the cut can apply to - up to 57 arcs, jd_slot.h: the flags of a longer row do not fit an item's loads - change their
 // order: the long rows of trigram-shaped graphs keep the file's, which the searches of such graphs are 2-3 % faster on (measured on
 // the north-star graph).

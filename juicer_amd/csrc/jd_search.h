@@ -558,15 +558,7 @@ __device__ __forceinline__ int grab_chunk(SearchShared &sh, int jw, int Cw)
     return jw + RFL(k) * Cw;
 }
 
-// collectPaths' count trigger (WFSTDecoderLite.cpp:360-362): nPath / nPathNew > 12 and nPath > 10000, with the IEEE float
-// division of the reference (nPathNew = 0 before the first collection: the ratio is +inf).  The counts are this
-// reference's where DecConst::pcount is there (n_paths_ref / path_new_ref: a Path per labelled propagateToken call, winner
-// or not, and what collectPaths keeps), else this build's own records - at most the reference's, which also creates
-// records for tokens that lose their state's recombination.
-__device__ __host__ __forceinline__ bool path_rule_fires(int n_path, int n_path_new)
-{
-    return n_path > 10000 && (float)n_path / (float)n_path_new > 12.0f;
-}
+// (collectPaths' count trigger, path_rule_fires: jd_prep.h - the host asks it too)
 
 // ---- cluster barrier: all Cw workgroups of one stream.  target = Cw * (number of this barrier).
 template <bool XL>
