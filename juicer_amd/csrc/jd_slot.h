@@ -182,6 +182,9 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
 #pragma unroll
         for (int j = 1; j <= NE; ++j) tk[j] = as_tok(ld16(V.rec, off + (unsigned)(HF + j - 1) * 1024u));
     };
+    // (the new list's base in scalar registers: as a vector pair it is spilled, and reloaded from scratch in front of every new-arc pass)
+    const unsigned long long newl_a = (unsigned long long)V.newl;
+    const GAS unsigned long long *const newl = (const GAS unsigned long long *)(((unsigned long long)(unsigned)RFL((int)(unsigned)(newl_a >> 32)) << 32) | (unsigned)RFL((int)(unsigned)newl_a));
     int u = slot_grab(&sh.nextA);
     // (80-byte records only: the nine fields of the 144-byte layout ahead cost 36 registers and 300 spilled ones)
     constexpr bool AHEAD = SLOT_REC_AHEAD != 0 && NE == 3;
@@ -197,6 +200,25 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
         int w, idx;
         v4i h0, h1, h2 = {0, 0, 0, 0};
         Tok tk[NE + 1];
+        // The best arrival at the source state (StateRec::e[p ^ 1]: the key kv) and, behind it, the entry token's item.  EARLY (80-byte
+        // records): each branch issues its own - a record pass knows the source state with its header, a new-arc pass with its list
+        // entry, two loads earlier.  (144-byte records keep one copy behind the branches: with two, k_slot_batch<6, false> spills 30
+        // registers for 27.)
+        constexpr bool EARLY = NE == 3;
+        unsigned long long kv;
+        v4i itv;
+        auto load_key = [&](int st) __attribute__((always_inline)) { return ld8(V.srec_r, valid ? SREC_E_OFF(C, st, p ^ 1) : OOB_OFF); };
+        // entry token = the best token that arrived at the arc's source state in the previous frame, over the arc (:560-582)
+        // The item is a THIRD round trip behind the record and the key, and all that it brings is the entry token's history (ac, lm,
+        // path): its score is in the key.  Everything that decides - maxima, thresholds, the histogram - runs on scores; with plain
+        // left-to-right models only state 1 can take the entry token, so the SOURCE takes the item up behind the arithmetic
+        // (JD_A_HMM_UPDATE).  The code object does not: the item's score word is read by nobody, the compiler reuses that register
+        // at once and waits for the load in front of the reuse, some twenty instructions behind the request (tools/waitchain.py).
+        // Asking for the three history words alone moves the wait behind the state loop - and measured nothing.
+        // (General topologies: any state may take the item - they wait for it in JD_A_ENTRY_TOKEN.)
+        auto load_item = [&](unsigned long long k) __attribute__((always_inline)) {
+            return ld16(V.items, k != 0ULL ? iprev + (unsigned)(k & 0xffffffffULL) * 32u : OOB_OFF);
+        };
         if (!is_new) {
             if constexpr (AHEAD) {
                 valid = pvalid; h0 = ph0; h1 = ph1; h2 = ph2;
@@ -204,40 +226,43 @@ __device__ __forceinline__ void slot_phase_a(const DecConst &C, SlotShared &sh, 
                 for (int j = 1; j <= NE; ++j) tk[j] = ptk[j];
                 if (un < Q0) load_rec(un, pvalid, ph0, ph1, ph2, ptk);
             } else load_rec(u, valid, h0, h1, h2, tk);
+            if constexpr (EARLY) { kv = load_key(h0.z); itv = load_item(kv); }
         } else {                                                       // attachNetInst :751-774, from the arc's template (the twin of jd_search.h: stage_k - see there)
             locate(1, u - Q0, n1, valid, w, idx);
-            const unsigned long long e = CL(V.newl + (valid ? (size_t)w * g.seg_new + (unsigned)idx : (size_t)0));
+            const unsigned long long e = CL((EARLY ? newl : (const GAS unsigned long long *)V.newl) + (valid ? (size_t)w * g.seg_new + (unsigned)idx : (size_t)0));
             const int2 nb = valid ? make_int2((int)(unsigned)e, (int)(unsigned)(e >> 32)) : make_int2(0, 0);   // {arc, source state}
-            const JdArc Bk = C.arcs[nb.x];
-            const int hm = max((Bk.in & ~ARC_FLAGS) - 1, 0);            // (arcs on the new list carry a model; idle lanes read arc 0)
-            const int4 a0 = ((const int4 *)C.aux_h)[(NE == 3) ? hm : 2 * hm];
-            h0 = (v4i){nb.x, valid ? (a0.x | (Bk.out != 0 ? REC_LABELLED : 0) | ((Bk.in & SOLE_FLAG) ? REC_SOLE : 0)) : 0, nb.y, Bk.to};
-            h1 = (v4i){a0.y, a0.z, a0.w, __float_as_int(Bk.w)};
-            if (NE == 6) { const int4 a1 = ((const int4 *)C.aux_h)[2 * hm + 1]; h2 = (v4i){a1.x, a1.y, a1.z, 0}; }
+            if constexpr (EARLY) {
+                // three round trips: the list entry -> {the arc, the key} -> {the template, the item}.  The key needs the source state
+                // alone, which is in the list entry; the arc and its template are 16-byte records and come as one load each.
+                const v4i Bk = ((const v4i *)C.arcs)[nb.x];             // JdArc {to, w, in, out}
+                kv = load_key(nb.y);
+                const int hm = max((Bk.z & ~ARC_FLAGS) - 1, 0);         // (arcs on the new list carry a model; idle lanes read arc 0)
+                const v4i a0 = ((const v4i *)C.aux_h)[hm];
+                itv = load_item(kv);
+                h0 = (v4i){nb.x, valid ? (a0.x | (Bk.w != 0 ? REC_LABELLED : 0) | ((Bk.z & SOLE_FLAG) ? REC_SOLE : 0)) : 0, nb.y, Bk.x};
+                h1 = (v4i){a0.y, a0.z, a0.w, Bk.y};
+            } else {
+                const JdArc Bk = C.arcs[nb.x];
+                const int hm = max((Bk.in & ~ARC_FLAGS) - 1, 0);
+                const int4 a0 = ((const int4 *)C.aux_h)[2 * hm];
+                h0 = (v4i){nb.x, valid ? (a0.x | (Bk.out != 0 ? REC_LABELLED : 0) | ((Bk.in & SOLE_FLAG) ? REC_SOLE : 0)) : 0, nb.y, Bk.to};
+                h1 = (v4i){a0.y, a0.z, a0.w, __float_as_int(Bk.w)};
+                const int4 a1 = ((const int4 *)C.aux_h)[2 * hm + 1]; h2 = (v4i){a1.x, a1.y, a1.z, 0};
+            }
 #pragma unroll
             for (int j = 1; j <= NE; ++j) tk[j] = null_tok();
         }
         const int arc = h0.x;
         const int n = h0.y & 0xff;                                     // 0 for lanes without an instance
         const int tm = (h0.y >> 8) & 0x1fffff;
-        // the best arrival at the source state (StateRec::e[p ^ 1]) and the likelihoods: in flight together
-        unsigned long long kv;
-        float outp[NE];
-        {
-            const unsigned long long ev = ld8(V.srec_r, valid ? SREC_E_OFF(C, h0.z, p ^ 1) : OOB_OFF);
+        if constexpr (!EARLY) kv = load_key(h0.z);                     // (the key and the likelihoods: in flight together)
+        float outp[NE];                                                // the likelihoods of the instance's states
 #pragma unroll
-            for (int j = 0; j < NE; ++j) {
-                const int gj = (j == 0) ? h1.x : (j == 1) ? h1.y : (j == 2) ? h1.z : (j == 3) ? h2.x : (j == 4) ? h2.y : h2.z;
-                outp[j] = LLL ? sh.ll[(j + 1 < n - 1) ? gj : 0] : llrow[(j + 1 < n - 1) ? gj : 0];   // :411
-            }
-            kv = ev;
+        for (int j = 0; j < NE; ++j) {
+            const int gj = (j == 0) ? h1.x : (j == 1) ? h1.y : (j == 2) ? h1.z : (j == 3) ? h2.x : (j == 4) ? h2.y : h2.z;
+            outp[j] = LLL ? sh.ll[(j + 1 < n - 1) ? gj : 0] : llrow[(j + 1 < n - 1) ? gj : 0];   // :411
         }
-        // entry token = the best token that arrived at the arc's source state in the previous frame, over the arc (:560-582)
-        const v4i itv = ld16(V.items, kv != 0ULL ? iprev + (unsigned)(kv & 0xffffffffULL) * 32u : OOB_OFF);
-        // The item is a THIRD round trip behind the record and the key, and all that it brings is the entry token's history (ac, lm,
-        // path): its score is in the key.  Everything that decides - maxima, thresholds, the histogram - runs on scores; with plain
-        // left-to-right models only state 1 can take the entry token, so the item is taken up BEHIND the arithmetic (below), its
-        // round trip running beside it.  (General topologies: any state may take it - they wait for it here.)
+        if constexpr (!EARLY) itv = load_item(kv);
         JD_A_ENTRY_TOKEN
         Tok nw[NE + 1];
         int live_mask = 0;
