@@ -154,6 +154,15 @@ int jd_net_push_labels(jd_net **out, const jd_net *cl, int64_t *n_moved);
 int jd_debug_cl_label_sets(const jd_net *cl, int64_t *row_ptr, int32_t *labels, int64_t cap, int64_t *n_total, uint8_t *mayfin);
 
 /*
+ * Diagnostics / tests (host code, no device): the look-ahead INTERVALS the composition uses without JD_LOOKAHEAD_SETS,
+ * for every state of a C.L transducer - lo[n_states], hi[n_states]: the smallest and largest output label of the first
+ * label-carrying arcs reachable from c through label-less arcs, in the caller's numbering (lo = 2^31 - 1, hi = 0: none;
+ * lo = 1, hi = 2^31 - 1: "every label", c lies on a cycle of label-less arcs or reaches one) - and mayfin[n_states] as
+ * above.
+ */
+int jd_debug_cl_lookahead(const jd_net *cl, int32_t *lo, int32_t *hi, uint8_t *mayfin);
+
+/*
  * Dynamic composition proper (WFSTOnTheFlyDecoder: C.L o G expanded where the search goes, never as a
  * whole): the network this returns holds only its start state; decoders created on it expand a composed
  * state - same expansion step as jd_net_compose, one state at a time - when a token first enters an arc

@@ -121,7 +121,7 @@ EXPORTS = [
     "jd_multi_create", "jd_multi_create_lazy", "jd_multi_decode_batch", "jd_multi_destroy",
     "jd_dec_set_partial_interval", "jd_stream_partial", "jd_stream_collect_info", "jd_stream_path_counts", "jd_dec_quiesce", "jd_debug_closure_path_counts", "jd_dec_set_max_alloc_models", "jd_net_compose", "jd_am_create_hybrid", "jd_net_create_lazy", "jd_net_lazy_size", "jd_net_lazy_reset",
     "jd_net_lazy_set_high_water", "jd_net_lazy_generation", "jd_release_cached_memory", "jd_net_push_labels", "jd_debug_cl_label_sets",
-    "jd_dec_prefetch_scores", "jd_streams_push", "jd_dec_info",
+    "jd_debug_cl_lookahead", "jd_dec_prefetch_scores", "jd_streams_push", "jd_dec_info",
     "jd_broker_create", "jd_broker_destroy", "jd_broker_open", "jd_broker_close", "jd_broker_init", "jd_broker_push",
     "jd_broker_finish", "jd_broker_get_stats", "jd_dec_debug_cells", "jd_dec_set_pipeline", "jd_dec_pipeline_stats",
     "jd_dec_set_scoring", "jd_am_score_frames_mode", "jd_debug_log1pe", "jd_debug_log_add",
@@ -283,6 +283,14 @@ class Network:
         labels = np.zeros(max(cap, 1), np.int32)
         _check(L.jd_debug_cl_label_sets(self.h, _p(rp, C.c_int64), _p(labels, C.c_int32), C.c_int64(cap), C.byref(n), _p(mf, C.c_uint8)))
         return rp, labels[:n.value], mf.astype(bool)
+
+    def lookahead(self):
+        """The look-ahead intervals of every state of this C.L transducer (jd_debug_cl_lookahead, host only):
+        (lo int32 [n_states], hi int32 [n_states], mayfin bool [n_states]); lo > hi: no label is reachable."""
+        ns = self.n_states
+        lo, hi, mf = np.zeros(ns, np.int32), np.zeros(ns, np.int32), np.zeros(ns, np.uint8)
+        _check(lib().jd_debug_cl_lookahead(self.h, _p(lo, C.c_int32), _p(hi, C.c_int32), _p(mf, C.c_uint8)))
+        return lo, hi, mf.astype(bool)
 
     def push_labels(self):
         """C.L with its output labels pushed towards the initial state (jd_net_push_labels): (network, labels moved)."""

@@ -397,6 +397,17 @@ extern "C" int jd_debug_cl_label_sets(const jd_net *cl, int64_t *row_ptr, int32_
     return jd_label_sets_csr(cl, row_ptr, labels, cap, n_total, mayfin);
 }
 
+// Diagnostics / tests (host only, no device): the look-ahead entries of the interval look-ahead (cl_lookahead), taken apart
+extern "C" int jd_debug_cl_lookahead(const jd_net *cl, int32_t *lo, int32_t *hi, uint8_t *mayfin)
+{
+    if (!cl || !lo || !hi || !mayfin) return jd_fail(JD_EINVAL, "jd_debug_cl_lookahead: null argument");
+    if (cl->lazy_dev) return jd_fail(JD_EINVAL, "jd_debug_cl_lookahead: not for a lazily composed network");
+    std::vector<int2> la;
+    cl_lookahead(cl, la);
+    for (size_t c = 0; c < la.size(); ++c) { lo[c] = la[c].x; hi[c] = la_hi(la[c]); mayfin[c] = la_mayfin(la[c]) ? 1 : 0; }
+    return JD_OK;
+}
+
 // Label pushing, the other half of the reference's -pushing (doLabelAndWeightPushing, juicer.cpp:240, 931-935).  The
 // reference gives every C.L transition the SET of output labels that can follow it (WFSTLabelPushingNetwork::
 // assignOutlabsToTrans, WFSTNetwork.cpp:1643-1764, loops included) and its on-the-fly decoder takes the G transition

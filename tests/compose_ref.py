@@ -83,7 +83,8 @@ def _finish(states, arcs_of, fin_of, init_key, order_key):
         row_ptr.append(len(to))
     fin = np.asarray([fin_of[k] for k in keys], np.float32)
     return dict(n_states=len(keys), init=idx[init_key], row_ptr=np.asarray(row_ptr, np.int32), to=np.asarray(to, np.int32),
-                w=np.asarray(w, np.float32), ilab=np.asarray(il, np.int32), olab=np.asarray(ol, np.int32), fin_w=fin)
+                w=np.asarray(w, np.float32), ilab=np.asarray(il, np.int32), olab=np.asarray(ol, np.int32), fin_w=fin,
+                keys=keys)                                               # (what each state is: (c, g, f), naive: (c, g))
 
 
 def compose_filtered(cl, cl_init, g, g_init, pushing=False):
@@ -165,6 +166,39 @@ def compose_naive(cl, cl_init, g, g_init):
                 states.add(dk)
                 queue.append(dk)
     return _finish(states, arcs_of, fin_of, start, lambda k: k)
+
+
+def _best(graph, words):
+    """best total weight (scores: higher is better) of a path from the initial state to a final state whose
+    output labels spell `words`; -inf if there is none.  Label-synchronous DP with epsilon-output relaxation
+    (all arcs of a kind at once: a composed graph of arbitrary shape has thousands)."""
+    S = graph["n_states"]
+    NEG = -np.inf
+    rp, to, w, ol = graph["row_ptr"], np.asarray(graph["to"], np.int64), graph["w"].astype(np.float64), graph["olab"]
+    src = np.repeat(np.arange(S, dtype=np.int64), np.diff(np.asarray(rp, np.int64)))
+    less = ol == 0
+
+    def relax(v):
+        while True:                                     # epsilon-output arcs (acyclic in weight terms: they only add)
+            new = v.copy()
+            with np.errstate(invalid="ignore"):
+                np.maximum.at(new, to[less], v[src[less]] + w[less])
+            better = new > v + 1e-12
+            if not better.any():
+                return v
+            v = np.where(better, new, v)
+
+    cur = np.full(S, NEG)
+    cur[graph["init"]] = 0.0
+    cur = relax(cur)
+    for x in words:
+        m = ol == x
+        nxt = np.full(S, NEG)
+        np.maximum.at(nxt, to[m], cur[src[m]] + w[m])
+        cur = relax(nxt)
+    fin = graph["fin_w"].astype(np.float64)
+    ok = np.isfinite(fin) & (cur > NEG)
+    return float(np.max(cur[ok] + fin[ok])) if ok.any() else NEG
 
 
 def push_labels(cl, cl_init):

@@ -120,7 +120,7 @@ def compose_sets(cl, cl_init, g, g_init, pushing=False):
         row_ptr.append(len(to))
     return dict(n_states=len(keys), init=idx[start], row_ptr=np.asarray(row_ptr, np.int32), to=np.asarray(to, np.int32),
                 w=np.asarray(w, np.float32), ilab=np.asarray(il, np.int32), olab=np.asarray(ol, np.int32),
-                fin_w=np.asarray([fin_of[k] for k in keys], np.float32))
+                fin_w=np.asarray([fin_of[k] for k in keys], np.float32), keys=keys)   # (keys: what each state is, (c, f, g))
 
 
 def random_perm(cl, g, seed):

@@ -5,7 +5,7 @@ weights - they are two graphs with the same weighted paths."""
 import numpy as np
 import pytest
 
-from compose_ref import compose_filtered, compose_naive
+from compose_ref import _best, compose_filtered, compose_naive
 
 
 def _csr_of(net, scale):
@@ -19,39 +19,6 @@ def _csr_of(net, scale):
     fin[net.fstate] = (-(net.fweight_file.astype(np.float64) * scale)).astype(np.float32)
     return dict(row_ptr=rp, to=net.dst[order], w=(-(net.w_file[order].astype(np.float64) * scale)).astype(np.float32),
                 ilab=net.ilab[order], olab=net.olab[order], fin_w=fin), int(net.src[0])
-
-
-def _best(graph, words):
-    """best total weight (scores: higher is better) of a path from the initial state to a final state whose
-    output labels spell `words`; -inf if there is none.  Label-synchronous DP with epsilon-output relaxation."""
-    S = graph["n_states"]
-    NEG = -np.inf
-    cur = np.full(S, NEG)
-    cur[graph["init"]] = 0.0
-    rp, to, w, ol = graph["row_ptr"], graph["to"], graph["w"].astype(np.float64), graph["olab"]
-
-    def relax(v):
-        changed = True
-        while changed:                                  # epsilon-output arcs (acyclic in weight terms: they only add)
-            changed = False
-            for s in np.nonzero(v > NEG)[0]:
-                for e in range(rp[s], rp[s + 1]):
-                    if ol[e] == 0 and v[s] + w[e] > v[to[e]] + 1e-12:
-                        v[to[e]] = v[s] + w[e]
-                        changed = True
-        return v
-
-    cur = relax(cur)
-    for x in words:
-        nxt = np.full(S, NEG)
-        for s in np.nonzero(cur > NEG)[0]:
-            for e in range(rp[s], rp[s + 1]):
-                if ol[e] == x and cur[s] + w[e] > nxt[to[e]]:
-                    nxt[to[e]] = cur[s] + w[e]
-        cur = relax(nxt)
-    fin = graph["fin_w"].astype(np.float64)
-    ok = np.isfinite(fin) & (cur > NEG)
-    return float(np.max(cur[ok] + fin[ok])) if ok.any() else NEG
 
 
 @pytest.mark.parametrize("seed,n_tri,with_sp", [(5, 30, True), (6, 0, False), (8, 40, True)])
