@@ -750,6 +750,22 @@ int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const floa
 int jd_debug_hist_bin(int32_t device, const float *s, int64_t n, int32_t hist_min, int32_t hist_max, int32_t *out);
 int jd_debug_hist_threshold(int32_t device, const int32_t *bins, int64_t n_cases, int32_t nb, const int32_t *max_hyps,
                             int32_t hist_min, float *out);
+/* ... and of the Path collection and the PARTIAL_DECODING trace (csrc/jd_gc.h) on a state the CALLER describes instead of
+ * one a search left behind: one to four streams - Path arenas, flags and counters, instance records by writer wave, the
+ * last frame's frontier items and dirty lists, arrival keys, bestFinalToken's Path - over a tiny CSR graph, and up to eight
+ * operations: a collection (launch_gc itself, on a work list or on one stream, with G workgroups per stream, gc_threshold and
+ * path_rule as given), a trace of one stream (k_partial, word or model level) and a trace of several (k_partial_many).
+ * desc is a list of n_desc int32 words whose grammar stands at the top of csrc/jd_paths.h; it is validated BEFORE any device
+ * call, and what could lead a kernel out of an arena is JD_EINVAL: a prev[q] outside [-1, q), a token's, an item's or
+ * bestFinalToken's path outside [-1, n_paths), an arrival key that names an item not written, a dirty or source state outside
+ * the graph, per-wave counts beyond make_geo's segments, n_paths above the arena's capacity, an arena above 2^18 records, G
+ * outside 1 .. 32, NE other than 3 or 6, res_cap < 1, more than four streams.  What comes back in out (same header: per stream
+ * its counters, GcState words, the Path arena now current, the path of every token slot and of every item; per trace its
+ * out words, result arrays and model row, prefilled with the description's sentinel): *n_out words, at most out_cap - too
+ * small an out_cap is JD_ENOMEM with *n_out set to what is needed, before any device call as well.  Device only; needs no
+ * jd_dec, network or model, and allocates and frees what it uses.  tests/test_gpu_paths.py compares every word that comes back
+ * with tests/paths_ref.py. */
+int jd_debug_paths(int32_t device, const int32_t *desc, int64_t n_desc, int32_t *out, int64_t out_cap, int64_t *n_out);
 
 const char *jd_last_error(void);
 const char *jd_version(void);

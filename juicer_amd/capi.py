@@ -129,6 +129,7 @@ EXPORTS = [
     "jd_dec_set_output_level", "jd_dec_get_output_level", "jd_dec_model_result",
     "jd_am_hmm_name", "jd_stream_partial_models",
     "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial", "jd_debug_score_rows",
+    "jd_debug_paths",
 ]
 
 _lib = None
@@ -567,6 +568,22 @@ def debug_hist_threshold(bins, max_hyps, hist_min: int, device: int = 0):
                                          C.c_int32(bins.shape[1]), _p(max_hyps, C.c_int32), C.c_int32(hist_min),
                                          _p(out, C.c_float)))
     return out
+
+
+def debug_paths(desc, device: int = 0):
+    """The Path collection and the partial trace (csrc/jd_gc.h) on a described state: desc is the int32 word list of
+    csrc/jd_paths.h, and the words that come back are those it lists (device only; a description that fails the validation
+    raises JD_EINVAL before any device call)."""
+    desc = _i32(desc)
+    assert desc.ndim == 1
+    n = C.c_int64(0)
+    rc = lib().jd_debug_paths(C.c_int32(device), _p(desc, C.c_int32), C.c_int64(desc.shape[0]), None, C.c_int64(0), C.byref(n))
+    if rc != JD_ENOMEM:
+        _check(rc if rc != 0 else JD_ESTATE)
+    out = np.empty(max(n.value, 1), np.int32)
+    _check(lib().jd_debug_paths(C.c_int32(device), _p(desc, C.c_int32), C.c_int64(desc.shape[0]), _p(out, C.c_int32),
+                                C.c_int64(n.value), C.byref(n)))
+    return out[:n.value]
 
 
 class Decoder:

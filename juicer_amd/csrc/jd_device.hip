@@ -1516,6 +1516,7 @@ extern "C" int jd_decode_batch(jd_dec *d, int32_t n_utts, const float *const *fe
 // ---- streaming API: IDecoder::init / processFrame / finish for one stream
 
 #include "jd_host_stream.h"
+#include "jd_host_paths.h"         // jd_debug_paths: the collection and the partial trace on a described state
 
 // Diagnostics: per-workgroup cycle accounting of k_search (100 MHz wall clock): for every
 // workgroup of the grid {work lists A, phase A, workgroup wait, cluster barrier, work lists X, phase X,
