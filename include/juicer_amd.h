@@ -656,6 +656,46 @@ int jd_stream_partial_models(jd_dec *d, int32_t s, int32_t trace_now, int32_t ca
                              int32_t *model, int32_t *label, int32_t *time, float *score, float *ac, float *lm,
                              int32_t *found);
 
+/* The CURRENT BEST hypothesis of live streams: what the decoder believes right now, beside the converged prefix the partial
+ * traces give (jd_stream_partial).  After the last frame pushed to a stream, the best token is the emitting-state token with
+ * the highest score among the active arc instances (HMM states 1 .. nStates - 2 with a score above LOG_ZERO; entry tokens
+ * pending at states have not been scored on a frame and do not count).  Equal scores: the lowest arc in the decoder's own arc
+ * order, then the lowest HMM state - a rule that does not depend on the run.  The hypothesis is the token's Path chain, OLDEST
+ * first: on a word-level decoder every record carries a word label; at model level (JD_OUTPUT_MODELS) it is every record of
+ * the chain with the fields of jd_model_hyp, and the word list is its entries with a label.  Nothing carries a final-state
+ * weight: the utterance has not ended.  Unstable by nature - every call may revise the whole list.
+ * jd_streams_best runs the search for the n listed streams, each at the frame it has reached, with ONE kernel launch (a
+ * workgroup per stream) and ONE device-to-host copy that brings the heads and every chain of up to 64 records; a longer chain
+ * is read from the stream's result arrays afterwards.  out[i] is stream i's head; the lists stay with the decoder and are read
+ * with jd_stream_best_words / jd_stream_best_models, which only read that host copy, with jd_stream_partial's conventions (*n
+ * the full length, at most cap entries written, any output pointer may be NULL; empty from jd_stream_init on and after a call
+ * that found nothing).  jd_stream_best_models: JD_ESTATE on a word-level decoder; jd_stream_best_words works at both levels.
+ * Anywhere between a stream's jd_stream_init and its jd_stream_finish, mixed freely with jd_stream_push, jd_streams_push,
+ * jd_stream_partial* and jd_streams_trace, under a trace interval and on a lazily composed network; it only reads the
+ * stream's state and never changes what those calls or jd_stream_finish return.
+ * JD_EINVAL: a null handle or list, n < 0, a stream outside the decoder's range or listed twice.  JD_ESTATE: a listed stream
+ * before its jd_stream_init; a decoder whose resident kernel a broker drives.  JD_ENOMEM: a chain longer than the result
+ * capacity - that stream's entry says found = 0 and its list is empty, the other entries are delivered, and the first such
+ * error is returned.
+ * jd_dec_best_stats: the kernel launches and device-to-host copies these calls have made (cumulative).
+ * Out of scope: the broker (jd_broker_* offers the converged prefix only), the batch calls, jd_multi_* and the resident
+ * kernels. */
+typedef struct jd_best {
+    int32_t found;        /* 0: the stream has no live emitting token (no frame yet, a failed stream, everything pruned) */
+    int32_t frame;        /* the frame the stream has reached (frames pushed)                                           */
+    int32_t n_words;      /* records with a word label on the chain                                                     */
+    int32_t n_records;    /* all records on the chain (= n_words on a word-level decoder)                               */
+    int32_t model;        /* in-label of the arc the token is inside (HMM index + 1)                                    */
+    int32_t state;        /* its HMM state, 1 .. nStates - 2                                                            */
+    float score, ac, lm;  /* the token's                                                                                */
+} jd_best;
+int jd_streams_best(jd_dec *d, int32_t n, const int32_t *streams, jd_best *out);
+int jd_stream_best_words(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *label, int32_t *time,
+                         float *score, float *ac, float *lm);
+int jd_stream_best_models(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *model, int32_t *label,
+                          int32_t *time, float *score, float *ac, float *lm);
+int jd_dec_best_stats(const jd_dec *d, int64_t *launches, int64_t *copies);
+
 /* What JD_FLOW_RESIDENT has done so far (cumulative over the decoder's life; a bench reads it on either side of its
  * timed region: frames_searched is what the slots really advanced in between, whatever was announced or handed back). */
 typedef struct jd_pipe_stats {

@@ -311,8 +311,39 @@ public:
         if (n > 0) check(jd_stream_partial(dec_, 0, 0, n, &n, &labels[0], &frames[0], &f2));
         return found != 0;
     }
+    // The current best hypothesis (jd_streams_best): the word chain of the best emitting-state token after the frames given so
+    // far (buffered frames are flushed first), as (output label, frame) pairs, oldest first - what partialPaths has converged on
+    // is its prefix; the rest may change with every frame.  false: no live token (no frame yet), the lists are empty.
+    bool bestPath(std::vector<int> &labels, std::vector<int> &frames)
+    {
+        const bool found = bestNow();
+        int n = 0;
+        check(jd_stream_best_words(dec_, 0, 0, &n, 0, 0, 0, 0, 0));
+        labels.assign((size_t)n, 0); frames.assign((size_t)n, 0);
+        if (n > 0) check(jd_stream_best_words(dec_, 0, n, &n, &labels[0], &frames[0], 0, 0, 0));
+        return found;
+    }
+    // ... at model level (modelLevelOutput): every record of the chain - models[k] the in-label of the model left at frames[k]
+    // (0: a word label on an epsilon-input arc), labels[k] the word label of the same arc or 0
+    bool bestPath(std::vector<int> &models, std::vector<int> &labels, std::vector<int> &frames)
+    {
+        const bool found = bestNow();
+        int n = 0;
+        check(jd_stream_best_models(dec_, 0, 0, &n, 0, 0, 0, 0, 0, 0));
+        models.assign((size_t)n, 0); labels.assign((size_t)n, 0); frames.assign((size_t)n, 0);
+        if (n > 0) check(jd_stream_best_models(dec_, 0, n, &n, &models[0], &labels[0], &frames[0], 0, 0, 0));
+        return found;
+    }
 
 private:
+    bool bestNow()
+    {
+        flush();
+        const int32_t s = 0;
+        jd_best b;
+        check(jd_streams_best(dec_, 1, &s, &b));
+        return b.found != 0;
+    }
 #ifdef JUICER_AMD_HAVE_LABHIST
     // the jd_model_hyp of the same decode (newest first) as one DecHypHist chain: an entry with a model gives a DHHTYPE
     // record, one with a word label a LABDHHTYPE record, one with both the two, the DHHTYPE one newer (addLabelHist, then

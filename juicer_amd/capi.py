@@ -68,6 +68,13 @@ class CModelHyp(C.Structure):
                 ("tot_score", C.c_float), ("tot_ac", C.c_float), ("tot_lm", C.c_float)]
 
 
+class CBest(C.Structure):
+    """jd_best: the head of a stream's current best hypothesis (jd_streams_best)."""
+    _fields_ = [("found", C.c_int32), ("frame", C.c_int32), ("n_words", C.c_int32), ("n_records", C.c_int32),
+                ("model", C.c_int32), ("state", C.c_int32),
+                ("score", C.c_float), ("ac", C.c_float), ("lm", C.c_float)]
+
+
 class PipeStats(C.Structure):
     _fields_ = [("mode", C.c_int32), ("depth", C.c_int32), ("slots", C.c_int32), ("resident", C.c_int32),
                 ("batches_announced", C.c_int32), ("pad0", C.c_int32),
@@ -130,6 +137,7 @@ EXPORTS = [
     "jd_am_hmm_name", "jd_stream_partial_models",
     "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial", "jd_debug_score_rows",
     "jd_debug_paths",
+    "jd_streams_best", "jd_stream_best_words", "jd_stream_best_models", "jd_dec_best_stats",
 ]
 
 _lib = None
@@ -734,6 +742,62 @@ class Decoder:
         k = n.value
         return was_found, ModelHyp(n=k, model=mod[:k].copy(), label=lab[:k].copy(), time=tim[:k].copy(), score=sc[:k].copy(),
                                    ac=ac[:k].copy(), lm=lm[:k].copy(), tot_score=0.0, tot_ac=0.0, tot_lm=0.0)
+
+    # -- the current best hypothesis of live streams (jd_streams_best)
+    def streams_best(self, streams):
+        """The best emitting-state token of each listed stream (each once) at the frame it has reached: one launch and one fetch
+        for all of them (jd_streams_best).  Returns a dict per stream with jd_best's fields; the lists are read with
+        stream_best_words(s) / stream_best_models(s).  A stream whose chain exceeds the result capacity raises (JD_ENOMEM) after
+        the others were served: the error carries what was delivered as .entries."""
+        ss = _i32(list(streams))
+        n = int(ss.shape[0])
+        out = (CBest * max(1, n))()
+        rc = lib().jd_streams_best(self.h, C.c_int32(n), _p(ss, C.c_int32), out)
+        entries = [{f: getattr(out[i], f) for f, _ in CBest._fields_} for i in range(n)]
+        if rc != 0:
+            err = JuicerAmdError(rc, lib().jd_last_error().decode())
+            err.entries = entries if rc == JD_ENOMEM else None
+            raise err
+        return entries
+
+    def stream_best_words(self, s: int = 0):
+        """The word list of stream s's best hypothesis as of the last streams_best, oldest first: (label, time, score, ac, lm)
+        arrays (jd_stream_best_words; at model level the labelled entries of stream_best_models)."""
+        n = C.c_int32(0)
+        cap = 256
+        while True:
+            lab, tim = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+            sc, ac, lm = (np.zeros(cap, np.float32) for _ in range(3))
+            _check(lib().jd_stream_best_words(self.h, C.c_int32(s), C.c_int32(cap), C.byref(n), _p(lab, C.c_int32), _p(tim, C.c_int32),
+                                              _p(sc, C.c_float), _p(ac, C.c_float), _p(lm, C.c_float)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        k = n.value
+        return lab[:k].copy(), tim[:k].copy(), sc[:k].copy(), ac[:k].copy(), lm[:k].copy()
+
+    def stream_best_models(self, s: int = 0) -> "ModelHyp":
+        """Every record of the chain of stream s's best hypothesis as of the last streams_best, OLDEST first, as a ModelHyp
+        (jd_stream_best_models, JD_OUTPUT_MODELS only); tot_* are 0."""
+        n = C.c_int32(0)
+        cap = 256
+        while True:
+            mod, lab, tim = (np.zeros(cap, np.int32) for _ in range(3))
+            sc, ac, lm = (np.zeros(cap, np.float32) for _ in range(3))
+            _check(lib().jd_stream_best_models(self.h, C.c_int32(s), C.c_int32(cap), C.byref(n), _p(mod, C.c_int32), _p(lab, C.c_int32),
+                                               _p(tim, C.c_int32), _p(sc, C.c_float), _p(ac, C.c_float), _p(lm, C.c_float)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        k = n.value
+        return ModelHyp(n=k, model=mod[:k].copy(), label=lab[:k].copy(), time=tim[:k].copy(), score=sc[:k].copy(),
+                        ac=ac[:k].copy(), lm=lm[:k].copy(), tot_score=0.0, tot_ac=0.0, tot_lm=0.0)
+
+    def best_stats(self):
+        """(kernel launches, device-to-host copies) the streams_best calls of this decoder have made (jd_dec_best_stats)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _check(lib().jd_dec_best_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # -- DecoderBatchTest inner loop
     def decode_batch(self, feats: Sequence[np.ndarray]) -> List[Hyp]:

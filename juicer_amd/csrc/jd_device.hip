@@ -57,6 +57,7 @@
 #include "jd_ahead.h"           // working ahead: the queue of announced batches, tables and banks, decode_wave's decisions
 #include "jd_pipe.h"            // batches through the resident slot kernel: the mailbox record, the slot pipeline's bookkeeping and pump decisions
 #include "jd_push.h"            // the streaming interface: a stream's record, argument checks, PARTIAL_DECODING's schedule, packing, k_partial_many's layout
+#include "jd_best.h"            // the current best hypothesis of live streams: k_best_many's layout, what a reply means, the word projection
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -304,6 +305,9 @@ struct jd_dec {
     // ... k_partial_many's buffers (trace_partial_many): [int4 work list][{found, n} heads][staging], for max_streams entries, on the
     // device and pinned on the host
     int *d_pmany = nullptr, *h_pmany = nullptr;
+    // ... and k_best_many's (jd_streams_best; best_layout, jd_best.h), with the launches and device-to-host copies those calls have made
+    int *d_best = nullptr, *h_best = nullptr;
+    int64_t best_launches = 0, best_copies = 0;
     // ... k_partial's export of the model-level list of the same traces (PushStream::partial_m, jd_stream_partial_models),
     // [model, label, time, score, ac, lm][res_cap] (model-level output only, allocated with d_res_model)
     int *d_partial_model = nullptr;
@@ -403,6 +407,7 @@ extern "C" void jd_dec_destroy(jd_dec *d)
     if (d->d_push) (void)hipFree(d->d_push);
     if (d->h_stage) (void)hipHostFree(d->h_stage);
     if (d->h_pmany) (void)hipHostFree(d->h_pmany);
+    if (d->h_best) (void)hipHostFree(d->h_best);
     if (d->d_work) (void)hipFree(d->d_work);
     if (d->h_status) (void)hipHostFree(d->h_status);
     if (d->s_gmm) (void)hipStreamDestroy(d->s_gmm);

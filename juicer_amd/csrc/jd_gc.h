@@ -465,6 +465,122 @@ __global__ __launch_bounds__(1024) void k_partial_many(DecConst C, StreamCtl *ct
     }
 }
 
+// The CURRENT BEST hypothesis of the streams of a work list (jd_streams_best), one workgroup each: work[i].x = the stream.  The best
+// token is the emitting-state token with the highest score among the instance records of the list the next frame reads - the slots
+// k_gc_mark walks; entry tokens pending at states have not been scored on a frame and are no candidates.  Equal scores: the lowest
+// arc number (h0.x, the decoder's own arc order), then the lowest HMM state - nothing that depends on where a record lies in its
+// list or which Path index it got.
+//   1. every wave scans its share of the records and reduces (ordered score << 32 | ~arc, NE + 1 - state) lexicographically - the arc
+//      takes all 32 bits of the low word (a lazily composed network numbers arcs up to 2^31), so the state rides beside the key -
+//      with __shfl_xor, the 16 waves' results meet in LDS;
+//   2. the lane that holds the winner (an arc has one instance in a list) writes the head: out[BEST_HEAD i ..] = found, -, n_words,
+//      n_records, the arc's in-label, the state, score, ac, lm (BestHead, jd_best.h; the host fills the frame);
+//   3. the chain of the token's Path is counted by one thread, as jd_partial_trace counts pm's, and - where it fits res_cap - written
+//      oldest first into the stream's own result arrays (scratch between finishes, rewritten whole by every trace; the model row
+//      res_model[stream][res_cap] at model level, else null) and, where it fits a share, into entry i's share of the staging area
+//      behind the heads (BEST_STAGE_AT).
+// Reads the arenas, writes the result arrays and its own buffer only (gc_idx, the trace's chain scratch, is not touched).  Every
+// return is the whole workgroup's: it depends on the stream's own state or on shared words read behind a barrier.
+template <int NE>
+__global__ __launch_bounds__(1024) void k_best_many(DecConst C, const StreamCtl *ctl, const StreamDev *streams, const int4 *work, int n_work, int *out,
+                                                    int *res_model)
+{
+    typedef RecLayout<NE> RL;
+    __shared__ unsigned long long sh_key[16];
+    __shared__ int sh_ist[16];
+    __shared__ int sh_path, sh_n;
+    const int i = blockIdx.x;
+    if (i >= n_work) return;                                           // (uniform)
+    const int s = work[i].x;
+    const StreamCtl &c = ctl[s];
+    const StreamDev &S = streams[s];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int *head = out + (size_t)BEST_HEAD * i;
+    if (tid < BEST_HEAD) head[tid] = 0;
+    if (!c.started || c.needs_init || c.error != 0 || c.lst_nw <= 0) return;
+    // 1. the scan
+    const int nw = c.lst_nw, p = c.frame & 1;
+    const Geo g = make_geo(C, nw);
+    unsigned long long key = 0ULL;                                     // (0: no candidate - the ordered form of a score > LOG_ZERO is not 0)
+    int ist = 0, arc = -1;
+    int4 tok = make_int4(0, 0, 0, -1);
+    for (int w = wid; w < nw; w += 16) {
+        const char *seg = (const char *)S.rec + (size_t)p * C.cap_slots * RL::REC_BYTES + (size_t)w * (g.seg_rec >> 6) * RL::CHUNK_BYTES;
+        const int n_rec = min(S.tot[(size_t)(TOT_REC0 + p) * MAXW + w], (int)g.seg_rec);
+        for (int k = lane; k < n_rec * NE; k += 64) {
+            const int q = k / NE, j = k - q * NE + 1;
+            const char *r = seg + (size_t)(q >> 6) * RL::CHUNK_BYTES + (size_t)(q & 63) * 16;
+            const int4 h0 = *(const int4 *)r;
+            if (j < (h0.y & 0xff) - 1) {
+                const int4 t = *(const int4 *)(r + (size_t)(RL::HF + j - 1) * 1024);
+                if (__int_as_float(t.x) > LZ) {
+                    const unsigned long long kk = ((unsigned long long)f2o(__int_as_float(t.x)) << 32) | (unsigned)~h0.x;
+                    const int is = NE + 1 - j;
+                    if (kk > key || (kk == key && is > ist)) { key = kk; ist = is; arc = h0.x; tok = t; }
+                }
+            }
+        }
+    }
+    unsigned long long bk = key;
+    int bi = ist;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long ok = __shfl_xor(bk, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ok > bk || (ok == bk && oi > bi)) { bk = ok; bi = oi; }
+    }
+    if (lane == 0) { sh_key[wid] = bk; sh_ist[wid] = bi; }
+    __syncthreads();
+    bk = sh_key[0]; bi = sh_ist[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+        const unsigned long long ok = sh_key[w];
+        const int oi = sh_ist[w];
+        if (ok > bk || (ok == bk && oi > bi)) { bk = ok; bi = oi; }
+    }
+    if (bk == 0ULL) return;                                            // no live emitting token (the same in every thread)
+    // 2. the head
+    if (key == bk && ist == bi) {
+        const int in = C.lazy ? C.lazy->arcs[arc].in : C.arcs[arc].in;
+        head[4] = in & ~ARC_FLAGS; head[5] = NE + 1 - ist;
+        head[6] = tok.x; head[7] = tok.y; head[8] = tok.z;
+        sh_path = tok.w;
+    }
+    __syncthreads();
+    // 3. the chain
+    const int path = sh_path, cap = S.res_cap;
+    if (tid == 0) {
+        int n = 0, n_words = 0;
+        for (int q = path; q >= 0;) {
+            const int4 a = *(const int4 *)&S.paths[q];                 // {prev, frame, label, model}
+            ++n; n_words += a.z != 0;
+            q = a.x;
+        }
+        if (n <= cap) {                                                // the record indices oldest first, which every thread then replaces
+            int k = n;
+            for (int q = path; q >= 0; q = S.paths[q].prev) S.res_label[--k] = q;
+        }
+        sh_n = n;
+        head[2] = n_words; head[3] = n; head[0] = 1;
+    }
+    __syncthreads();
+    const int n = sh_n;
+    if (n > cap) return;
+    const bool staged = n <= BEST_SHARE;
+    int *stage = out + BEST_STAGE_AT(n_work, i);
+    int *rm = res_model ? res_model + (size_t)s * cap : nullptr;
+    for (int k = tid; k < n; k += blockDim.x) {
+        const PathRec pr = S.paths[S.res_label[k]];
+        S.res_label[k] = pr.label; S.res_time[k] = pr.frame; S.res_score[k] = pr.score; S.res_ac[k] = pr.ac; S.res_lm[k] = pr.lm;
+        if (rm) rm[k] = pr.model;
+        if (staged) {
+            stage[BEST_STAGE_WORD(0, k)] = pr.model; stage[BEST_STAGE_WORD(1, k)] = pr.label; stage[BEST_STAGE_WORD(2, k)] = pr.frame;
+            stage[BEST_STAGE_WORD(3, k)] = __float_as_int(pr.score); stage[BEST_STAGE_WORD(4, k)] = __float_as_int(pr.ac);
+            stage[BEST_STAGE_WORD(5, k)] = __float_as_int(pr.lm);
+        }
+    }
+}
+
 // recognitionFinish (:230-309): walk the Path chain of bestFinalToken.  res_model (model-level output, else null): the records'
 // models beside the five arrays, [stream][res_cap] - every record then, and the host picks the words out.
 __global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int n, int *res_model)

@@ -1,7 +1,8 @@
 // jd_host_stream.h - the IDecoder seam of the C ABI (included by jd_device.hip): jd_stream_init / _push / _finish (IDecoder::init /
 // processFrame / finish, src/Decoder.h:18-30, src/WFSTDecoderLite.cpp:139-372), jd_streams_push (several callers' frames in one launch),
 // PARTIAL_DECODING (jd_dec_set_partial_interval, jd_stream_partial, jd_streams_trace: src/WFSTDecoderLite.cpp:822-896) for one stream
-// and for a list of them, and the collection bookkeeping.  What is DECIDED here - the stream's record, the argument checks, where a
+// and for a list of them, the current best hypothesis of live streams (jd_streams_best; its decisions: jd_best.h), and the collection
+// bookkeeping.  What is DECIDED here - the stream's record, the argument checks, where a
 // chunk or a round ends and what the control words behind a launch mean, the packing of a call, k_partial_many's layout - is jd_push.h
 // (plain functions, tested on the CPU); this file makes the copies, launches and synchronisations between those steps.
 #pragma once
@@ -381,6 +382,117 @@ extern "C" int jd_dec_get_partial_interval(const jd_dec *d, int32_t *interval)
 
 
 #include "jd_host_resident.h"
+
+// The current best hypothesis of each listed stream at the frame it has reached (k_best_many, jd_gc.h; the layout and what a reply
+// means: jd_best.h): ONE launch, one workgroup per stream that has a frame, and ONE copy back - the heads and, behind them, the chains
+// that fit a staging share; a longer chain is fetched from the stream's result arrays.  The chains stay with the streams' records
+// (PushStream::best) for jd_stream_best_words / _models.  A chain longer than the result capacity fails its stream's entry alone; the
+// first such error is returned.
+static_assert(sizeof(BestRequest) == sizeof(int4), "k_best_many's work list is int4");
+static_assert(sizeof(jd_best) == sizeof(BestHead) && offsetof(jd_best, score) == offsetof(BestHead, score), "jd_best is BestHead");
+static int best_many(jd_dec *d, const std::vector<int> &ss, const std::vector<int> &at, jd_best *out)
+{
+    const int n = (int)ss.size();
+    if (n == 0) return JD_OK;
+    const BestLayout Y = best_layout(d->max_streams);
+    if (!d->d_best) { int rc = dmalloc(d, &d->d_best, Y.words); if (rc) return rc; }
+    if (!d->h_best) HIPCHK(hipHostMalloc((void **)&d->h_best, Y.words * sizeof(int)));
+    BestRequest *hw = (BestRequest *)d->h_best;
+    for (int i = 0; i < n; ++i) hw[i] = best_request(ss[(size_t)i]);
+    hipStream_t st = d->s_search;
+    int *d_out = d->d_best + Y.head_at, *ho = d->h_best + Y.head_at;
+    HIPCHK(hipMemcpyAsync(d->d_best, hw, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
+    if (d->am->max_n <= 5)
+        hipLaunchKernelGGL(k_best_many<3>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_best, n, d_out, res_model_of(d));
+    else
+        hipLaunchKernelGGL(k_best_many<6>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_best, n, d_out, res_model_of(d));
+    HIPCHK(hipGetLastError());
+    d->best_launches += 1;
+    HIPCHK(hipMemcpyAsync(ho, d_out, Y.reply_words(n) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    d->best_copies += 1;
+    int rc_all = JD_OK;
+    std::vector<int32_t> rows, mrow;
+    for (int i = 0; i < n; ++i) {
+        const int s = ss[(size_t)i];
+        PushStream &S = d->push[(size_t)s];
+        BestHead h;
+        memcpy(&h, ho + (size_t)BEST_HEAD * i, sizeof h);
+        h.frame = S.T;
+        const BestReply reply = best_reply(h.found, h.n_records, d->res_cap);
+        if (reply == BEST_NOT_FOUND || reply == BEST_TOO_LONG) {
+            best_clear(S.best);
+            if (reply == BEST_TOO_LONG) {
+                const int rc = jd_fail(JD_ENOMEM, "stream %d: the best hypothesis has %d records (> %d, the result capacity)", s, h.n_records, d->res_cap);
+                if (!rc_all) rc_all = rc;
+            }
+            h = best_none(S.T);
+        } else if (reply == BEST_FROM_STAGE) best_take_stage(S.best, h.n_records, ho + BEST_STAGE_AT(n, i));
+        else {
+            const size_t nr = (size_t)h.n_records;
+            rows.resize(5 * nr);
+            HIPCHK(hipMemcpy2D(rows.data(), nr * 4, d->d_res + (size_t)s * 5 * d->res_cap, (size_t)d->res_cap * 4, nr * 4, 5, hipMemcpyDeviceToHost));
+            d->best_copies += 1;
+            if (d->models) {
+                mrow.resize(nr);
+                HIPCHK(hipMemcpy(mrow.data(), d->d_res_model + (size_t)s * d->res_cap, nr * 4, hipMemcpyDeviceToHost));
+                d->best_copies += 1;
+            }
+            best_take_rows(S.best, h.n_records, rows.data(), d->models ? mrow.data() : nullptr);
+        }
+        memcpy(&out[at[(size_t)i]], &h, sizeof h);
+    }
+    return rc_all;
+}
+
+extern "C" int jd_streams_best(jd_dec *d, int32_t n, const int32_t *streams, jd_best *out)
+{
+    if (push_check_call(d != nullptr, n, streams && out).verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_streams_best: bad argument");
+    if (d->res && d->res->on && !d->pipe_on) return jd_fail(JD_ESTATE, "jd_streams_best: a broker drives this decoder's resident kernel");
+    std::vector<int> ss, at;
+    const BestCheck chk = best_check(d->push, n, streams, &ss, &at);
+    if (chk.verdict == BEST_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_best: bad stream %d (each stream once)", chk.stream);
+    if (chk.verdict == BEST_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_best before jd_stream_init (stream %d)", chk.stream);
+    if (chk.verdict == BEST_ARG_RESIDENT) return jd_fail(JD_ESTATE, "jd_streams_best: stream %d is a broker's (its utterance runs on the resident kernel)", chk.stream);
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    // (a stream without a frame has nothing to look at: not found, its list empty)
+    for (int i = 0; i < n; ++i) {
+        PushStream &S = d->push[(size_t)streams[i]];
+        if (S.T > 0) continue;
+        best_clear(S.best);
+        const BestHead h = best_none(S.T);
+        memcpy(&out[i], &h, sizeof h);
+    }
+    return best_many(d, ss, at, out);
+}
+
+extern "C" int jd_stream_best_words(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *label, int32_t *time, float *score, float *ac, float *lm)
+{
+    if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_best_words: bad argument");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_best_words before jd_stream_init");
+    best_words(d->push[(size_t)s].best, cap, n, label, time, score, ac, lm);
+    return JD_OK;
+}
+
+extern "C" int jd_stream_best_models(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *model, int32_t *label, int32_t *time, float *score,
+                                     float *ac, float *lm)
+{
+    if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_best_models: bad argument");
+    if (!d->models) return jd_fail(JD_ESTATE, "jd_stream_best_models: the decoder's output level is JD_OUTPUT_WORDS");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_best_models before jd_stream_init");
+    best_models(d->push[(size_t)s].best, cap, n, model, label, time, score, ac, lm);
+    return JD_OK;
+}
+
+// the k_best_many launches and the device-to-host copies the jd_streams_best calls of this decoder have made
+extern "C" int jd_dec_best_stats(const jd_dec *d, int64_t *launches, int64_t *copies)
+{
+    if (!d) return jd_fail(JD_EINVAL, "jd_dec_best_stats: null decoder");
+    if (launches) *launches = d->best_launches;
+    if (copies) *copies = d->best_copies;
+    return JD_OK;
+}
 
 // collectPaths runs (WFSTDecoderLite.cpp:362) of stream s since its init, and the frame after which the last one ran
 // (lastPathCollectFrame, :746; -1: none yet).  Counted while PARTIAL_DECODING is on (jd_dec_set_partial_interval > 0).

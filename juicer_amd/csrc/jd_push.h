@@ -23,20 +23,23 @@ struct PushStream {
     int T = 0;                                         // frames pushed so far
     int started = 0;
     int open = 0;                                      // frames pushed since the stream's init, not finished yet (jd_dec_set_output_level)
+    int resident = 0;                                  // the utterance was begun on the resident kernel (jd_res_init: a broker's stream)
     // PARTIAL_DECODING (WFSTDecoderLite.h:199-205)
     int last_collect = -1, last_trace = -1;            // lastPathCollectFrame, lastPartialTraceFrame
     int n_collect = 0;                                 // collections of the stream's utterance so far (jd_stream_collect_info)
     std::vector<int32_t> partial_label, partial_time;  // partialPaths, oldest first
     PushModels partial_m;                              // ... the model-level list of the same traces (jd_stream_partial_models)
+    PushModels best;                                   // the best token's record chain as of the last jd_streams_best, oldest first (jd_best.h)
     void init()                                        // jd_stream_init (WFSTDecoderLite.cpp:179-181, 202-206)
     {
-        T = 0; started = 1; open = 0;
+        T = 0; started = 1; open = 0; resident = 0;
         last_collect = -1; last_trace = -1; n_collect = 0;
         partial_label.clear(); partial_time.clear();
         partial_m = PushModels();
+        best = PushModels();
     }
-    void begin() { T = 0; started = 1; open = 0; }     // jd_res_init: the broker's stream begins an utterance (it runs no PARTIAL_DECODING)
-    void taken_over() { started = 0; T = 0; open = 0; }   // a batch takes every stream over (jd_decode_batch_device)
+    void begin() { T = 0; started = 1; open = 0; resident = 1; }     // jd_res_init: the broker's stream begins an utterance (it runs no PARTIAL_DECODING)
+    void taken_over() { started = 0; T = 0; open = 0; resident = 0; }   // a batch takes every stream over (jd_decode_batch_device)
     // jd_stream_finish: under PARTIAL_DECODING one more trace, from the best token (:245-251) - the hypothesis (n < 0: none) comes
     // newest first, partialPaths are oldest first
     void finish(bool partial, int n, const int32_t *label, const int32_t *time)
