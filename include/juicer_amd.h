@@ -556,7 +556,7 @@ typedef struct jd_timing {
                                  flight": announcements two batches ahead, a batch on at most half of the streams) */
     int32_t slot_launches;    /* of search_launches: launches of the slot kernel (csrc/jd_slot.h: one workgroup per stream, two per
                                  CU - batches of more streams than the chip has CUs) */
-    int32_t trace_launches;   /* partial-trace kernel launches (k_partial, k_partial_many), cumulative over the streaming calls as
+    int32_t trace_launches;   /* partial-trace kernel launches (k_partial, k_partial_many, k_partial_many_models), cumulative over the streaming calls as
                                  search_ms is: a jd_streams_push round traces all its due streams with one */
 } jd_timing;
 int jd_dec_last_timing(const jd_dec *d, jd_timing *out);
@@ -695,6 +695,54 @@ int jd_stream_best_words(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t 
 int jd_stream_best_models(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *model, int32_t *label,
                           int32_t *time, float *score, float *ac, float *lm);
 int jd_dec_best_stats(const jd_dec *d, int64_t *launches, int64_t *copies);
+
+/* The END-OF-UTTERANCE view of live streams: the hypothesis jd_stream_finish would return if the utterance ended now, read
+ * without ending it.  The decoder keeps bestFinalToken behind every frame (WFSTDecoderLite.cpp:513-520): the best token in a
+ * final state, its score with the final-state weight.  found follows jd_stream_finish's rule - that token's score is above
+ * LOG_ZERO and the stream has processed a frame.  The hypothesis is the token's Path chain, OLDEST first like every other live
+ * list; the newest (last) entry carries the token's own score / ac / lm with the final weight (:293-300).  Reversed, the lists
+ * are entry for entry and bit for bit the jd_hyp (jd_stream_final_words, at both output levels: at model level the labelled
+ * entries, the newest of which carries the totals as in jd_hyp) or the jd_model_hyp (jd_stream_final_models) that
+ * jd_stream_finish would return after the same frames, and the head's score / ac / lm are the totals of a non-empty result
+ * (jd_stream_finish reports LOG_ZERO totals for an empty one; the head says the token's).
+ * jd_streams_final serves the n listed streams, each at the frame it has reached, with ONE kernel launch (a workgroup per
+ * stream) and ONE device-to-host copy that brings the heads and every chain of up to 64 records; a longer chain is read from
+ * the stream's result arrays afterwards.  out[i] is stream i's head; the lists stay with the decoder and are read with
+ * jd_stream_final_words / jd_stream_final_models, which only read that host copy, with jd_stream_partial's conventions (*n the
+ * full length, at most cap entries written, any output pointer may be NULL; empty from jd_stream_init on and after a call that
+ * found nothing).  jd_stream_final_models: JD_ESTATE on a word-level decoder.
+ * Non-destructive: allowed wherever jd_streams_best is, mixed freely with the push, trace and best calls, under a trace
+ * interval and on a lazily composed network; it never changes what a later call returns.  Taken behind the same frame,
+ * jd_best.score and jd_final.score are under the same normalisation; the rule that compares them (an endpointer's) is the
+ * caller's.
+ * JD_EINVAL: a null handle or list, n < 0, a stream outside the decoder's range or listed twice.  JD_ESTATE: a listed stream
+ * before its jd_stream_init; a stream, or a decoder, whose resident kernel a broker drives.  JD_ENOMEM: a chain longer than
+ * the result capacity - that stream's entry says found = 0 and its list is empty, the other entries are delivered, and the
+ * first such error is returned.
+ * jd_dec_final_stats: the kernel launches and device-to-host copies these calls have made (cumulative). */
+typedef struct jd_final {
+    int32_t found;        /* 0: no token is in a final state behind the last frame pushed (also: no frame yet, a failed stream) */
+    int32_t frame;        /* frames pushed                                                                                     */
+    int32_t n_words;      /* records with a word label on the chain                                                            */
+    int32_t n_records;    /* all records on the chain (= n_words on a word-level decoder); 0 is possible with found = 1        */
+    float score, ac, lm;  /* bestFinalToken's, final-state weight included: jd_hyp.tot_score / tot_ac / tot_lm of that finish    */
+} jd_final;
+int jd_streams_final(jd_dec *d, int32_t n, const int32_t *streams, jd_final *out);
+int jd_stream_final_words(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *label, int32_t *time,
+                          float *score, float *ac, float *lm);
+int jd_stream_final_models(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *model, int32_t *label,
+                           int32_t *time, float *score, float *ac, float *lm);
+int jd_dec_final_stats(const jd_dec *d, int64_t *launches, int64_t *copies);
+
+/* jd_stream_partial_models(s, trace_now = 1) for a list of streams of a MODEL-level decoder (each once), each at the frame it
+ * has reached: one kernel launch (a workgroup per stream) and one device-to-host copy, as jd_streams_trace is for
+ * jd_stream_partial.  found[i] (found may be NULL) is stream i's trace's result; the lists are read afterwards with
+ * jd_stream_partial_models(s, 0, ...) and jd_stream_partial(s, 0, ...) - both are updated, as by a single-stream trace.
+ * Counts once per call in jd_timing.trace_launches.  JD_ESTATE on a word-level decoder (its counterpart there is
+ * jd_streams_trace); otherwise jd_streams_trace's argument rules.  A list longer than the result capacity fails that stream
+ * alone (JD_ENOMEM; the first such error is returned).  Explicit traces only: jd_dec_set_partial_interval stays refused at
+ * model level. */
+int jd_streams_trace_models(jd_dec *d, int32_t n, const int32_t *streams, int32_t *found);
 
 /* What JD_FLOW_RESIDENT has done so far (cumulative over the decoder's life; a bench reads it on either side of its
  * timed region: frames_searched is what the slots really advanced in between, whatever was announced or handed back). */

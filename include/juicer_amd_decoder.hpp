@@ -334,8 +334,39 @@ public:
         if (n > 0) check(jd_stream_best_models(dec_, 0, n, &n, &models[0], &labels[0], &frames[0], 0, 0, 0));
         return found;
     }
+    // The end-of-utterance view (jd_streams_final): what finish() would return if the utterance ended behind the frames given so
+    // far (buffered frames are flushed first) - the word chain of the best token in a final state, as (output label, frame)
+    // pairs, oldest first.  Nothing is ended: frames may follow.  false: no token is in a final state (no frame yet), the lists
+    // are empty; true with empty lists: a final hypothesis without a word.
+    bool finalPath(std::vector<int> &labels, std::vector<int> &frames)
+    {
+        const bool found = finalNow();
+        int n = 0;
+        check(jd_stream_final_words(dec_, 0, 0, &n, 0, 0, 0, 0, 0));
+        labels.assign((size_t)n, 0); frames.assign((size_t)n, 0);
+        if (n > 0) check(jd_stream_final_words(dec_, 0, n, &n, &labels[0], &frames[0], 0, 0, 0));
+        return found;
+    }
+    // ... at model level (modelLevelOutput): every record of the chain, as bestPath's
+    bool finalPath(std::vector<int> &models, std::vector<int> &labels, std::vector<int> &frames)
+    {
+        const bool found = finalNow();
+        int n = 0;
+        check(jd_stream_final_models(dec_, 0, 0, &n, 0, 0, 0, 0, 0, 0));
+        models.assign((size_t)n, 0); labels.assign((size_t)n, 0); frames.assign((size_t)n, 0);
+        if (n > 0) check(jd_stream_final_models(dec_, 0, n, &n, &models[0], &labels[0], &frames[0], 0, 0, 0));
+        return found;
+    }
 
 private:
+    bool finalNow()
+    {
+        flush();
+        const int32_t s = 0;
+        jd_final f;
+        check(jd_streams_final(dec_, 1, &s, &f));
+        return f.found != 0;
+    }
     bool bestNow()
     {
         flush();

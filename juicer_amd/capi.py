@@ -75,6 +75,12 @@ class CBest(C.Structure):
                 ("score", C.c_float), ("ac", C.c_float), ("lm", C.c_float)]
 
 
+class CFinal(C.Structure):
+    """jd_final: the head of a stream's end-of-utterance view (jd_streams_final)."""
+    _fields_ = [("found", C.c_int32), ("frame", C.c_int32), ("n_words", C.c_int32), ("n_records", C.c_int32),
+                ("score", C.c_float), ("ac", C.c_float), ("lm", C.c_float)]
+
+
 class PipeStats(C.Structure):
     _fields_ = [("mode", C.c_int32), ("depth", C.c_int32), ("slots", C.c_int32), ("resident", C.c_int32),
                 ("batches_announced", C.c_int32), ("pad0", C.c_int32),
@@ -138,6 +144,7 @@ EXPORTS = [
     "jd_streams_trace", "jd_dec_get_partial_interval", "jd_broker_partial", "jd_debug_score_rows",
     "jd_debug_paths",
     "jd_streams_best", "jd_stream_best_words", "jd_stream_best_models", "jd_dec_best_stats",
+    "jd_streams_final", "jd_stream_final_words", "jd_stream_final_models", "jd_dec_final_stats", "jd_streams_trace_models",
 ]
 
 _lib = None
@@ -798,6 +805,71 @@ class Decoder:
         a, b = C.c_int64(0), C.c_int64(0)
         _check(lib().jd_dec_best_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- the end-of-utterance view of live streams (jd_streams_final)
+    def streams_final(self, streams):
+        """What stream_finish would return now for each listed stream (each once), without finishing: one launch and one fetch
+        for all of them (jd_streams_final).  Returns a dict per stream with jd_final's fields; the lists are read with
+        stream_final_words(s) / stream_final_models(s).  A stream whose chain exceeds the result capacity raises (JD_ENOMEM)
+        after the others were served: the error carries what was delivered as .entries."""
+        ss = _i32(list(streams))
+        n = int(ss.shape[0])
+        out = (CFinal * max(1, n))()
+        rc = lib().jd_streams_final(self.h, C.c_int32(n), _p(ss, C.c_int32), out)
+        entries = [{f: getattr(out[i], f) for f, _ in CFinal._fields_} for i in range(n)]
+        if rc != 0:
+            err = JuicerAmdError(rc, lib().jd_last_error().decode())
+            err.entries = entries if rc == JD_ENOMEM else None
+            raise err
+        return entries
+
+    def stream_final_words(self, s: int = 0):
+        """The word list of stream s's final hypothesis as of the last streams_final, OLDEST first: (label, time, score, ac, lm)
+        arrays (jd_stream_final_words); reversed it is the Hyp of a stream_finish behind the same frames."""
+        n = C.c_int32(0)
+        cap = 256
+        while True:
+            lab, tim = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+            sc, ac, lm = (np.zeros(cap, np.float32) for _ in range(3))
+            _check(lib().jd_stream_final_words(self.h, C.c_int32(s), C.c_int32(cap), C.byref(n), _p(lab, C.c_int32), _p(tim, C.c_int32),
+                                               _p(sc, C.c_float), _p(ac, C.c_float), _p(lm, C.c_float)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        k = n.value
+        return lab[:k].copy(), tim[:k].copy(), sc[:k].copy(), ac[:k].copy(), lm[:k].copy()
+
+    def stream_final_models(self, s: int = 0) -> "ModelHyp":
+        """Every record of the chain of stream s's final hypothesis as of the last streams_final, OLDEST first, as a ModelHyp
+        (jd_stream_final_models, JD_OUTPUT_MODELS only); tot_* are 0 (the totals: the entry of streams_final)."""
+        n = C.c_int32(0)
+        cap = 256
+        while True:
+            mod, lab, tim = (np.zeros(cap, np.int32) for _ in range(3))
+            sc, ac, lm = (np.zeros(cap, np.float32) for _ in range(3))
+            _check(lib().jd_stream_final_models(self.h, C.c_int32(s), C.c_int32(cap), C.byref(n), _p(mod, C.c_int32), _p(lab, C.c_int32),
+                                                _p(tim, C.c_int32), _p(sc, C.c_float), _p(ac, C.c_float), _p(lm, C.c_float)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        k = n.value
+        return ModelHyp(n=k, model=mod[:k].copy(), label=lab[:k].copy(), time=tim[:k].copy(), score=sc[:k].copy(),
+                        ac=ac[:k].copy(), lm=lm[:k].copy(), tot_score=0.0, tot_ac=0.0, tot_lm=0.0)
+
+    def final_stats(self):
+        """(kernel launches, device-to-host copies) the streams_final calls of this decoder have made (jd_dec_final_stats)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _check(lib().jd_dec_final_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def streams_trace_models(self, streams):
+        """stream_partial_models(s, trace_now=True) for each of the listed streams (each once) of a model-level decoder: one launch
+        and one fetch for all of them (jd_streams_trace_models).  Returns found per stream; the lists are read with
+        stream_partial_models(s) and stream_partial(s)."""
+        ss = _i32(list(streams))
+        found = np.zeros(max(1, ss.shape[0]), np.int32)
+        _check(lib().jd_streams_trace_models(self.h, C.c_int32(ss.shape[0]), _p(ss, C.c_int32), _p(found, C.c_int32)))
+        return [bool(f) for f in found[:ss.shape[0]]]
 
     # -- DecoderBatchTest inner loop
     def decode_batch(self, feats: Sequence[np.ndarray]) -> List[Hyp]:

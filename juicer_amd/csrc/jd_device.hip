@@ -58,6 +58,7 @@
 #include "jd_pipe.h"            // batches through the resident slot kernel: the mailbox record, the slot pipeline's bookkeeping and pump decisions
 #include "jd_push.h"            // the streaming interface: a stream's record, argument checks, PARTIAL_DECODING's schedule, packing, k_partial_many's layout
 #include "jd_best.h"            // the current best hypothesis of live streams: k_best_many's layout, what a reply means, the word projection
+#include "jd_final.h"           // the end-of-utterance view of live streams: k_final_many's layout, what a reply means, the word projection
 
 #define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -308,6 +309,12 @@ struct jd_dec {
     // ... and k_best_many's (jd_streams_best; best_layout, jd_best.h), with the launches and device-to-host copies those calls have made
     int *d_best = nullptr, *h_best = nullptr;
     int64_t best_launches = 0, best_copies = 0;
+    // ... k_final_many's (jd_streams_final; final_layout, jd_final.h), with its launches and device-to-host copies
+    int *d_final = nullptr, *h_final = nullptr;
+    int64_t final_launches = 0, final_copies = 0;
+    // ... and k_partial_many_models' (jd_streams_trace_models; partial_models_layout, jd_push.h) with the per-stream area the model lists
+    // are exported into, [stream][model, label, time, score, ac, lm][res_cap]
+    int *d_pmm = nullptr, *h_pmm = nullptr, *d_pmm_area = nullptr;
     // ... k_partial's export of the model-level list of the same traces (PushStream::partial_m, jd_stream_partial_models),
     // [model, label, time, score, ac, lm][res_cap] (model-level output only, allocated with d_res_model)
     int *d_partial_model = nullptr;
@@ -408,6 +415,8 @@ extern "C" void jd_dec_destroy(jd_dec *d)
     if (d->h_stage) (void)hipHostFree(d->h_stage);
     if (d->h_pmany) (void)hipHostFree(d->h_pmany);
     if (d->h_best) (void)hipHostFree(d->h_best);
+    if (d->h_final) (void)hipHostFree(d->h_final);
+    if (d->h_pmm) (void)hipHostFree(d->h_pmm);
     if (d->d_work) (void)hipFree(d->d_work);
     if (d->h_status) (void)hipHostFree(d->h_status);
     if (d->s_gmm) (void)hipStreamDestroy(d->s_gmm);

@@ -581,6 +581,119 @@ __global__ __launch_bounds__(1024) void k_best_many(DecConst C, const StreamCtl 
     }
 }
 
+// The END-OF-UTTERANCE view of the streams of a work list (jd_streams_final), one workgroup each: work[i].x = the stream.  What
+// jd_finish_kernel would export right now - the Path chain of ctl[s].best_final, which both search kernels evaluate behind the last
+// frame of every launch and the collection keeps and remaps - without ending the utterance:
+//   1. found follows jd_finish_kernel's rule (best_final.score > LOG_ZERO and a frame processed), on a stream that is in order;
+//   2. one thread counts the chain (n_records, n_words) as k_best_many's step 3 does, and - where it fits res_cap - puts the record
+//      indices oldest first into res_label; it writes the head: out[FINAL_HEAD i ..] = found, -, n_words, n_records, score, ac, lm
+//      (FinalHead, jd_final.h; the host fills the frame);
+//   3. every thread replaces indices by records: into the stream's own result arrays (scratch between finishes; the model row
+//      res_model[stream][res_cap] where MODELS) and, where the chain fits a share, into entry i's share of the staging area behind
+//      the heads (FINAL_STAGE_AT).  The NEWEST (last) entry carries the token's own score / ac / lm, which include the final-state
+//      weight (:293-300), in both places.
+// The hypothesis is sent whole at every call (FINAL_SHARE: jd_final.h).  Reads the control block and the Path arena, writes the result
+// arrays and its own buffer only - not gc_idx, not the control block.  Every return is the whole workgroup's: it depends on the
+// stream's own state or on a shared word read behind a barrier.
+// FINAL_THREADS = 256: there is no record scan here, so nothing for sixteen waves to divide - the walk is one thread's chain of
+// dependent loads, and the export that follows is n records of two 16-byte loads and six or twelve stores each.  A chain that fits
+// the share (64 records, the live case) is exported by ONE wave in one step; four waves put a res_cap-long chain through in a few
+// dozen steps, and keep the two barriers cheap and the workgroup quick to place beside a running search.
+template <bool MODELS>
+__global__ __launch_bounds__(FINAL_THREADS) void k_final_many(const StreamCtl *ctl, const StreamDev *streams, const int4 *work, int n_work, int *out, int *res_model)
+{
+    __shared__ int sh_n;
+    const int i = blockIdx.x;
+    if (i >= n_work) return;                                           // (uniform)
+    const int s = work[i].x;
+    const StreamCtl &c = ctl[s];
+    const StreamDev &S = streams[s];
+    const int tid = threadIdx.x, cap = S.res_cap;
+    int *head = out + (size_t)FINAL_HEAD * i;
+    // 1. found
+    const Tok best = c.best_final;
+    const bool found = c.started && !c.needs_init && c.error == 0 && c.frame != 0 && best.score > LZ;
+    if (!found) {
+        if (tid < FINAL_HEAD) head[tid] = 0;
+        return;
+    }
+    // 2. the chain, counted and laid out by one thread
+    if (tid == 0) {
+        int n = 0, n_words = 0;
+        for (int q = best.path; q >= 0;) {
+            const int4 a = *(const int4 *)&S.paths[q];                 // {prev, frame, label, model}
+            ++n; n_words += a.z != 0;
+            q = a.x;
+        }
+        if (n <= cap) {
+            int k = n;
+            for (int q = best.path; q >= 0; q = S.paths[q].prev) S.res_label[--k] = q;
+        }
+        sh_n = n;
+        head[0] = 1; head[1] = 0; head[2] = n_words; head[3] = n;
+        head[4] = __float_as_int(best.score); head[5] = __float_as_int(best.ac); head[6] = __float_as_int(best.lm); head[7] = 0;
+    }
+    __syncthreads();
+    const int n = sh_n;
+    if (n > cap) return;
+    // 3. the export: a record's two 16-byte halves are requested together
+    const bool staged = n <= FINAL_SHARE;
+    int *stage = out + FINAL_STAGE_AT(n_work, i);
+    int *rm = MODELS ? res_model + (size_t)s * cap : nullptr;
+    for (int k = tid; k < n; k += blockDim.x) {
+        const PathRec *r = &S.paths[S.res_label[k]];
+        const int4 a = *(const int4 *)r;                               // {prev, frame, label, model}
+        float4 b = *((const float4 *)r + 1);                           // {score, ac, lm, -}
+        if (k == n - 1) { b.x = best.score; b.y = best.ac; b.z = best.lm; }
+        S.res_label[k] = a.z; S.res_time[k] = a.y; S.res_score[k] = b.x; S.res_ac[k] = b.y; S.res_lm[k] = b.z;
+        if (MODELS) rm[k] = a.w;
+        if (staged) {
+            stage[FINAL_STAGE_WORD(0, k)] = a.w; stage[FINAL_STAGE_WORD(1, k)] = a.z; stage[FINAL_STAGE_WORD(2, k)] = a.y;
+            stage[FINAL_STAGE_WORD(3, k)] = __float_as_int(b.x); stage[FINAL_STAGE_WORD(4, k)] = __float_as_int(b.y);
+            stage[FINAL_STAGE_WORD(5, k)] = __float_as_int(b.z);
+        }
+    }
+}
+
+// jd_partial_trace WITH its model export for the streams of a work list (jd_streams_trace_models), one workgroup each: work[i] =
+// {stream, last_frame (the frame of the last word record the host has of it, -1: none), have (the word records the host has), have_m
+// (the model records it has)}.  out[PM_HEAD i ..] = found, n, nm, - (k_partial's out[0..2]); the word chain goes into the stream's
+// own res_label / res_time, the model list into the stream's part of pm_all ([stream][model, label, time, score, ac, lm][res_cap]),
+// the chain scratch is the stream's own gc_idx: the workgroups share nothing.  Both lists extend those of the trace before, so the
+// words [have, n) - where they fit PARTIAL_SHARE - and the model records [have_m, nm) - where they fit PM_SHARE - also go into
+// entry i's share of the staging area behind the heads (PM_STAGE_AT, PM_STAGE_WORD: jd_push.h), which the host fetches with the
+// heads in ONE copy; a stream with more of either is read from the arrays.  k_partial_many stays as it is (its code generation
+// is sensitive to edits: partial_many_stage_at, jd_push.h); this is a kernel beside it.
+template <int NE>
+__global__ __launch_bounds__(1024) void k_partial_many_models(DecConst C, StreamCtl *ctl, StreamDev *streams, const int4 *work, int n_work, int *out, int *pm_all)
+{
+    const int i = blockIdx.x;
+    if (i >= n_work) return;                                           // (uniform)
+    const int4 w = work[i];
+    const StreamDev &S = streams[w.x];
+    const int cap = S.res_cap;
+    int *head = out + (size_t)PM_HEAD * i;
+    int *pm = pm_all + (size_t)w.x * PM_FIELDS * (size_t)cap;
+    if (threadIdx.x == 0) { head[2] = 0; head[3] = 0; }                // (the trace writes head[0..1] always, head[2] where it finds a record: by this thread)
+    const int n = jd_partial_trace<NE>(C, ctl[w.x], S, w.y, head, pm);
+    if (n <= 0 || n > cap) return;                                     // (n is the same in every thread)
+    __syncthreads();                                                   // the chain is in res_label / res_time, the model list in pm, its length in head[2]
+    const int nm = head[2];
+    if (nm > cap) return;
+    const int have = w.z, have_m = w.w;
+    int *stage = out + PM_STAGE_AT(n_work, i);
+    if (have >= 0 && n > have && n - have <= PARTIAL_SHARE)
+        for (int k = have + (int)threadIdx.x; k < n; k += blockDim.x) {
+            stage[2 * (k - have)] = S.res_label[k]; stage[2 * (k - have) + 1] = S.res_time[k];
+        }
+    if (have_m >= 0 && nm > have_m && nm - have_m <= PM_SHARE)
+        for (int k = have_m + (int)threadIdx.x; k < nm; k += blockDim.x) {
+            const int j = k - have_m;
+#pragma unroll
+            for (int f = 0; f < PM_FIELDS; ++f) stage[PM_STAGE_WORD(f, j)] = pm[(size_t)f * cap + k];
+        }
+}
+
 // recognitionFinish (:230-309): walk the Path chain of bestFinalToken.  res_model (model-level output, else null): the records'
 // models beside the five arrays, [stream][res_cap] - every record then, and the host picks the words out.
 __global__ void jd_finish_kernel(StreamCtl *ctl, StreamDev *streams, int s0, int n, int *res_model)

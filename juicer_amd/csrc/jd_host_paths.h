@@ -1,9 +1,9 @@
-// jd_host_paths.h - jd_debug_paths (included by jd_device.hip): the Path collection (launch_gc) and the PARTIAL_DECODING trace (k_partial,
-// k_partial_many) of jd_gc.h on a state the CALLER describes - Path arenas, instance records, frontier items, dirty lists, arrival keys, a
-// tiny graph - instead of one a search left behind.  No decoder, network or model: the description (jd_paths.h, plain words, validated
+// jd_host_paths.h - jd_debug_paths (included by jd_device.hip): the Path collection (launch_gc), the PARTIAL_DECODING trace (k_partial,
+// k_partial_many, k_partial_many_models) and the end-of-utterance view (k_final_many) of jd_gc.h on a state the CALLER describes - Path
+// arenas, instance records, frontier items, dirty lists, arrival keys, a tiny graph - instead of one a search left behind.  No decoder, network or model: the description (jd_paths.h, plain words, validated
 // before any device call) is laid out exactly as the kernels expect it, uploaded, the listed operations run through the production
 // launches, and the state afterwards comes back.  No kernel of its own.  tests/test_gpu_paths.py holds what comes back to
-// tests/paths_ref.py, word for word.
+// tests/paths_ref.py, word for word (the two live views: tests/test_gpu_paths_live.py, tests/paths_live_ref.py).
 #pragma once
 
 #include <string>
@@ -11,6 +11,7 @@
 #include "jd_paths.h"
 
 static_assert(PD_MAXW == MAXW && PD_TOT_N == TOT_N && PD_TOT_REC0 == TOT_REC0 && PD_TOT_DIRTY0 == TOT_DIRTY0 && PD_SHARE == PARTIAL_SHARE, "jd_paths.h: the kernels' constants");
+static_assert(PD_FINAL_HEAD == FINAL_HEAD && PD_FINAL_SHARE == FINAL_SHARE && FINAL_FIELDS == 6 && PD_PM_HEAD == PM_HEAD && PD_PM_SHARE == PM_SHARE && PM_FIELDS == 6, "jd_paths.h: the live views' constants");
 static_assert(PD_GC_WORDS * 4 == sizeof(GcState) && sizeof(PathRec) == 32 && sizeof(JdArc) == 16 && GC_MAXG == 32, "jd_paths.h: the kernels' structs");
 static_assert(RecLayout<3>::HF == 2 && RecLayout<6>::HF == 3 && RecLayout<3>::CHUNK_BYTES == 5 * 1024 && RecLayout<6>::CHUNK_BYTES == 9 * 1024, "jd_paths.h: RecLayout");
 
@@ -120,6 +121,44 @@ extern "C" int jd_debug_paths(int32_t device, const int32_t *desc, int64_t n_des
         }
         const size_t cap = (size_t)O.res_cap;
         HIPCHK(hipMemcpy(h_streams.data(), d_streams, h_streams.size() * sizeof(StreamDev), hipMemcpyDeviceToHost));
+        if (O.kind == PD_FINAL_MANY || O.kind == PD_TRACE_MANY_MODELS) {
+            // [the kernel's reply buffer][per entry: the result arrays it uses][by STREAM: the model rows | the model lists]
+            const bool fin = O.kind == PD_FINAL_MANY;
+            const int n = O.n_work;
+            const size_t reply = fin ? final_layout(n).reply_words(n) : partial_models_layout(n).reply_words(n), per_entry = (fin ? 5 : 2) * cap;
+            TraceOut T;
+            T.words = (size_t)(fin ? PdOp::final_words(n, B, O.res_cap) : PdOp::pm_words(n, B, O.res_cap));
+            int *d_buf = nullptr;
+            if ((rc = dev.filled(&d_buf, T.words, D.sentinel))) return rc;
+            T.d = d_buf;
+            int *by_stream = d_buf + reply + per_entry * (size_t)n;
+            int4 hw[PD_MAX_STREAMS];
+            for (int k = 0; k < n; ++k) {
+                StreamDev &S = h_streams[(size_t)O.streams[k]];
+                S.res_label = d_buf + reply + per_entry * (size_t)k; S.res_time = S.res_label + cap; S.res_cap = O.res_cap;
+                if (fin) {
+                    S.res_score = (float *)(S.res_time + cap); S.res_ac = S.res_score + cap; S.res_lm = S.res_ac + cap;
+                    // the three floats of best_final; its path stays what the device holds (a collection may have remapped it)
+                    StreamCtl c;
+                    HIPCHK(hipMemcpy((void *)&c, d_ctl + O.streams[k], sizeof c, hipMemcpyDeviceToHost));
+                    memcpy(&c.best_final.score, &O.final_tok[k][0], 4); memcpy(&c.best_final.ac, &O.final_tok[k][1], 4); memcpy(&c.best_final.lm, &O.final_tok[k][2], 4);
+                    HIPCHK(hipMemcpy(d_ctl + O.streams[k], (const void *)&c, sizeof c, hipMemcpyHostToDevice));
+                    hw[k] = make_int4(O.streams[k], 0, 0, 0);
+                } else hw[k] = make_int4(O.streams[k], O.last_frame[k], O.have[k], O.have_m[k]);
+            }
+            HIPCHK(hipMemcpy(d_streams, h_streams.data(), h_streams.size() * sizeof(StreamDev), hipMemcpyHostToDevice));
+            int4 *d_work = nullptr;
+            if ((rc = dev.upload(&d_work, hw, (size_t)n * sizeof(int4)))) return rc;
+            if (fin) {
+                if (O.model_level) hipLaunchKernelGGL(k_final_many<true>, dim3((unsigned)n), dim3(FINAL_THREADS), 0, 0, d_ctl, d_streams, (const int4 *)d_work, n, d_buf, by_stream);
+                else hipLaunchKernelGGL(k_final_many<false>, dim3((unsigned)n), dim3(FINAL_THREADS), 0, 0, d_ctl, d_streams, (const int4 *)d_work, n, d_buf, (int *)nullptr);
+            } else if (ne3) hipLaunchKernelGGL(k_partial_many_models<3>, dim3((unsigned)n), dim3(1024), 0, 0, C, d_ctl, d_streams, (const int4 *)d_work, n, d_buf, by_stream);
+            else hipLaunchKernelGGL(k_partial_many_models<6>, dim3((unsigned)n), dim3(1024), 0, 0, C, d_ctl, d_streams, (const int4 *)d_work, n, d_buf, by_stream);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipDeviceSynchronize());
+            traces.push_back(T);
+            continue;
+        }
         // [out: 3 | PD_TRACE_MANY's buffer][per entry: res_label, res_time][pm: 6 res_cap]
         const size_t head = O.kind == PD_TRACE ? 3 : (size_t)(2 + 2 * PARTIAL_SHARE) * (size_t)O.n_work;
         TraceOut T;

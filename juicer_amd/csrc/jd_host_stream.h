@@ -1,9 +1,9 @@
 // jd_host_stream.h - the IDecoder seam of the C ABI (included by jd_device.hip): jd_stream_init / _push / _finish (IDecoder::init /
 // processFrame / finish, src/Decoder.h:18-30, src/WFSTDecoderLite.cpp:139-372), jd_streams_push (several callers' frames in one launch),
 // PARTIAL_DECODING (jd_dec_set_partial_interval, jd_stream_partial, jd_streams_trace: src/WFSTDecoderLite.cpp:822-896) for one stream
-// and for a list of them, the current best hypothesis of live streams (jd_streams_best; its decisions: jd_best.h), and the collection
-// bookkeeping.  What is DECIDED here - the stream's record, the argument checks, where a
-// chunk or a round ends and what the control words behind a launch mean, the packing of a call, k_partial_many's layout - is jd_push.h
+// and for a list of them (at model level: jd_streams_trace_models), the current best hypothesis of live streams (jd_streams_best; its
+// decisions: jd_best.h), their end-of-utterance view (jd_streams_final; jd_final.h), and the collection bookkeeping.  What is
+// DECIDED here - the stream's record, the argument checks, where a chunk or a round ends and what the control words behind a launch mean, the packing of a call, k_partial_many's layout - is jd_push.h
 // (plain functions, tested on the CPU); this file makes the copies, launches and synchronisations between those steps.
 #pragma once
 
@@ -492,6 +492,194 @@ extern "C" int jd_dec_best_stats(const jd_dec *d, int64_t *launches, int64_t *co
     if (launches) *launches = d->best_launches;
     if (copies) *copies = d->best_copies;
     return JD_OK;
+}
+
+// The end-of-utterance view of each listed stream at the frame it has reached (k_final_many, jd_gc.h; the layout and what a reply
+// means: jd_final.h): what jd_stream_finish would return now, read without finishing.  ONE launch, one workgroup per stream that has a
+// frame, and ONE copy back - the heads and, behind them, the chains that fit a staging share; a longer chain is fetched from the
+// stream's result arrays.  The chains stay with the streams' records (PushStream::fin) for jd_stream_final_words / _models.  A chain
+// longer than the result capacity fails its stream's entry alone; the first such error is returned.
+static_assert(sizeof(FinalRequest) == sizeof(int4), "k_final_many's work list is int4");
+static_assert(sizeof(jd_final) == sizeof(FinalHead) && offsetof(jd_final, score) == offsetof(FinalHead, score), "jd_final is FinalHead");
+static int final_many(jd_dec *d, const std::vector<int> &ss, const std::vector<int> &at, jd_final *out)
+{
+    const int n = (int)ss.size();
+    if (n == 0) return JD_OK;
+    const FinalLayout Y = final_layout(d->max_streams);
+    if (!d->d_final) { int rc = dmalloc(d, &d->d_final, Y.words); if (rc) return rc; }
+    if (!d->h_final) HIPCHK(hipHostMalloc((void **)&d->h_final, Y.words * sizeof(int)));
+    FinalRequest *hw = (FinalRequest *)d->h_final;
+    for (int i = 0; i < n; ++i) hw[i] = final_request(ss[(size_t)i]);
+    hipStream_t st = d->s_search;
+    int *d_out = d->d_final + Y.head_at, *ho = d->h_final + Y.head_at;
+    HIPCHK(hipMemcpyAsync(d->d_final, hw, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
+    if (d->models)
+        hipLaunchKernelGGL(k_final_many<true>, dim3((unsigned)n), dim3(FINAL_THREADS), 0, st, d->d_ctl, d->d_streams, (const int4 *)d->d_final, n, d_out, d->d_res_model);
+    else
+        hipLaunchKernelGGL(k_final_many<false>, dim3((unsigned)n), dim3(FINAL_THREADS), 0, st, d->d_ctl, d->d_streams, (const int4 *)d->d_final, n, d_out, (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    d->final_launches += 1;
+    HIPCHK(hipMemcpyAsync(ho, d_out, Y.reply_words(n) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    d->final_copies += 1;
+    int rc_all = JD_OK;
+    std::vector<int32_t> rows, mrow;
+    for (int i = 0; i < n; ++i) {
+        const int s = ss[(size_t)i];
+        PushStream &S = d->push[(size_t)s];
+        FinalHead h;
+        memcpy(&h, ho + (size_t)FINAL_HEAD * i, sizeof h);
+        h.frame = S.T;
+        const FinalReply reply = final_reply(h.found, h.n_records, d->res_cap);
+        if (reply == FINAL_NOT_FOUND || reply == FINAL_TOO_LONG) {
+            best_clear(S.fin);
+            if (reply == FINAL_TOO_LONG) {
+                const int rc = jd_fail(JD_ENOMEM, "stream %d: the final hypothesis has %d records (> %d, the result capacity)", s, h.n_records, d->res_cap);
+                if (!rc_all) rc_all = rc;
+            }
+            h = final_none(S.T);
+        } else if (reply == FINAL_FROM_STAGE) final_take_stage(S.fin, h.n_records, ho + FINAL_STAGE_AT(n, i));
+        else {
+            const size_t nr = (size_t)h.n_records;
+            rows.resize(5 * nr);
+            HIPCHK(hipMemcpy2D(rows.data(), nr * 4, d->d_res + (size_t)s * 5 * d->res_cap, (size_t)d->res_cap * 4, nr * 4, 5, hipMemcpyDeviceToHost));
+            d->final_copies += 1;
+            if (d->models) {
+                mrow.resize(nr);
+                HIPCHK(hipMemcpy(mrow.data(), d->d_res_model + (size_t)s * d->res_cap, nr * 4, hipMemcpyDeviceToHost));
+                d->final_copies += 1;
+            }
+            final_take_rows(S.fin, h.n_records, rows.data(), d->models ? mrow.data() : nullptr);
+        }
+        S.fin_tot[0] = h.score; S.fin_tot[1] = h.ac; S.fin_tot[2] = h.lm;
+        memcpy(&out[at[(size_t)i]], &h, sizeof h);
+    }
+    return rc_all;
+}
+
+extern "C" int jd_streams_final(jd_dec *d, int32_t n, const int32_t *streams, jd_final *out)
+{
+    if (push_check_call(d != nullptr, n, streams && out).verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_streams_final: bad argument");
+    if (d->res && d->res->on && !d->pipe_on) return jd_fail(JD_ESTATE, "jd_streams_final: a broker drives this decoder's resident kernel");
+    std::vector<int> ss, at;
+    const BestCheck chk = final_check(d->push, n, streams, &ss, &at);
+    if (chk.verdict == BEST_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_final: bad stream %d (each stream once)", chk.stream);
+    if (chk.verdict == BEST_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_final before jd_stream_init (stream %d)", chk.stream);
+    if (chk.verdict == BEST_ARG_RESIDENT) return jd_fail(JD_ESTATE, "jd_streams_final: stream %d is a broker's (its utterance runs on the resident kernel)", chk.stream);
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    // (a stream without a frame has nothing behind it: not found, its list empty)
+    for (int i = 0; i < n; ++i) {
+        PushStream &S = d->push[(size_t)streams[i]];
+        if (S.T > 0) continue;
+        best_clear(S.fin);
+        S.fin_tot[0] = S.fin_tot[1] = S.fin_tot[2] = 0.0f;
+        const FinalHead h = final_none(S.T);
+        memcpy(&out[i], &h, sizeof h);
+    }
+    return final_many(d, ss, at, out);
+}
+
+extern "C" int jd_stream_final_words(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *label, int32_t *time, float *score, float *ac, float *lm)
+{
+    if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_final_words: bad argument");
+    const PushStream &S = d->push[(size_t)s];
+    if (!S.started) return jd_fail(JD_ESTATE, "jd_stream_final_words before jd_stream_init");
+    final_words(S.fin, S.fin_tot, cap, n, label, time, score, ac, lm);
+    return JD_OK;
+}
+
+extern "C" int jd_stream_final_models(jd_dec *d, int32_t s, int32_t cap, int32_t *n, int32_t *model, int32_t *label, int32_t *time, float *score,
+                                      float *ac, float *lm)
+{
+    if (!d || s < 0 || s >= d->max_streams || cap < 0 || !n) return jd_fail(JD_EINVAL, "jd_stream_final_models: bad argument");
+    if (!d->models) return jd_fail(JD_ESTATE, "jd_stream_final_models: the decoder's output level is JD_OUTPUT_WORDS");
+    if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_final_models before jd_stream_init");
+    final_models(d->push[(size_t)s].fin, cap, n, model, label, time, score, ac, lm);
+    return JD_OK;
+}
+
+// the k_final_many launches and the device-to-host copies the jd_streams_final calls of this decoder have made
+extern "C" int jd_dec_final_stats(const jd_dec *d, int64_t *launches, int64_t *copies)
+{
+    if (!d) return jd_fail(JD_EINVAL, "jd_dec_final_stats: null decoder");
+    if (launches) *launches = d->final_launches;
+    if (copies) *copies = d->final_copies;
+    return JD_OK;
+}
+
+// trace_partial for a list of streams (each once) of a MODEL-level decoder, each at the frame it has reached: ONE
+// k_partial_many_models launch and ONE copy back - the {found, n, nm} heads and, behind them, the words and model records that are
+// new to the host (jd_gc.h; the layout and what a reply means: jd_push.h).  Both lists of a stream are updated, as trace_partial
+// updates both.  A stream whose trace fails (a list longer than the result capacity) does not keep the others from theirs; the first
+// such error is returned.
+static_assert(sizeof(PartialModelsRequest) == sizeof(int4), "k_partial_many_models' work list is int4");
+static int trace_partial_many_models(jd_dec *d, const std::vector<int> &ss, int32_t *found)
+{
+    const int n = (int)ss.size();
+    if (n == 0) return JD_OK;
+    const PartialModelsLayout Y = partial_models_layout(d->max_streams);
+    if (!d->d_pmm) { int rc = dmalloc(d, &d->d_pmm, Y.words); if (rc) return rc; }
+    if (!d->d_pmm_area) { int rc = dmalloc(d, &d->d_pmm_area, partial_models_area_words(d->max_streams, d->res_cap)); if (rc) return rc; }
+    if (!d->h_pmm) HIPCHK(hipHostMalloc((void **)&d->h_pmm, Y.words * sizeof(int)));
+    PartialModelsRequest *hw = (PartialModelsRequest *)d->h_pmm;
+    for (int i = 0; i < n; ++i) hw[i] = partial_models_request(d->push[(size_t)ss[(size_t)i]], ss[(size_t)i]);
+    hipStream_t st = d->s_search;
+    int *d_out = d->d_pmm + Y.head_at, *ho = d->h_pmm + Y.head_at;
+    HIPCHK(hipMemcpyAsync(d->d_pmm, hw, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
+    if (d->am->max_n <= 5)
+        hipLaunchKernelGGL(k_partial_many_models<3>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmm, n, d_out, d->d_pmm_area);
+    else
+        hipLaunchKernelGGL(k_partial_many_models<6>, dim3((unsigned)n), dim3(1024), 0, st, d->C, d->d_ctl, d->d_streams, (const int4 *)d->d_pmm, n, d_out, d->d_pmm_area);
+    HIPCHK(hipGetLastError());
+    d->timing.trace_launches += 1;
+    HIPCHK(hipMemcpyAsync(ho, d_out, Y.reply_words(n) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int rc_all = JD_OK;
+    std::vector<int32_t> words, rows;
+    for (int i = 0; i < n; ++i) {
+        const int s = ss[(size_t)i];
+        const int *h = ho + (size_t)PM_HEAD * i;
+        const int fnd = h[0], len = h[1], nm = h[2];
+        PushStream &S = d->push[(size_t)s];
+        S.last_trace = S.T - 1;                                        // :867
+        if (found) found[i] = fnd;
+        const int have = (int)S.partial_label.size(), have_m = (int)S.partial_m.model.size();
+        const PartialModelsReply reply = partial_models_reply(fnd, len, nm, have, have_m, d->res_cap);
+        if (reply == PARTIAL_M_NOT_FOUND) continue;
+        if (reply == PARTIAL_M_TOO_LONG) {
+            const int rc = len > d->res_cap ? jd_fail(JD_ENOMEM, "stream %d: partial path has %d records (> %d)", s, len, d->res_cap)
+                                            : jd_fail(JD_ENOMEM, "stream %d: the model-level partial path has %d records (> %d, the result capacity)", s, nm, d->res_cap);
+            if (!rc_all) rc_all = rc;
+            continue;
+        }
+        if (reply == PARTIAL_M_FROM_STAGE) { partial_models_take(S, have, len, have_m, nm, ho + PM_STAGE_AT(n, i)); continue; }
+        words.resize(2 * (size_t)len); rows.resize((size_t)PM_FIELDS * (size_t)nm);
+        HIPCHK(hipMemcpy2D(words.data(), (size_t)len * 4, d->d_res + (size_t)s * 5 * d->res_cap, (size_t)d->res_cap * 4, (size_t)len * 4, 2, hipMemcpyDeviceToHost));
+        if (nm)
+            HIPCHK(hipMemcpy2D(rows.data(), (size_t)nm * 4, d->d_pmm_area + (size_t)s * PM_FIELDS * d->res_cap, (size_t)d->res_cap * 4, (size_t)nm * 4, PM_FIELDS,
+                               hipMemcpyDeviceToHost));
+        partial_models_take_arrays(S, len, words.data(), nm, rows.data());
+    }
+    return rc_all;
+}
+
+// tracePartialPath now on each of the listed streams of a model-level decoder (jd_stream_partial_models with trace_now, for a list):
+// one launch, one fetch.  Explicit traces only: the interval stays refused at model level.
+extern "C" int jd_streams_trace_models(jd_dec *d, int32_t n, const int32_t *streams, int32_t *found)
+{
+    if (push_check_call(d != nullptr, n, streams != nullptr).verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_streams_trace_models: bad argument");
+    if (!d->models) return jd_fail(JD_ESTATE, "jd_streams_trace_models: the decoder's output level is JD_OUTPUT_WORDS (word level: jd_streams_trace)");
+    std::vector<int> ss, at;
+    const PushCheck chk = push_check_trace(d->push, n, streams, found, &ss, &at);
+    if (chk.verdict == PUSH_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_trace_models: bad stream %d (each stream once)", chk.stream);
+    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_trace_models before jd_stream_init (stream %d)", chk.stream);
+    int rc = check_device(d->device);
+    if (rc) return rc;
+    std::vector<int32_t> fnd(ss.size(), 0);
+    rc = trace_partial_many_models(d, ss, fnd.data());
+    if (found) for (size_t k = 0; k < ss.size(); ++k) found[at[k]] = fnd[k];
+    return rc;
 }
 
 // collectPaths runs (WFSTDecoderLite.cpp:362) of stream s since its init, and the frame after which the last one ran

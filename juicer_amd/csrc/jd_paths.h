@@ -1,7 +1,8 @@
 // jd_paths.h - jd_debug_paths' description of a stream state as plain data (no HIP: compiled and tested on the CPU,
 // tests/paths_driver.cpp, tests/test_paths_ref_cpu.py): the words of a description, their validation - nothing that passes it lets a
 // kernel of jd_gc.h follow an index out of an arena - and the byte images of the lists exactly as the kernels read them.
-// jd_host_paths.h allocates, uploads these images, runs launch_gc / k_partial / k_partial_many on them and reads the state back.
+// jd_host_paths.h allocates, uploads these images, runs launch_gc / k_partial / k_partial_many / k_final_many / k_partial_many_models on them and
+// reads the state back.
 //
 // A description is a list of int32 words (floats as their bits):
 //   desc   := PD_MAGIC NE n_streams n_ops cap_slots cap_items cap_new pcount sentinel
@@ -16,11 +17,19 @@
 //   op     := PD_COLLECT n_work stream * max(n_work, 1) G gc_threshold path_rule              (n_work 0: one stream, null work list)
 //           | PD_TRACE stream last_frame res_cap model_level
 //           | PD_TRACE_MANY n {stream last_frame have} * n res_cap
+//           | PD_FINAL_MANY n {stream score ac lm} * n res_cap model_level      (k_final_many; the three floats of the stream's best_final are
+//                                                                                 set first, its path is the stream's - as remapped by any
+//                                                                                 earlier PD_COLLECT)
+//           | PD_TRACE_MANY_MODELS n {stream last_frame have have_m} * n res_cap             (k_partial_many_models)
 // and what comes back is
 //   per stream: n_paths path_new n_collect n_paths_ref path_new_ref best_final_path active kept kept_ref by_rule
 //               {prev frame label model score ac lm} * n_paths   path of every token slot [wave][instance][NE]   path of every item
 //   per PD_TRACE: out[3] res_label[res_cap] res_time[res_cap] pm[6 res_cap]; per PD_TRACE_MANY: the 2 n + 2 PARTIAL_SHARE n words of its buffer
-// (all of a trace's words prefilled with the sentinel).
+//   per PD_FINAL_MANY: the (PD_FINAL_HEAD + 6 PD_FINAL_SHARE) n words of its buffer, per entry res_label res_time res_score res_ac res_lm
+//               [res_cap each], then the model rows [n_streams][res_cap] (written at model_level 1 only)
+//   per PD_TRACE_MANY_MODELS: the (PD_PM_HEAD + 2 PD_SHARE + 6 PD_PM_SHARE) n words of its buffer, per entry res_label res_time [res_cap each],
+//               then the streams' model lists [n_streams][6][res_cap]
+// (all of a trace's or a look's words prefilled with the sentinel).
 #pragma once
 
 #include <cstdint>
@@ -29,13 +38,17 @@
 #include <vector>
 
 #define PD_MAGIC 0x4a445031
-enum { PD_COLLECT = 1, PD_TRACE = 2, PD_TRACE_MANY = 3 };
+enum { PD_COLLECT = 1, PD_TRACE = 2, PD_TRACE_MANY = 3, PD_FINAL_MANY = 4, PD_TRACE_MANY_MODELS = 5 };
 // what the kernels' headers call these (jd_host_paths.h holds them to the kernels' own with static_asserts)
 #define PD_MAXW 512
 #define PD_TOT_N 10
 #define PD_TOT_REC0 0
 #define PD_TOT_DIRTY0 3
 #define PD_SHARE 32
+#define PD_FINAL_HEAD 8
+#define PD_FINAL_SHARE 64
+#define PD_PM_HEAD 4
+#define PD_PM_SHARE 112
 #define PD_GC_WORDS 68
 #define PD_MAX_STREAMS 4
 #define PD_MAX_PATHS (1 << 18)
@@ -56,6 +69,12 @@ struct PdOp {
     int kind = 0;
     int n_work = 0, streams[PD_MAX_STREAMS] = {0, 0, 0, 0}, G = 0, gc_threshold = 0, path_rule = 0;                       // PD_COLLECT
     int last_frame[PD_MAX_STREAMS] = {0, 0, 0, 0}, have[PD_MAX_STREAMS] = {0, 0, 0, 0}, res_cap = 0, model_level = 0;     // the traces
+    int have_m[PD_MAX_STREAMS] = {0, 0, 0, 0};                                                                            // PD_TRACE_MANY_MODELS
+    int32_t final_tok[PD_MAX_STREAMS][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};                                  // PD_FINAL_MANY: score, ac, lm (bits)
+    // the words a look or a model trace of n entries brings back
+    static long long final_words(int n, int n_streams, int res_cap) { return (PD_FINAL_HEAD + 6LL * PD_FINAL_SHARE) * n + 5LL * res_cap * n + (long long)n_streams * res_cap; }
+    static long long pm_reply_words(int n) { return (PD_PM_HEAD + 2LL * PD_SHARE + 6LL * PD_PM_SHARE) * n; }
+    static long long pm_words(int n, int n_streams, int res_cap) { return pm_reply_words(n) + 2LL * res_cap * n + 6LL * n_streams * res_cap; }
 };
 struct PdDesc {
     int NE = 0, n_streams = 0, n_ops = 0, cap_slots = 0, cap_items = 0, cap_new = 0, pcount = 0, sentinel = 0, n_states = 0, n_arcs = 0;
@@ -220,10 +239,29 @@ inline bool pd_parse(const int32_t *w, long long n, PdDesc *D, std::string *err)
                 for (int j = 0; j < k; ++j) if (O.streams[j] == O.streams[k]) return pd_err(err, "operation %lld: stream %lld twice", i, O.streams[k]);
             }
             if (!R.take(&O.res_cap)) return pd_err(err, "the description ends inside operation %lld", i);
+        } else if (O.kind == PD_FINAL_MANY || O.kind == PD_TRACE_MANY_MODELS) {
+            if (!R.take(&O.n_work) || O.n_work < 1 || O.n_work > D->n_streams) return pd_err(err, "operation %lld: a work list of %lld streams", i, O.n_work);
+            for (int k = 0; k < O.n_work; ++k) {
+                int a, b, c;
+                if (!R.take(&O.streams[k]) || !R.take(&a) || !R.take(&b) || !R.take(&c)) return pd_err(err, "the description ends inside operation %lld", i);
+                if (!stream_ok(O.streams[k])) return pd_err(err, "operation %lld: bad stream", i);
+                for (int j = 0; j < k; ++j) if (O.streams[j] == O.streams[k]) return pd_err(err, "operation %lld: stream %lld twice", i, O.streams[k]);
+                if (O.kind == PD_FINAL_MANY) { O.final_tok[k][0] = a; O.final_tok[k][1] = b; O.final_tok[k][2] = c; }
+                else {
+                    O.last_frame[k] = a; O.have[k] = b; O.have_m[k] = c;
+                    if (b < 0 || c < 0) return pd_err(err, "operation %lld: have %lld / have_m %lld < 0", i, b, c);
+                }
+            }
+            if (!R.take(&O.res_cap)) return pd_err(err, "the description ends inside operation %lld", i);
+            if (O.kind == PD_FINAL_MANY) {
+                if (!R.take(&O.model_level)) return pd_err(err, "the description ends inside operation %lld", i);
+                if (O.model_level != 0 && O.model_level != 1) return pd_err(err, "operation %lld: model_level %lld (0 or 1)", i, O.model_level);
+            }
         } else return pd_err(err, "operation %lld: kind %lld", i, O.kind);
         if (O.kind != PD_COLLECT) {
             if (O.res_cap < 1 || O.res_cap > PD_MAX_RES_CAP) return pd_err(err, "operation %lld: res_cap %lld outside [1, 2^16]", i, O.res_cap);
-            out += O.kind == PD_TRACE ? 3 + 8LL * O.res_cap : (2LL + 2LL * PD_SHARE) * O.n_work;
+            out += O.kind == PD_TRACE ? 3 + 8LL * O.res_cap : O.kind == PD_TRACE_MANY ? (2LL + 2LL * PD_SHARE) * O.n_work
+                   : O.kind == PD_FINAL_MANY ? PdOp::final_words(O.n_work, D->n_streams, O.res_cap) : PdOp::pm_words(O.n_work, D->n_streams, O.res_cap);
         }
     }
     if (R.at != n) return pd_err(err, "%lld words behind the description's end", n - R.at);

@@ -1,7 +1,7 @@
 // jd_push.h - the streaming interface (jd_stream_init / _push / _finish, jd_streams_push, jd_streams_trace) as DECISIONS: the host's
 // record of a stream, what a call's arguments are refused for, PARTIAL_DECODING's schedule (src/WFSTDecoderLite.cpp:358-368: where a
 // chunk or a round ends, what the control words read behind a launch mean, who collects, when a trace is due), the packing of a
-// jd_streams_push call and the layout of k_partial_many's buffers.  Plain functions over plain structs, no HIP: jd_host_stream.h makes
+// jd_streams_push call and the layout of k_partial_many's and k_partial_many_models' buffers.  Plain functions over plain structs, no HIP: jd_host_stream.h makes
 // the copies, launches and synchronisations between them; tests/push_driver.cpp runs them on the CPU (tests/test_push_cpu.py).  That
 // driver carries a twin of jd_stream_push's loop and of streams_push_rounds with the device replaced by a model: whoever changes how
 // these functions are called changes both.
@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "jd_prep.h"            // path_rule_fires, PARTIAL_SHARE: what the kernels use of the same rules
@@ -30,6 +31,8 @@ struct PushStream {
     std::vector<int32_t> partial_label, partial_time;  // partialPaths, oldest first
     PushModels partial_m;                              // ... the model-level list of the same traces (jd_stream_partial_models)
     PushModels best;                                   // the best token's record chain as of the last jd_streams_best, oldest first (jd_best.h)
+    PushModels fin;                                    // bestFinalToken's record chain as of the last jd_streams_final, oldest first (jd_final.h)
+    float fin_tot[3] = {0.0f, 0.0f, 0.0f};             // ... and its totals: the token's score, ac, lm with the final-state weight
     void init()                                        // jd_stream_init (WFSTDecoderLite.cpp:179-181, 202-206)
     {
         T = 0; started = 1; open = 0; resident = 0;
@@ -37,6 +40,7 @@ struct PushStream {
         partial_label.clear(); partial_time.clear();
         partial_m = PushModels();
         best = PushModels();
+        fin = PushModels(); fin_tot[0] = fin_tot[1] = fin_tot[2] = 0.0f;
     }
     void begin() { T = 0; started = 1; open = 0; resident = 1; }     // jd_res_init: the broker's stream begins an utterance (it runs no PARTIAL_DECODING)
     void taken_over() { started = 0; T = 0; open = 0; resident = 0; }   // a batch takes every stream over (jd_decode_batch_device)
@@ -251,4 +255,80 @@ static inline PartialReply partial_many_reply(int found, int len, int have, int 
 static inline void partial_many_take(PushStream &P, int have, int len, const int *stage)
 {
     for (int k = have; k < len; ++k) { P.partial_label[(size_t)k] = stage[2 * (k - have)]; P.partial_time[(size_t)k] = stage[2 * (k - have) + 1]; }
+}
+
+// ---- k_partial_many_models' buffers (jd_gc.h; jd_streams_trace_models), for max_streams entries: [int4 work list][heads: PM_HEAD words
+// per entry: found, n (word records), nm (model records), -][staging per entry: PARTIAL_SHARE (label, frame) pairs, then PM_SHARE model
+// records of PM_FIELDS words, field-major].  A launch of n entries writes its n heads and, behind them, its n shares, and the host
+// fetches reply_words(n) in ONE copy.  A trace's lists extend the lists of the trace before it (both of them: the model list ends at
+// the record the word list ends at), so only the words [have, n) and the model records [have_m, nm) are new to the host.
+// PM_SHARE: the word share is PARTIAL_SHARE = 32 new words per trace (its reasoning: at k_partial_many).  A model-level chain carries
+// every model the path has left beside the word labels; on the measured utterance of DESIGN.md section 7 that is 59 model entries
+// where the word list has 17, so the model records that 32 new words bring are 32 * 59 / 17 = 111.06: 112, which also keeps every
+// field of a share a multiple of 16 bytes long (448 bytes).  A stream with more new records of either kind (a first trace late in a
+// long utterance) is read from the device arrays instead.
+#define PM_SHARE 112
+#define PM_FIELDS 6             // model, label, time, score, ac, lm
+#define PM_HEAD 4
+#define PM_PER ((size_t)PM_HEAD + 2 * (size_t)PARTIAL_SHARE + (size_t)PM_FIELDS * PM_SHARE)
+// where entry i's share begins in the words a launch of n entries writes: its word pairs first, its model records behind them, field
+// f of new record k (kernel and host)
+#define PM_STAGE_AT(n, i) ((size_t)PM_HEAD * (size_t)(n) + (2 * (size_t)PARTIAL_SHARE + (size_t)PM_FIELDS * PM_SHARE) * (size_t)(i))
+#define PM_STAGE_MODELS (2 * (size_t)PARTIAL_SHARE)
+#define PM_STAGE_WORD(f, k) (PM_STAGE_MODELS + (size_t)(f) * PM_SHARE + (size_t)(k))
+struct PartialModelsLayout {
+    size_t head_at, per, words;
+    size_t reply_words(int n) const { return per * (size_t)n; }
+};
+static inline PartialModelsLayout partial_models_layout(int max_streams)
+{
+    const size_t M = (size_t)max_streams, head_at = 4 * M;
+    return PartialModelsLayout{head_at, PM_PER, head_at + PM_PER * M};
+}
+// the per-stream area the kernel exports a trace's model list into: [model, label, time, score, ac, lm][res_cap] for every stream
+static inline size_t partial_models_area_words(int max_streams, int res_cap) { return (size_t)max_streams * PM_FIELDS * (size_t)res_cap; }
+// the request of a stream: {stream, the frame of the last word record the host has of it (-1: none), the word records it has, the
+// model records it has}
+struct PartialModelsRequest { int stream, last_frame, have, have_m; };
+static inline PartialModelsRequest partial_models_request(const PushStream &P, int s)
+{
+    return PartialModelsRequest{s, P.partial_time.empty() ? -1 : P.partial_time.back(), (int)P.partial_label.size(), (int)P.partial_m.model.size()};
+}
+// the reply {found, n, nm} of a stream of which the host has `have` words and `have_m` model records: nothing converged; a list
+// longer than the result capacity (an error, the stream's alone); the new entries of both lists from its share of the staging area;
+// or - more than a share of either, or a host that is ahead of the device (never after a trace of this library) - both lists whole
+// from the device arrays
+enum PartialModelsReply { PARTIAL_M_NOT_FOUND = 0, PARTIAL_M_TOO_LONG, PARTIAL_M_FROM_STAGE, PARTIAL_M_FROM_ARRAYS };
+static inline PartialModelsReply partial_models_reply(int found, int n, int nm, int have, int have_m, int res_cap)
+{
+    if (!found) return PARTIAL_M_NOT_FOUND;
+    if (n > res_cap || nm > res_cap) return PARTIAL_M_TOO_LONG;
+    if (have > n || have_m > nm) return PARTIAL_M_FROM_ARRAYS;
+    return (n - have <= PARTIAL_SHARE && nm - have_m <= PM_SHARE) ? PARTIAL_M_FROM_STAGE : PARTIAL_M_FROM_ARRAYS;
+}
+static inline void partial_models_resize(PushModels &M, size_t n) { M.model.resize(n); M.label.resize(n); M.time.resize(n); M.score.resize(n); M.ac.resize(n); M.lm.resize(n); }
+// ... from the staging share (the entry's, at PM_STAGE_AT): words [have, n) and model records [have_m, nm)
+static inline void partial_models_take(PushStream &P, int have, int n, int have_m, int nm, const int *stage)
+{
+    P.partial_label.resize((size_t)n); P.partial_time.resize((size_t)n);
+    for (int k = have; k < n; ++k) { P.partial_label[(size_t)k] = stage[2 * (k - have)]; P.partial_time[(size_t)k] = stage[2 * (k - have) + 1]; }
+    PushModels &M = P.partial_m;
+    partial_models_resize(M, (size_t)nm);
+    for (int k = have_m; k < nm; ++k) {
+        const int j = k - have_m;
+        M.model[(size_t)k] = stage[PM_STAGE_WORD(0, j)]; M.label[(size_t)k] = stage[PM_STAGE_WORD(1, j)]; M.time[(size_t)k] = stage[PM_STAGE_WORD(2, j)];
+        memcpy(&M.score[(size_t)k], &stage[PM_STAGE_WORD(3, j)], 4); memcpy(&M.ac[(size_t)k], &stage[PM_STAGE_WORD(4, j)], 4);
+        memcpy(&M.lm[(size_t)k], &stage[PM_STAGE_WORD(5, j)], 4);
+    }
+}
+// ... or whole from the device arrays: words = [label, time][n] as fetched, rows = [model, label, time, score, ac, lm][nm]
+static inline void partial_models_take_arrays(PushStream &P, int n, const int32_t *words, int nm, const int32_t *rows)
+{
+    const size_t N = (size_t)n, NM = (size_t)nm;
+    P.partial_label.assign(words, words + N); P.partial_time.assign(words + N, words + 2 * N);
+    PushModels &M = P.partial_m;
+    partial_models_resize(M, NM);
+    if (!NM) return;
+    memcpy(M.model.data(), rows, NM * 4); memcpy(M.label.data(), rows + NM, NM * 4); memcpy(M.time.data(), rows + 2 * NM, NM * 4);
+    memcpy(M.score.data(), rows + 3 * NM, NM * 4); memcpy(M.ac.data(), rows + 4 * NM, NM * 4); memcpy(M.lm.data(), rows + 5 * NM, NM * 4);
 }
