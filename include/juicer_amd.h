@@ -242,6 +242,44 @@ int jd_am_load_mmf(jd_am **out, const char *mmf_path);
  * file (the phone list only gives names). */
 int jd_am_create_hybrid(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model);
 
+/* Neural acoustic models: jd_am_create_hybrid's models (same topology, same priors, same refusals: JD_FLOW_RESIDENT, JD_SCORE_FAST,
+ * jd_am_save_jmbi, tile lists) with the NETWORK that yields the log posteriors, so that the caller pushes feature vectors of in_dim
+ * values (jd_am_vec_size) and the device runs the forward pass: a fused kernel behind every scoring call of every entry point
+ * (batches, streaming pushes, jd_streams_push, the broker, jd_multi_*, the C++ adapter).  n_layers >= 1 fully connected layers;
+ * width[n_layers], the last equal to n_phones; act[n_layers - 1]: the HIDDEN layers' activations (NULL when n_layers == 1);
+ * weight[l]: [width[l]][K_l] row-major with K_0 = in_dim, K_l = width[l - 1]; bias[l]: [width[l]].  The outputs of the last layer
+ * are the logits z of a log-softmax, and an emitting state of phone j scores (z[j] - logZ) - log(prior[j]).
+ * Numerics (csrc/jd_mlp.h defines them, jd_am_mlp_forward_host runs them on the host, and the device equals it bit for bit): a
+ * linear output is ONE fmaf chain from the bias, k ascending; RELU y > 0 ? y : 0; SIGMOID 1.0f / (1.0f + expf(-y)); logZ is the
+ * chain of HTKFlatModels::logAdd over z[0], z[1], ... from JD_LOG_ZERO.  A row's result depends on that row alone.
+ * Limits (JD_EINVAL names the one exceeded): in_dim and every width 1 .. 1024, 1 .. 16 layers.  Context splicing is the caller's. */
+#define JD_ACT_LINEAR  0
+#define JD_ACT_RELU    1
+#define JD_ACT_SIGMOID 2
+int jd_am_create_mlp(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model, int32_t in_dim,
+                     int32_t n_layers, const int32_t *width, const int32_t *act, const float *const *weight,
+                     const float *const *bias);
+/* The network's shape: width[n_layers] and act[n_layers] (the last act is JD_ACT_LINEAR) - up to 16 entries; any pointer may be
+ * NULL.  JD_ESTATE for models without a network. */
+int jd_am_mlp_info(const jd_am *a, int32_t *in_dim, int32_t *n_layers, int32_t *width, int32_t *act);
+/* A network and its priors as a file of this project's own (little-endian): "JMLP", u32 version 1, i32 n_phones,
+ * states_per_model, in_dim, n_layers, i32 width[n_layers], i32 act[n_layers] (the last 0), f32 priors[n_phones], then per layer
+ * f32 weight[width][K], f32 bias[width].  Loading a file that is truncated, malformed or longer than its header says: JD_EFORMAT. */
+int jd_am_save_mlp(const jd_am *a, const char *path);
+int jd_am_load_mlp(jd_am **out, const char *path);
+/* The forward pass on its own.  frames: n_frames x in_dim; logpost: n_frames x n_phones log posteriors z - logZ (no priors) - from
+ * HIP device `device`, and from the host twin (needs no device). */
+int jd_am_mlp_forward(const jd_am *a, int32_t device, const float *frames, int32_t n_frames, float *logpost);
+int jd_am_mlp_forward_host(const jd_am *a, const float *frames, int32_t n_frames, float *logpost);
+/* ... and a layer of it, to place a mismatch: out = n_frames x width[layer], the activations behind layer `layer` (the raw logits
+ * for the last).  on_device != 0: the kernel's, from HIP device `device`; 0: the host twin's (device is ignored). */
+int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t on_device, const float *frames, int32_t n_frames, int32_t layer,
+                             float *out);
+/* ... and its time: the scoring launch of these models (launch_gmm's branch, max_blocks as there) on n_frames rows, `warmup` launches
+ * unmeasured, then ms[iters] - one launch each between two events.  tools/mlp_bench.py. */
+int jd_debug_mlp_time(const jd_am *a, int32_t device, const float *frames, int32_t n_frames, int32_t max_blocks, int32_t warmup,
+                      int32_t iters, float *ms);
+
 /* Juicer's binary model cache "<mmf>.bin" (JMBI), preferred by juicer.cpp:778-784:
  * HTKModels::readBinary (HTKModels.cpp:1110-1233) + HTKFlatModels::init.  The derived values in
  * the file (sumLogVarPlusNObsLog2Pi, logCompWeights, transition logProbs) are used as stored. */
@@ -814,7 +852,8 @@ int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const floa
  * whose used rows are not a prefix of it (the kernels let the tile's first row decide); a list entry outside [0, n_rows); listed
  * tiles that overlap; a tile list for hybrid models (launch_gmm would ignore it); and, launch_gmm's own refusal, a tile list for exact
  * scoring of D != 39.  Tile rows: 128 at D = 39
- * and with JD_SCORE_FAST, 64 for exact scoring of any other D, none for hybrid models (which ignore skip_unused).
+ * and with JD_SCORE_FAST, 64 for exact scoring of any other D, none for hybrid models (which ignore skip_unused; those with a network,
+ * jd_am_create_mlp, included: jd_mlp_kernel's tiles of 16 rows are its own affair, and rows with row_src = -1 are written as 0.0f).
  * tests/test_gpu_score_rows.py holds every cell of the buffer to tests/score_rows_cases.py. */
 typedef enum jd_score_kernel {
     JD_KERNEL_NONE = 0,            /* nothing was launched                                  */
@@ -825,7 +864,8 @@ typedef enum jd_score_kernel {
     JD_KERNEL_GMM_FAST39_64 = 5,   /* jd_gmm_fast39<64>                                     */
     JD_KERNEL_GMM_FAST_16 = 6,     /* jd_gmm_fast<16>                                       */
     JD_KERNEL_GMM_FAST_64 = 7,     /* jd_gmm_fast<64>                                       */
-    JD_KERNEL_HYBRID = 8           /* jd_hybrid_kernel                                      */
+    JD_KERNEL_HYBRID = 8,          /* jd_hybrid_kernel                                      */
+    JD_KERNEL_MLP = 9              /* jd_mlp_kernel: jd_am_create_mlp's models, 16-row tiles */
 } jd_score_kernel;
 int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
                         int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,

@@ -145,6 +145,8 @@ EXPORTS = [
     "jd_debug_paths",
     "jd_streams_best", "jd_stream_best_words", "jd_stream_best_models", "jd_dec_best_stats",
     "jd_streams_final", "jd_stream_final_words", "jd_stream_final_models", "jd_dec_final_stats", "jd_streams_trace_models",
+    "jd_am_create_mlp", "jd_am_mlp_info", "jd_am_save_mlp", "jd_am_load_mlp", "jd_am_mlp_forward", "jd_am_mlp_forward_host",
+    "jd_debug_mlp_activations", "jd_debug_mlp_time",
 ]
 
 _lib = None
@@ -493,6 +495,81 @@ class Models:
         _check(lib().jd_am_create_hybrid(C.byref(h), C.c_int32(pr.shape[0]), _p(pr, C.c_float), C.c_int32(states_per_model)))
         return cls(h)
 
+    @classmethod
+    def from_mlp(cls, priors, states_per_model, layers):
+        """Neural acoustic models (jd_am_create_mlp): jd_am_create_hybrid's models with the network that yields the log posteriors.
+        layers: [(weight [out, in], bias [out], act)], act one of ACT_LINEAR / ACT_RELU / ACT_SIGMOID for a hidden layer (the last
+        layer's outputs are the logits; its act is ignored and may be left out).  Feature vectors hold in = layers[0] weight's columns."""
+        pr = _f32(priors)
+        ws = [np.ascontiguousarray(_f32(l[0])) for l in layers]
+        bs = [np.ascontiguousarray(_f32(l[1])) for l in layers]
+        n = len(layers)
+        assert n >= 1 and all(w.ndim == 2 and b.shape == (w.shape[0],) for w, b in zip(ws, bs))
+        assert all(ws[i].shape[1] == ws[i - 1].shape[0] for i in range(1, n))
+        width = _i32([w.shape[0] for w in ws])
+        act = _i32([int(l[2]) for l in layers[:-1]] + [ACT_LINEAR])
+        wp = (C.POINTER(C.c_float) * n)(*[_p(w, C.c_float) for w in ws])
+        bp = (C.POINTER(C.c_float) * n)(*[_p(b, C.c_float) for b in bs])
+        h = C.c_void_p()
+        _check(lib().jd_am_create_mlp(C.byref(h), C.c_int32(pr.shape[0]), _p(pr, C.c_float), C.c_int32(states_per_model),
+                                      C.c_int32(ws[0].shape[1]), C.c_int32(n), _p(width, C.c_int32), _p(act, C.c_int32), wp, bp))
+        return cls(h)
+
+    @classmethod
+    def load_mlp(cls, path):
+        """Neural acoustic models from a JMLP file (jd_am_load_mlp)."""
+        h = C.c_void_p()
+        _check(lib().jd_am_load_mlp(C.byref(h), os.fsencode(path)))
+        return cls(h)
+
+    def save_mlp(self, path):
+        _check(lib().jd_am_save_mlp(self.h, os.fsencode(path)))
+
+    def mlp_info(self):
+        """(in_dim, [width], [act]) of the network (jd_am_mlp_info)."""
+        d, n = C.c_int32(0), C.c_int32(0)
+        width, act = np.zeros(16, np.int32), np.zeros(16, np.int32)
+        _check(lib().jd_am_mlp_info(self.h, C.byref(d), C.byref(n), _p(width, C.c_int32), _p(act, C.c_int32)))
+        return d.value, [int(v) for v in width[:n.value]], [int(v) for v in act[:n.value]]
+
+    def mlp_forward(self, frames, device: int = 0):
+        """The network's log posteriors [T, n_phones] for feature vectors [T, in_dim], from the device (jd_am_mlp_forward)."""
+        x = _f32(frames)
+        assert x.ndim == 2 and (x.shape[0] == 0 or x.shape[1] == self.vec_size)
+        out = np.zeros((x.shape[0], self.n_gmms), np.float32)
+        _check(lib().jd_am_mlp_forward(self.h, C.c_int32(device), _p(x, C.c_float), C.c_int32(x.shape[0]), _p(out, C.c_float)))
+        return out
+
+    def mlp_forward_host(self, frames):
+        """... and from the host twin, which defines them (jd_am_mlp_forward_host; needs no device)."""
+        x = _f32(frames)
+        assert x.ndim == 2 and (x.shape[0] == 0 or x.shape[1] == self.vec_size)
+        out = np.zeros((x.shape[0], self.n_gmms), np.float32)
+        _check(lib().jd_am_mlp_forward_host(self.h, _p(x, C.c_float), C.c_int32(x.shape[0]), _p(out, C.c_float)))
+        return out
+
+    def mlp_activations(self, frames, layer: int, on_device: bool = True, device: int = 0):
+        """The activations [T, width[layer]] behind a layer, the raw logits for the last (jd_debug_mlp_activations): the kernel's or
+        the host twin's."""
+        x = _f32(frames)
+        assert x.ndim == 2 and (x.shape[0] == 0 or x.shape[1] == self.vec_size)
+        width = self.mlp_info()[1]
+        if not 0 <= layer < len(width):
+            raise JuicerAmdError(JD_EINVAL, "mlp_activations: layer %d outside [0, %d)" % (layer, len(width)))
+        out = np.zeros((x.shape[0], width[layer]), np.float32)
+        _check(lib().jd_debug_mlp_activations(self.h, C.c_int32(device), C.c_int32(1 if on_device else 0), _p(x, C.c_float),
+                                              C.c_int32(x.shape[0]), C.c_int32(layer), _p(out, C.c_float)))
+        return out
+
+    def mlp_time(self, frames, warmup: int = 5, iters: int = 20, max_blocks: int = 0, device: int = 0):
+        """ms of `iters` scoring launches of these models on the rows of frames, after `warmup` unmeasured ones (jd_debug_mlp_time)."""
+        x = _f32(frames)
+        assert x.ndim == 2 and x.shape[0] >= 1 and x.shape[1] == self.vec_size
+        ms = np.zeros(iters, np.float32)
+        _check(lib().jd_debug_mlp_time(self.h, C.c_int32(device), _p(x, C.c_float), C.c_int32(x.shape[0]), C.c_int32(max_blocks),
+                                       C.c_int32(warmup), C.c_int32(iters), _p(ms, C.c_float)))
+        return ms
+
     def score_frames(self, frames, device: int = 0, mode: int = 0):
         """Companion GMM kernel on its own: [T, D] -> [T, n_gmm] log-likelihoods (mode: SCORE_EXACT, the default, or SCORE_FAST)."""
         x = _f32(frames)
@@ -506,6 +583,9 @@ class Models:
             _lib.jd_am_destroy(self.h)
             self.h = None
 
+
+# a hidden layer's activation (jd_am_create_mlp)
+ACT_LINEAR, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 
 # jd_debug_log_add's variants: the generic kernel's logAdd, jd_gmm_kernel39's pairwise step, jd_gmm_fast39's (device only)
 LOGADD_GENERIC, LOGADD_PAIR, LOGADD_FAST = 0, 1, 2
@@ -536,6 +616,7 @@ def debug_log1pe(d, variant: int, device: int = -1):
 # jd_debug_score_rows: the kernel launch_gmm chose (jd_score_kernel)
 (KERNEL_NONE, KERNEL_GMM_GENERIC, KERNEL_GMM39_16, KERNEL_GMM39_64, KERNEL_GMM_FAST39_16, KERNEL_GMM_FAST39_64, KERNEL_GMM_FAST_16,
  KERNEL_GMM_FAST_64, KERNEL_HYBRID) = range(9)
+KERNEL_MLP = 9                     # jd_mlp_kernel (Models.from_mlp); beside KERNEL_NAMES, the list of the kernels of tests/score_rows_cases.py
 KERNEL_NAMES = ["none", "jd_gmm_kernel<0>", "jd_gmm_kernel39<16>", "jd_gmm_kernel39<64>", "jd_gmm_fast39<16>", "jd_gmm_fast39<64>",
                 "jd_gmm_fast<16>", "jd_gmm_fast<64>", "jd_hybrid_kernel"]
 

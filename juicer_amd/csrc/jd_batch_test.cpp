@@ -170,6 +170,7 @@ static bool load_features(const char *path, int D, std::vector<float> &x, int32_
 int main(int argc, char **argv)
 {
     const char *fsm = 0, *insyms = 0, *outsyms = 0, *amf = 0, *mmf = 0, *list = 0;
+    const char *mlpf = 0, *monoList = 0;                                     // -mlpFName: a JMLP file (jd_am_load_mlp); its phones' names
     const char *gramFsm = 0, *gramInSyms = 0, *gramOutSyms = 0;              // juicer.cpp:128-130: separate C.L and G
     float mainBeam = 0, startBeam = 0, endBeam = 0, wordBeam = 0, lmScale = 1.0f, insPen = 0.0f;
     int maxHyps = 0, framesPerSec = 100, device = 0, batch = 64, useAdapter = 0, writeBinaryFiles = 0, nDevices = 0, pushing = 0, lazy = 0, nThreads = 0, lookaheadSets = 0;
@@ -192,6 +193,7 @@ int main(int argc, char **argv)
         else if (a == "-lazy") lazy = 1;                                         // compose where the search goes (jd_net_create_lazy)
         else if (a == "-outSymsFName") outsyms = nxt(); else if (a == "-modelsFName") amf = nxt();
         else if (a == "-htkModelsFName") mmf = nxt();
+        else if (a == "-mlpFName") mlpf = nxt();
         else if (a == "-inputFName") list = nxt(); else if (a == "-mainBeam") mainBeam = (float)atof(nxt());
         else if (a == "-phoneStartBeam") startBeam = (float)atof(nxt()); else if (a == "-phoneEndBeam") endBeam = (float)atof(nxt());
         else if (a == "-wordEmitBeam") wordBeam = (float)atof(nxt()); else if (a == "-maxHyps") maxHyps = atoi(nxt());
@@ -209,12 +211,16 @@ int main(int argc, char **argv)
         else if (a == "-sentStartWord") sentStartWord = nxt(); else if (a == "-sentEndWord") sentEndWord = nxt();
         else if (a == "-modelLevelOutput") modelLevel = 1;
         // juicer.cpp's phone-lookup options (-monoListFName, -tiedListFName, -cdSepChars, -silMonophone, -pauseMonophone):
-        // accepted for the command lines that carry them; phones are printed by the models' own names
-        else if (a == "-monoListFName" || a == "-tiedListFName" || a == "-cdSepChars" || a == "-silMonophone" || a == "-pauseMonophone") (void)nxt();
+        // accepted for the command lines that carry them; phones are printed by the models' own names - but for a JMLP file, which
+        // has none: there the monophone list names them
+        else if (a == "-monoListFName") monoList = nxt();
+        else if (a == "-tiedListFName" || a == "-cdSepChars" || a == "-silMonophone" || a == "-pauseMonophone") (void)nxt();
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
-    if (!fsm || (!amf && !mmf) || !list) {
-        fprintf(stderr, "usage: jd_batch_test -fsmFName F (-htkModelsFName M.mmf | -modelsFName M.jdam) -inputFName LIST [-mainBeam b] [-phoneStartBeam b]\n"
+    if (!fsm || (!amf && !mmf && !mlpf) || !list) {
+        fprintf(stderr, "usage: jd_batch_test -fsmFName F (-htkModelsFName M.mmf | -modelsFName M.jdam | -mlpFName M.jmlp) -inputFName LIST [-mainBeam b]\n"
+                        "       [-phoneStartBeam b]   (-mlpFName: a neural acoustic model, jd_am_save_mlp's file; the inputs are then feature vectors of the\n"
+                        "        network's input size, and the device runs its forward pass)\n"
                         "       [-phoneEndBeam b] [-wordEmitBeam b] [-maxHyps n] [-lmScaleFactor s] [-insPenalty p] [-batch n] [-perFrameAdapter]\n"
                         "       [-outputFormat ref|trans|mlf|xmlf|verbose] [-writeBinaryFiles] [-refFName REF] [-removeSentMarks]\n"
                         "       [-sentStartWord W] [-sentEndWord W] [-outSymsFName SYMS] [-outputFName stdout|stderr|FILE]\n"
@@ -228,7 +234,7 @@ int main(int argc, char **argv)
                         "       [-modelLevelOutput   (phones: the HMMs the best path passed, by the models' names, words beside them in mlf / xmlf;\n"
                         "        not with -threads, -devices or -refFName)]\n"
                         "       [-monoListFName F] [-tiedListFName F] [-cdSepChars C] [-silMonophone P] [-pauseMonophone P]   (accepted, no effect:\n"
-                        "        phones are printed by the HMM names of the models file)\n");
+                        "        phones are printed by the HMM names of the models file - except -monoListFName with -mlpFName: line h names phone h)\n");
         return 2;
     }
     if (lookaheadSets && !gramFsm) { fprintf(stderr, "jd_batch_test: -lookaheadSets needs -gramFsmFName (it is an option of the composition)\n"); return 1; }
@@ -278,15 +284,27 @@ int main(int argc, char **argv)
             if (jd_am_load_mmf(&am, mmf)) die("jd_am_load_mmf");
             if (writeBinaryFiles && jd_am_save_jmbi(am, amBin.c_str())) die("jd_am_save_jmbi");
         }
+    } else if (mlpf) {
+        if (jd_am_load_mlp(&am, mlpf)) die("jd_am_load_mlp");
     } else am = load_jdam(amf);
     const int D = jd_am_vec_size(am);
     std::vector<std::string> hmmNames;         // PhoneLookup::getModelStr (juicer.cpp:606-621): the models' names
-    if (modelLevel) {
+    if (modelLevel && mlpf && !mmf && monoList) {                               // (a JMLP file holds no names: line h of the monophone list is phone h)
+        FILE *f = fopen(monoList, "rb");
+        char line[10000], sym[10000];
+        while (f && fgets(line, sizeof line, f))
+            if (sscanf(line, "%9999s", sym) == 1) hmmNames.push_back(sym);
+        if (f) fclose(f);
+        if ((int)hmmNames.size() != jd_am_num_hmms(am)) {
+            fprintf(stderr, "jd_batch_test: -monoListFName %s names %d phones, the network has %d\n", monoList, (int)hmmNames.size(), jd_am_num_hmms(am));
+            return 1;
+        }
+    } else if (modelLevel) {
         for (int h = 0; h < jd_am_num_hmms(am); ++h) {
             const char *nm = 0;
             if (jd_am_hmm_name(am, h, &nm)) die("jd_am_hmm_name");
             if (!nm) {
-                fprintf(stderr, "jd_batch_test: -modelLevelOutput needs the HMMs' names (an MMF or JMBI models file; %s has none)\n", amf ? amf : mmf);
+                fprintf(stderr, "jd_batch_test: -modelLevelOutput needs the HMMs' names (an MMF or JMBI models file, or -monoListFName beside -mlpFName; %s has none)\n", amf ? amf : mmf ? mmf : mlpf);
                 return 1;
             }
             hmmNames.push_back(nm);

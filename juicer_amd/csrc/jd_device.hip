@@ -96,6 +96,7 @@ __device__ __forceinline__ int rank_in(unsigned long long bal)
 
 // ------------------------------------------------------------------- scoring kernels
 #include "jd_gmm.h"
+#include "jd_mlp_kernel.h"      // neural acoustic models: the fused forward pass (jd_mlp.h: the network as data, the host twin)
 
 // --------------------------------------------------------------- search kernels
 #include "jd_search.h"

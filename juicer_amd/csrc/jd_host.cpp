@@ -401,31 +401,128 @@ extern "C" int jd_am_create_flat(jd_am **out, int32_t D, int32_t n_gmm, int32_t 
 // models.  One HMM per phone with statesPerModel states whose emitting states all score
 // x[phone] - log(prior[phone]) (calcOutput, :481-512 / HTKFlatModels.cpp:190-222); ONE transition matrix:
 // entry -> first emitting state 1.0, every emitting state 0.5 self loop / 0.5 forward (:188-207).
-extern "C" int jd_am_create_hybrid(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model)
+// (D: the feature vectors' size - n_phones for jd_am_create_hybrid, the network's in_dim for jd_am_create_mlp; who: the caller's name)
+static int create_hybrid_models(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model, int32_t D, const char *who)
 {
-    if (!out || !priors || n_phones <= 0) return jd_fail(JD_EINVAL, "jd_am_create_hybrid: bad argument");
+    if (!out || !priors || n_phones <= 0 || D <= 0) return jd_fail(JD_EINVAL, "%s: bad argument", who);
     if (states_per_model <= 2) return jd_fail(JD_EINVAL, "HTKModels::Models(3) - statesPerModel <= 2 (ie. no emitting states)");
-    if (states_per_model > JD_MAXN) return jd_fail(JD_EINVAL, "jd_am_create_hybrid: HMMs with more than %d states are not supported", JD_MAXN);
+    if (states_per_model > JD_MAXN) return jd_fail(JD_EINVAL, "%s: HMMs with more than %d states are not supported", who, JD_MAXN);
     const int32_t P = n_phones, N = states_per_model;
     std::vector<int32_t> n_mix((size_t)P, 1), hmm_n((size_t)P, N), hmm_gmm((size_t)P * N, -1), hmm_tm((size_t)P, 0), tm_n(1, N);
-    std::vector<float> weight((size_t)P, 1.0f), mean((size_t)P * P, 0.0f), var((size_t)P * P, 1.0f), transp((size_t)N * N, 0.0f);
+    std::vector<float> weight((size_t)P, 1.0f), mean((size_t)P * D, 0.0f), var((size_t)P * D, 1.0f), transp((size_t)N * N, 0.0f);
     for (int32_t h = 0; h < P; ++h)
         for (int32_t j = 1; j < N - 1; ++j) hmm_gmm[(size_t)h * N + j] = h;     // :176-179 gmmInds[i] = nHMMs
     transp[1] = 1.0f;                                                            // :196-199
     for (int32_t i = 1; i < N - 1; ++i) { transp[(size_t)i * N + i] = 0.5f; transp[(size_t)i * N + i + 1] = 0.5f; }   // :200-204
     jd_am *a = nullptr;
     // (the Gaussian tables are placeholders: in hybrid mode nothing reads them)
-    int rc = jd_am_create_htk(&a, P, P, 1, n_mix.data(), weight.data(), mean.data(), var.data(), P, N, hmm_n.data(), hmm_gmm.data(),
+    int rc = jd_am_create_htk(&a, D, P, 1, n_mix.data(), weight.data(), mean.data(), var.data(), P, N, hmm_n.data(), hmm_gmm.data(),
                               hmm_tm.data(), 1, tm_n.data(), transp.data());
     if (rc) return rc;
     a->hybrid = true;
     a->log_prior.resize((size_t)P);
     for (int32_t h = 0; h < P; ++h) {
-        if (!(priors[h] > 0.0f)) { delete a; return jd_fail(JD_EINVAL, "jd_am_create_hybrid: prior %d is not positive", h); }
+        if (!(priors[h] > 0.0f)) { delete a; return jd_fail(JD_EINVAL, "%s: prior %d is not positive", who, h); }
         a->log_prior[(size_t)h] = std::log(priors[h]);                            // :183 log(float)
     }
     *out = a;
     return JD_OK;
+}
+extern "C" int jd_am_create_hybrid(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model)
+{
+    return create_hybrid_models(out, n_phones, priors, states_per_model, n_phones, "jd_am_create_hybrid");
+}
+
+// Neural acoustic models (jd_mlp.h): jd_am_create_hybrid's topology and priors, and the network that turns a feature vector of
+// in_dim values into the log posteriors - on the device (jd_mlp_kernel behind launch_gmm).  D = in_dim, n_gmm = n_phones.
+static int create_mlp_models(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model, const JdMlpDesc &d,
+                             const float *w, const float *b, const char *who)
+{
+    char why[200];
+    if (jd_mlp_check(d, n_phones, why, sizeof why)) return jd_fail(JD_EINVAL, "%s: %s", who, why);
+    jd_am *a = nullptr;
+    int rc = create_hybrid_models(&a, n_phones, priors, states_per_model, d.in_dim, who);
+    if (rc) return rc;
+    a->mlp = true;
+    a->mlp_desc = d;
+    a->mlp_states_per_model = states_per_model;
+    a->mlp_prior.assign(priors, priors + n_phones);
+    a->mlp_w.assign(w, w + jd_mlp_w_begin(d, d.n_layers));
+    a->mlp_b.assign(b, b + jd_mlp_b_begin(d, d.n_layers));
+    jd_mlp_pack(d, a->mlp_w.data(), a->mlp_b.data(), a->mlp_wp, a->mlp_bp);
+    *out = a;
+    return JD_OK;
+}
+extern "C" int jd_am_create_mlp(jd_am **out, int32_t n_phones, const float *priors, int32_t states_per_model, int32_t in_dim,
+                                int32_t n_layers, const int32_t *width, const int32_t *act, const float *const *weight,
+                                const float *const *bias)
+{
+    if (!out || !priors || !width || !weight || !bias || n_phones <= 0 || (n_layers > 1 && !act)) return jd_fail(JD_EINVAL, "jd_am_create_mlp: bad argument");
+    if (n_layers < 1 || n_layers > JD_MLP_MAX_LAYERS)
+        return jd_fail(JD_EINVAL, "jd_am_create_mlp: n_layers = %d outside 1 .. %d (JD_MLP_MAX_LAYERS)", n_layers, JD_MLP_MAX_LAYERS);
+    JdMlpDesc d;
+    d.in_dim = in_dim; d.n_layers = n_layers;
+    for (int32_t l = 0; l < n_layers; ++l) {
+        if (!weight[l] || !bias[l]) return jd_fail(JD_EINVAL, "jd_am_create_mlp: layer %d has no weights or biases", l);
+        d.width[l] = width[l];
+        d.act[l] = l < n_layers - 1 ? act[l] : JD_ACT_LINEAR;
+    }
+    char why[200];
+    if (jd_mlp_check(d, n_phones, why, sizeof why)) return jd_fail(JD_EINVAL, "jd_am_create_mlp: %s", why);
+    std::vector<float> w(jd_mlp_w_begin(d, n_layers)), b(jd_mlp_b_begin(d, n_layers));
+    for (int32_t l = 0; l < n_layers; ++l) {
+        memcpy(w.data() + jd_mlp_w_begin(d, l), weight[l], (size_t)d.width[l] * jd_mlp_k(d, l) * sizeof(float));
+        memcpy(b.data() + jd_mlp_b_begin(d, l), bias[l], (size_t)d.width[l] * sizeof(float));
+    }
+    return create_mlp_models(out, n_phones, priors, states_per_model, d, w.data(), b.data(), "jd_am_create_mlp");
+}
+extern "C" int jd_am_mlp_info(const jd_am *a, int32_t *in_dim, int32_t *n_layers, int32_t *width, int32_t *act)
+{
+    if (!a) return jd_fail(JD_EINVAL, "jd_am_mlp_info: null");
+    if (!a->mlp) return jd_fail(JD_ESTATE, "jd_am_mlp_info: these models hold no network (jd_am_create_mlp / jd_am_load_mlp make the ones that do)");
+    if (in_dim) *in_dim = a->mlp_desc.in_dim;
+    if (n_layers) *n_layers = a->mlp_desc.n_layers;
+    for (int32_t l = 0; l < a->mlp_desc.n_layers; ++l) {
+        if (width) width[l] = a->mlp_desc.width[l];
+        if (act) act[l] = a->mlp_desc.act[l];
+    }
+    return JD_OK;
+}
+// the JMLP file (jd_mlp.h holds the layout)
+extern "C" int jd_am_save_mlp(const jd_am *a, const char *path)
+{
+    if (!a || !path) return jd_fail(JD_EINVAL, "jd_am_save_mlp: null argument");
+    if (!a->mlp) return jd_fail(JD_ESTATE, "jd_am_save_mlp: these models hold no network");
+    JdMlpFile f;
+    f.d = a->mlp_desc; f.n_phones = a->n_hmm; f.states_per_model = a->mlp_states_per_model;
+    f.priors = a->mlp_prior; f.w = a->mlp_w; f.b = a->mlp_b;
+    std::vector<unsigned char> bytes;
+    jd_mlp_file_write(f, bytes);
+    FILE *fd = fopen(path, "wb");
+    if (!fd) return jd_fail(JD_EFORMAT, "jd_am_save_mlp: error opening file %s", path);
+    const bool ok = fwrite(bytes.data(), 1, bytes.size(), fd) == bytes.size();
+    if (fclose(fd) != 0 || !ok) return jd_fail(JD_EFORMAT, "jd_am_save_mlp: error writing file %s", path);
+    return JD_OK;
+}
+extern "C" int jd_am_load_mlp(jd_am **out, const char *path)
+{
+    if (!out || !path) return jd_fail(JD_EINVAL, "jd_am_load_mlp: null argument");
+    FILE *fd = fopen(path, "rb");
+    if (!fd) return jd_fail(JD_EFORMAT, "jd_am_load_mlp: error opening file %s", path);
+    std::vector<unsigned char> bytes;
+    unsigned char chunk[65536];
+    size_t n;
+    while ((n = fread(chunk, 1, sizeof chunk, fd)) > 0) bytes.insert(bytes.end(), chunk, chunk + n);
+    fclose(fd);
+    JdMlpFile f;
+    char why[300];
+    if (jd_mlp_file_read(bytes.data(), bytes.size(), f, why, sizeof why)) return jd_fail(JD_EFORMAT, "%s: %s", path, why);
+    const int rc = create_mlp_models(out, f.n_phones, f.priors.data(), f.states_per_model, f.d, f.w.data(), f.b.data(), "jd_am_load_mlp");
+    if (rc == JD_EINVAL) {                                             // (a prior that is not positive, a states_per_model outside 3 .. JD_MAXN)
+        const std::string what = jd_last_error();
+        return jd_fail(JD_EFORMAT, "%s: %s", path, what.c_str());
+    }
+    return rc;
 }
 
 extern "C" int32_t jd_am_num_hmms(const jd_am *a) { return a ? a->n_hmm : 0; }

@@ -1,6 +1,6 @@
 // jd_host_scoring.h - the host side of the companion scoring kernels (included by jd_device.hip): the model parameters on the device,
-// launch_gmm (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast, jd_dec_set_scoring's option; the generic and the hybrid kernel),
-// jd_am_score_frames.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
+// launch_gmm (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast, jd_dec_set_scoring's option; the generic and the hybrid kernel;
+// jd_mlp_kernel for the models of jd_am_create_mlp), jd_am_score_frames, jd_am_mlp_forward.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
 #pragma once
 
 // hybrid scoring (HTKFlatModels.cpp:190-222): output = x[model] - log prior; rows as in the GMM kernels
@@ -20,6 +20,7 @@ struct AmDevBuf {
                                     // (DP = jd_fast_dp(D): D = 39 as it is, every other D padded with (0, 0) to jd_gmm_fast's chunk)
     int fast = 0;                   // launch_gmm scores with jd_gmm_fast39 (D = 39) / jd_gmm_fast
     float *log_prior = nullptr;
+    float *mlp_w = nullptr, *mlp_b = nullptr;   // jd_am_create_mlp's models: the packed network (jd_mlp_pack)
     JdLogTab *logtab = nullptr;
     int device = -1;
 };
@@ -48,6 +49,14 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
     if (a->hybrid) {
         HIPCHK(hipMalloc(&b.log_prior, a->log_prior.size() * sizeof(float)));
         HIPCHK(hipMemcpy(b.log_prior, a->log_prior.data(), a->log_prior.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (a->mlp) {
+        HIPCHK(hipMalloc(&b.mlp_w, a->mlp_wp.size() * sizeof(float)));
+        HIPCHK(hipMalloc(&b.mlp_b, a->mlp_bp.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(b.mlp_w, a->mlp_wp.data(), a->mlp_wp.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.mlp_b, a->mlp_bp.data(), a->mlp_bp.size() * sizeof(float), hipMemcpyHostToDevice));
+        // (above 64 KB of dynamic LDS a kernel has to be told; per device, and the same value every time)
+        HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_LDS_MAX));
     }
     return JD_OK;
 }
@@ -83,6 +92,8 @@ static void free_am_gmm(AmDevBuf &b)
     if (b.n_mix) (void)hipFree(b.n_mix);
     if (b.logtab) (void)hipFree(b.logtab);
     if (b.log_prior) (void)hipFree(b.log_prior);
+    if (b.mlp_w) (void)hipFree(b.mlp_w);
+    if (b.mlp_b) (void)hipFree(b.mlp_b);
     b = AmDevBuf();
 }
 
@@ -93,6 +104,20 @@ static size_t gmm_fast_lds() { return (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * si
 
 // which kernel a launch_gmm call ran and on what grid (jd_score_kernel of juicer_amd.h; 0 / 0: nothing was launched)
 struct GmmLaunch { int kernel = JD_KERNEL_NONE; unsigned grid = 0; };
+
+// jd_mlp_kernel on rows [0, n_rows): d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
+static int launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
+                      int max_blocks, int out_mode, int layer, GmmLaunch *info)
+{
+    const JdMlpDev m = jd_mlp_dev(a->mlp_desc);
+    const int tiles = (n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
+    const dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
+    hipLaunchKernelGGL(jd_mlp_kernel, grid, dim3(256), jd_mlp_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
+                       b.logtab, m, d_out, out_mode, layer);
+    HIPCHK(hipGetLastError());
+    if (info) { info->kernel = JD_KERNEL_MLP; info->grid = grid.x; }
+    return JD_OK;
+}
 
 // max_blocks > 0 bounds the grid (the kernel strides over the tiles): next to the search, a
 // chip-filling scoring launch holds every wave slot for milliseconds and the latency-bound search
@@ -108,7 +133,9 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 {
     if (info) *info = GmmLaunch();
     if (n_rows <= 0) return JD_OK;
-    if (a->hybrid) {                                                    // (all of rows [0, n_rows), whatever the other arguments say)
+    // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds jd_mlp_kernel's grid)
+    if (a->mlp) return launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, max_blocks, JD_MLP_OUT_LL, 0, info);
+    if (a->hybrid) {
         const long long n = (long long)n_rows * a->n_gmm;
         const dim3 grid((unsigned)((n + 255) / 256));
         hipLaunchKernelGGL(jd_hybrid_kernel, grid, dim3(256), 0, st, d_feats, d_row_src, n_rows, b.log_prior,
@@ -330,4 +357,93 @@ extern "C" int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode,
     if (kernel) *kernel = info.kernel;
     if (grid) *grid = (int32_t)info.grid;
     return JD_OK;
+}
+
+// ---- the forward pass of jd_am_create_mlp's models on its own (include/juicer_amd.h): the kernel's and the host twin's
+static int mlp_on_device(const jd_am *a, int device, const float *frames, int n_frames, int out_mode, int layer, float *out)
+{
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (n_frames == 0) return JD_OK;
+    ScoreBufs s;
+    rc = upload_am_gmm(a, s.b);
+    if (rc) return rc;
+    const size_t D = (size_t)a->D, W = (size_t)(out_mode == JD_MLP_OUT_LAYER ? a->mlp_desc.width[layer] : a->n_gmm);
+    std::vector<int> src((size_t)n_frames);
+    for (int i = 0; i < n_frames; ++i) src[(size_t)i] = i;
+    HIPCHK(hipMalloc(&s.d_x, (size_t)n_frames * D * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_ll, (size_t)n_frames * W * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_src, (size_t)n_frames * sizeof(int)));
+    HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.d_src, src.data(), (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice));
+    rc = launch_mlp(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, 0, out_mode, layer, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, s.d_ll, (size_t)n_frames * W * sizeof(float), hipMemcpyDeviceToHost));
+    return JD_OK;
+}
+static int mlp_args(const jd_am *a, const float *frames, int32_t n_frames, const float *out, const char *who)
+{
+    if (!a || !out || n_frames < 0 || (n_frames > 0 && !frames)) return jd_fail(JD_EINVAL, "%s: bad argument", who);
+    if (!a->mlp) return jd_fail(JD_ESTATE, "%s: these models hold no network (jd_am_create_mlp / jd_am_load_mlp make the ones that do)", who);
+    return JD_OK;
+}
+extern "C" int jd_am_mlp_forward(const jd_am *a, int32_t device, const float *frames, int32_t n_frames, float *logpost)
+{
+    const int rc = mlp_args(a, frames, n_frames, logpost, "jd_am_mlp_forward");
+    return rc ? rc : mlp_on_device(a, device, frames, n_frames, JD_MLP_OUT_LOGPOST, 0, logpost);
+}
+extern "C" int jd_am_mlp_forward_host(const jd_am *a, const float *frames, int32_t n_frames, float *logpost)
+{
+    const int rc = mlp_args(a, frames, n_frames, logpost, "jd_am_mlp_forward_host");
+    if (rc) return rc;
+    const JdMlpHostMath math;
+    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math);
+    return JD_OK;
+}
+extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t on_device, const float *frames, int32_t n_frames, int32_t layer,
+                                        float *out)
+{
+    const int rc = mlp_args(a, frames, n_frames, out, "jd_debug_mlp_activations");
+    if (rc) return rc;
+    if (layer < 0 || layer >= a->mlp_desc.n_layers)
+        return jd_fail(JD_EINVAL, "jd_debug_mlp_activations: layer %d outside [0, %d)", layer, a->mlp_desc.n_layers);
+    if (on_device) return mlp_on_device(a, device, frames, n_frames, JD_MLP_OUT_LAYER, layer, out);
+    const JdMlpHostMath math;
+    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math);
+    return JD_OK;
+}
+
+// launch_gmm's MLP branch timed with events: warmup launches, then ms[iters], one launch each on n_frames rows (frames [n_frames][in_dim])
+extern "C" int jd_debug_mlp_time(const jd_am *a, int32_t device, const float *frames, int32_t n_frames, int32_t max_blocks, int32_t warmup,
+                                 int32_t iters, float *ms)
+{
+    int rc = mlp_args(a, frames, n_frames, ms, "jd_debug_mlp_time");
+    if (rc) return rc;
+    if (n_frames < 1 || warmup < 0 || iters < 1 || max_blocks < 0) return jd_fail(JD_EINVAL, "jd_debug_mlp_time: bad argument");
+    rc = check_device(device);
+    if (rc) return rc;
+    ScoreBufs s;
+    rc = upload_am_gmm(a, s.b);
+    if (rc) return rc;
+    std::vector<int> src((size_t)n_frames);
+    for (int i = 0; i < n_frames; ++i) src[(size_t)i] = i;
+    HIPCHK(hipMalloc(&s.d_x, (size_t)n_frames * a->D * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_ll, (size_t)n_frames * a->n_gmm * sizeof(float)));
+    HIPCHK(hipMalloc(&s.d_src, (size_t)n_frames * sizeof(int)));
+    HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * a->D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.d_src, src.data(), (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return jd_fail(JD_EHIP, "jd_debug_mlp_time: hipEventCreate"); }
+    for (int i = 0; i < warmup + iters && rc == JD_OK; ++i) {
+        bool ok = hipEventRecord(e0, 0) == hipSuccess;
+        rc = launch_gmm(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, max_blocks);
+        float t = 0.0f;
+        ok = ok && rc == JD_OK && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
+        if (rc == JD_OK && !ok) rc = jd_fail(JD_EHIP, "jd_debug_mlp_time: timing a launch failed");
+        if (i >= warmup) ms[i - warmup] = t;
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return rc;
 }

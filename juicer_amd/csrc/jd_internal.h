@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "juicer_amd.h"
+#include "jd_mlp.h"             // neural acoustic models: the network as plain data, its packing, the host twin
 
 #define JD_MAXN 8          // max HMM states (incl. entry/exit) the search kernel handles
 
@@ -65,6 +66,12 @@ struct jd_am {
     // the feature vector holds one log posterior per model, output = x[model] - log prior (:481-512)
     bool hybrid = false;
     std::vector<float> log_prior;                 // [n_hmm]
+    // neural acoustic models (jd_am_create_mlp, jd_mlp.h): hybrid models whose log posteriors the device computes from feature
+    // vectors of D = in_dim values with this network (mlp_w / mlp_b as given, mlp_wp / mlp_bp packed for jd_mlp_kernel)
+    bool mlp = false;
+    JdMlpDesc mlp_desc;
+    int32_t mlp_states_per_model = 0;
+    std::vector<float> mlp_prior, mlp_w, mlp_b, mlp_wp, mlp_bp;
     // HMM names (HTKModels::getHMMName, for phone output): the MMF's ~h names / JMBI's JMHM names; empty when the models
     // were built from arrays
     std::vector<std::string> hmm_name;            // [n_hmm] or empty

@@ -1,0 +1,189 @@
+// jd_mlp_kernel.h - the forward pass of a neural acoustic model on the device (included by jd_device.hip behind jd_gmm.h; gfx950 only):
+// jd_mlp_kernel takes a tile of JD_MLP_ROWS = 16 rows of a likelihood table through ALL layers of the network - linear layers on
+// v_mfma_f32_16x16x4_f32, activations, log-softmax, minus the log priors - and writes only its rows of the table.  The numerics are
+// jd_mlp_forward_row's (jd_mlp.h), bit for bit.
+//
+// Fused because launch_gmm has no memory of its own: it is called with one shared AmDevBuf on several streams at once, and a layer's
+// activations in global memory would be shared by the launches in flight.  They live in LDS: two buffers [16][stride] that the
+// layers fill in turn, stride = the widest padded layer + 4 floats.
+//
+// A workgroup is four waves.  A wave takes PAIRS of n tiles (16 outputs each) of a layer: two independent accumulators keep the
+// MFMA's issue rate (32 cycles issue, 40 dependent), and both share the A operand.  Per k group of 16 inputs a lane reads 16 bytes of
+// activations from LDS (jd_mlp_act_pos: its four k-steps side by side) and 16 bytes of each tile's packed weights from memory
+// (jd_mlp_w_index: 1 KB contiguous per wave), two k groups ahead of their use, then issues four MFMAs per tile; C-in of the first is
+// the bias.  K is never split and a chain never reordered: the result is the k-ascending fmaf chain whatever the tile or the batch.
+// Padded inputs are -0 in the activations and +0 in the weights (a padded step leaves every c as it is), padded outputs are not stored.
+//
+// The logits of the last layer land in LDS; lane r of the first wave runs row r's logAdd chain (serial by definition: no tree), and
+// all threads write (z - logZ) - log_prior, coalesced.  A row with row_src < 0 is written as 0.0f (as jd_hybrid_kernel does); a tile
+// whose rows are all unused does no arithmetic.  The grid strides over the row tiles (launch_gmm's max_blocks).
+#pragma once
+
+typedef float jd_mlp_f4 __attribute__((ext_vector_type(4)));
+
+// glibc's expf with its special cases around jd_expf_impl (e_expf.c: NaN, +-inf, overflow above 0x1.62e42ep6, zero below -0x1.9fe368p6)
+__host__ __device__ __forceinline__ float jd_mlp_expf(float x, const unsigned long long *tab)
+{
+    if (!(x <= 0x1.62e42ep6f)) return x > 0.0f ? __builtin_inff() : x + x;
+    if (x < -0x1.9fe368p6f) return 0.0f;
+    return jd_expf_impl(x, tab);
+}
+// the policy of jd_mlp_forward_row on the host: the replicas the kernel runs
+struct JdMlpHostMath {
+    JdLogTab tab[129];
+    JdMlpHostMath() { jd_fill_logtab(tab); }
+    float exp(float x) const { return jd_mlp_expf(x, jd_exp2f_tab_host); }
+    float log_add(float a, float c) const { return jd_log_add_impl(a, c, tab, jd_exp2f_tab_host, jd_log_tab_host); }
+};
+
+#define JD_MLP_OUT_LL 0             // out [n_rows][n_phones]: (z - logZ) - log_prior; 0.0f for unused rows
+#define JD_MLP_OUT_LOGPOST 1        // z - logZ
+#define JD_MLP_OUT_LAYER 2          // out [n_rows][width[layer]]: the activations behind `layer` (raw logits for the last)
+
+__device__ __forceinline__ float jd_mlp_activate(float y, int act)
+{
+    if (act == JD_ACT_RELU) return y > 0.0f ? y : 0.0f;
+    if (act == JD_ACT_SIGMOID) return 1.0f / (1.0f + jd_mlp_expf(-y, jd_exp2f_tab));
+    return y;
+}
+
+// an accumulator tile (column lane & 15, rows 4 (lane >> 4) + reg) into the next layer's operand / the logits
+__device__ __forceinline__ void jd_mlp_store_tile(const jd_mlp_f4 acc, int nt, int N, int act, bool last, float *dst, int S, int lane)
+{
+    const int j = nt * JD_MLP_NT + (lane & 15), q = lane >> 4;
+    const int col = last ? j : jd_mlp_act_pos(j);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const float v = acc[reg];
+        if (last) { if (j < N) dst[(4 * q + reg) * S + col] = v; }
+        else dst[(4 * q + reg) * S + col] = (j < N) ? jd_mlp_activate(v, act) : -0.0f;
+    }
+}
+
+// The chains of one n tile (TWO: of a pair) over a layer's KG k groups: c = fma(a[k], b[k], c), k ascending.  ap: the lane's
+// activations (16 bytes a k group, 64 bytes apart), w0 / w1: its packed weights (16 bytes a k group, 1 KB apart).  The operands
+// of the next JD_MLP_CH k groups are requested before the current ones are multiplied, so that a wave waits for memory once a layer
+// and not once a k group; a request behind the last k group repeats the last one (in bounds) and is not used.
+#define JD_MLP_CH 2
+template <bool TWO>
+__device__ __forceinline__ void jd_mlp_chain(const jd_mlp_f4 *__restrict__ ap, const jd_mlp_f4 *__restrict__ w0, const jd_mlp_f4 *__restrict__ w1,
+                                             int KG, jd_mlp_f4 &c0, jd_mlp_f4 &c1)
+{
+    jd_mlp_f4 a[JD_MLP_CH], b0[JD_MLP_CH], b1[JD_MLP_CH], an[JD_MLP_CH], b0n[JD_MLP_CH], b1n[JD_MLP_CH];
+#pragma unroll
+    for (int i = 0; i < JD_MLP_CH; ++i) {
+        const int k = min(i, KG - 1);
+        a[i] = ap[k * 4]; b0[i] = w0[k * 64];
+        if (TWO) b1[i] = w1[k * 64];
+    }
+    for (int kg0 = 0; kg0 < KG; kg0 += JD_MLP_CH) {
+#pragma unroll
+        for (int i = 0; i < JD_MLP_CH; ++i) {
+            const int k = min(kg0 + JD_MLP_CH + i, KG - 1);
+            an[i] = ap[k * 4]; b0n[i] = w0[k * 64];
+            if (TWO) b1n[i] = w1[k * 64];
+        }
+#pragma unroll
+        for (int i = 0; i < JD_MLP_CH; ++i) {
+            if (kg0 + i < KG) {                                        // (wave-uniform)
+                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b0[i].x, c0, 0, 0, 0);
+                if (TWO) c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b1[i].x, c1, 0, 0, 0);
+                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b0[i].y, c0, 0, 0, 0);
+                if (TWO) c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b1[i].y, c1, 0, 0, 0);
+                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b0[i].z, c0, 0, 0, 0);
+                if (TWO) c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b1[i].z, c1, 0, 0, 0);
+                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b0[i].w, c0, 0, 0, 0);
+                if (TWO) c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b1[i].w, c1, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < JD_MLP_CH; ++i) { a[i] = an[i]; b0[i] = b0n[i]; if (TWO) b1[i] = b1n[i]; }
+    }
+}
+
+__global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
+                                                     const float *__restrict__ wp, const float *__restrict__ bp,
+                                                     const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
+                                                     const JdMlpDev m, float *__restrict__ out, int out_mode, int layer)
+{
+    extern __shared__ __align__(16) char smem[];
+    const int S = m.stride;
+    float *buf0 = (float *)smem, *buf1 = buf0 + JD_MLP_ROWS * S;      // [16][S] each
+    int *ssrc = (int *)(buf1 + JD_MLP_ROWS * S);                       // [16] the tile's row_src (-1 behind n_rows)
+    float *slz = (float *)(ssrc + JD_MLP_ROWS);                        // [16] logZ
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int P = m.width[m.n_layers - 1];
+    const int n_rt = (n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
+    for (int rt = blockIdx.x; rt < n_rt; rt += gridDim.x) {
+        const int r0 = rt * JD_MLP_ROWS;
+        __syncthreads();                                               // the previous tile's readers are done
+        if (tid < JD_MLP_ROWS) ssrc[tid] = (r0 + tid < n_rows) ? row_src[r0 + tid] : -1;
+        __syncthreads();
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < JD_MLP_ROWS; ++r) any |= ssrc[r] >= 0;
+        if (!any) {                                                    // (workgroup-uniform)
+            if (out_mode == JD_MLP_OUT_LL)
+                for (int e = tid; e < JD_MLP_ROWS * P; e += 256) {
+                    const int r = e / P;
+                    if (r0 + r < n_rows) out[(size_t)(r0 + r) * P + (e - r * P)] = 0.0f;
+                }
+            continue;
+        }
+        {   // the input rows, padded with -0 to the k group
+            const int K = m.in_dim, Kp = (K + 15) & ~15;
+            for (int e = tid; e < JD_MLP_ROWS * Kp; e += 256) {
+                const int r = e / Kp, k = e - r * Kp;
+                const int src = ssrc[r];
+                buf0[r * S + jd_mlp_act_pos(k)] = (k < K) ? (src >= 0 ? feats[(size_t)src * K + k] : 0.0f) : -0.0f;
+            }
+        }
+        __syncthreads();
+        float *in = buf0, *nx = buf1;
+        bool done = false;
+        for (int l = 0; l < m.n_layers && !done; ++l) {
+            const int K = l ? m.width[l - 1] : m.in_dim, KG = (K + 15) >> 4, N = m.width[l], n_nt = (N + 15) >> 4;
+            const bool last = l == m.n_layers - 1;
+            const int act = m.act[l];
+            const float *B = bp + m.b_off[l];
+            const jd_mlp_f4 *W = (const jd_mlp_f4 *)(wp + m.w_off[l]) + lane;          // (n tile, k group): 64 lanes x 16 bytes
+            const jd_mlp_f4 *ap = (const jd_mlp_f4 *)(in + (lane & 15) * S + 4 * (lane >> 4));
+            for (int nt0 = wid * 2; nt0 < n_nt; nt0 += 8) {                            // (wave-uniform)
+                const bool two = nt0 + 1 < n_nt;
+                const float bias0 = B[nt0 * JD_MLP_NT + (lane & 15)];
+                const float bias1 = two ? B[(nt0 + 1) * JD_MLP_NT + (lane & 15)] : 0.0f;
+                jd_mlp_f4 c0 = {bias0, bias0, bias0, bias0}, c1 = {bias1, bias1, bias1, bias1};
+                const jd_mlp_f4 *w0 = W + (size_t)nt0 * KG * 64;
+                if (two) jd_mlp_chain<true>(ap, w0, w0 + (size_t)KG * 64, KG, c0, c1);
+                else jd_mlp_chain<false>(ap, w0, w0, KG, c0, c1);
+                jd_mlp_store_tile(c0, nt0, N, act, last, nx, S, lane);
+                if (two) jd_mlp_store_tile(c1, nt0 + 1, N, act, last, nx, S, lane);
+            }
+            __syncthreads();
+            if (out_mode == JD_MLP_OUT_LAYER && l == layer) {
+                for (int e = tid; e < JD_MLP_ROWS * N; e += 256) {
+                    const int r = e / N, j = e - r * N;
+                    if (r0 + r < n_rows) out[(size_t)(r0 + r) * N + j] = nx[r * S + (last ? j : jd_mlp_act_pos(j))];
+                }
+                done = true;
+            }
+            float *t = in; in = nx; nx = t;
+        }
+        if (done) continue;
+        // `in` holds the logits [16][S], plain order
+        if (tid < JD_MLP_ROWS) {
+            float lz = LZ;
+            for (int j = 0; j < P; ++j) lz = jd_log_add(lz, in[tid * S + j], logtab);
+            slz[tid] = lz;
+        }
+        __syncthreads();
+        for (int e = tid; e < JD_MLP_ROWS * P; e += 256) {
+            const int r = e / P, j = e - r * P;
+            if (r0 + r < n_rows) {
+                const float lp = in[r * S + j] - slz[r];
+                out[(size_t)(r0 + r) * P + j] = (ssrc[r] < 0) ? 0.0f : (out_mode == JD_MLP_OUT_LL ? lp - log_prior[j] : lp);
+            }
+        }
+    }
+}
