@@ -59,10 +59,8 @@
 #include "jd_push.h"            // the streaming interface: a stream's record, argument checks, PARTIAL_DECODING's schedule, packing, k_partial_many's layout
 #include "jd_best.h"            // the current best hypothesis of live streams: k_best_many's layout, what a reply means, the word projection
 #include "jd_final.h"           // the end-of-utterance view of live streams: k_final_many's layout, what a reply means, the word projection
+#include "jd_score_plan.h"      // a scoring launch: the kernel, its tiles, grid and LDS (launch_gmm); the scoring kernels' tile constants (GMM_*)
 
-#define GMM_ROWS 64             // stream-frames per GMM tile (one per lane)
-#define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
-#define GMM_GT_SMALL 16         // ... of a launch with few rows (jd_gmm_kernel39 only)
 #define HIST_MAX_BINS 2048
 
 struct __align__(16) Tok { float score, ac, lm; int path; };

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void jd_gmm_kernel(const float *__restrict__ f
 // through the scalar cache.  logAdd (HTKFlatModels.cpp:266-293) evaluates log(1.0 + e), e in
 // (0, 1], in double as the libm the reference links does: a table value, and where its last bits could
 // move the float result the replica of glibc's log (jd_log_add_gate / jd_log_libm_impl above).
-#define GMM_ROWS2 128
+// (GMM_ROWS2 = 128, like the other tile constants: jd_score_plan.h)
 typedef float jd_f2 __attribute__((ext_vector_type(2)));
 // One logAdd step for the two frames of a lane, straight-line (no branch: some lane of a wave always takes the long path) and
 // written pairwise so that the two dependent chains interleave.  etab is the LDS copy of jd_exp2f_tab, tab the LDS copy of
@@ -560,8 +560,7 @@ __global__ __launch_bounds__(256, 4) void jd_gmm_fast39(const float *__restrict_
 //               for every state and block of mixtures (the loops are then workgroup-uniform: bound by M, not n_mix) - 32 loads a lane
 //               against 512 packed FMAs at 8 mixtures.
 //   output      straight to the table (two dwords per lane and state): the LDS is the slab's, there is no room for a tile to transpose.
-#define GMM_FAST_DC 8
-#define GMM_FAST_DS 64
+// (GMM_FAST_DC = 8, GMM_FAST_DS = 64: jd_score_plan.h)
 #define GMM_FAST_MB 8               // (16: the compiler keeps scalar registers in vector lanes across the chunk loop)
 template <int GT>
 __global__ __launch_bounds__(256, 4) void jd_gmm_fast(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,

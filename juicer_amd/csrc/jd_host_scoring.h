@@ -1,6 +1,7 @@
 // jd_host_scoring.h - the host side of the companion scoring kernels (included by jd_device.hip): the model parameters on the device,
-// launch_gmm (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast, jd_dec_set_scoring's option; the generic and the hybrid kernel;
-// jd_mlp_kernel for the models of jd_am_create_mlp), jd_am_score_frames, jd_am_mlp_forward.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
+// launch_gmm - the launch of what jd_score_plan.h plans: which kernel (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast,
+// jd_dec_set_scoring's option; the generic and the hybrid kernel; jd_mlp_kernel for the models of jd_am_create_mlp), its tiles, grid and
+// LDS are decided there, on plain data, and tested on the CPU - jd_am_score_frames, jd_am_mlp_forward.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
 #pragma once
 
 // hybrid scoring (HTKFlatModels.cpp:190-222): output = x[model] - log prior; rows as in the GMM kernels
@@ -61,8 +62,7 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
     return JD_OK;
 }
 
-// the parameters of the scoring option (jd_gmm.h: jd_gmm_fast39, jd_gmm_fast): par is [gm][jd_fast_dp(D)][2], zero behind dimension D
-static int jd_fast_dp(int D) { return D == 39 ? 39 : (D + GMM_FAST_DC - 1) / GMM_FAST_DC * GMM_FAST_DC; }
+// the parameters of the scoring option (jd_gmm.h: jd_gmm_fast39, jd_gmm_fast): par is [gm][jd_fast_dp(D)][2], zero behind dimension D (jd_score_plan.h)
 static void prep_par_fast(const float *mean, const float *ivar, size_t gm, size_t D, std::vector<float> &par)
 {
     const size_t DP = (size_t)jd_fast_dp((int)D);
@@ -97,26 +97,26 @@ static void free_am_gmm(AmDevBuf &b)
     b = AmDevBuf();
 }
 
-// dynamic LDS of the kernels of 128-row tiles
-static size_t gmm39_lds() { return 130 * sizeof(JdLogTab) + 32 * sizeof(unsigned long long) + (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float); }
-static size_t gmm_fast39_lds() { return (size_t)GMM_ROWS2 * std::max(39, GMM_GT + 1) * sizeof(float); }
-static size_t gmm_fast_lds() { return (size_t)GMM_ROWS2 * (GMM_FAST_DS + 1) * sizeof(float); }
+static_assert(sizeof(JdLogTab) == SCORE_LOGTAB_BYTES, "gmm39_lds (jd_score_plan.h) counts jd_gmm_kernel39's copy of the table");
 
 // which kernel a launch_gmm call ran and on what grid (jd_score_kernel of juicer_amd.h; 0 / 0: nothing was launched)
 struct GmmLaunch { int kernel = JD_KERNEL_NONE; unsigned grid = 0; };
 
-// jd_mlp_kernel on rows [0, n_rows): d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
-static int launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
-                      int max_blocks, int out_mode, int layer, GmmLaunch *info)
+// The plan of a scoring launch for these models on this device (jd_score_plan.h): the kernel, its tiles, the grid, the LDS
+static bool am_fast(const AmDevBuf &b) { return b.fast && b.par_fast; }                   // launch_gmm scores with jd_gmm_fast39 / jd_gmm_fast
+static ScorePlan gmm_plan(const jd_am *a, const AmDevBuf &b, int n_rows, int max_blocks = 0, int used_row_tiles = -1, bool has_list = false,
+                          int n_rt_list = 0)
+{
+    return score_plan(ScorePlanIn{a->D, a->n_gmm, a->hybrid, a->mlp, am_fast(b), n_rows, max_blocks, used_row_tiles, has_list, n_rt_list});
+}
+
+// jd_mlp_kernel on rows [0, n_rows), on the plan's grid: d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
+static void launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
+                       unsigned grid, int out_mode, int layer)
 {
     const JdMlpDev m = jd_mlp_dev(a->mlp_desc);
-    const int tiles = (n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
-    const dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
-    hipLaunchKernelGGL(jd_mlp_kernel, grid, dim3(256), jd_mlp_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
+    hipLaunchKernelGGL(jd_mlp_kernel, dim3(grid), dim3(256), jd_mlp_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
                        b.logtab, m, d_out, out_mode, layer);
-    HIPCHK(hipGetLastError());
-    if (info) { info->kernel = JD_KERNEL_MLP; info->grid = grid.x; }
-    return JD_OK;
 }
 
 // max_blocks > 0 bounds the grid (the kernel strides over the tiles): next to the search, a
@@ -127,71 +127,33 @@ static int launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 // used_row_tiles >= 0: the row tiles that are not skipped (else: all of them)
 // rt_base (device, or null) / n_rt_list: score these row tiles (first rows) only - the kernels of 128-row tiles (D = 39; jd_gmm_fast)
 // info (or null): what was launched (jd_debug_score_rows)
+// (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds jd_mlp_kernel's grid)
 static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows,
                       float *d_ll, hipStream_t st, int max_blocks = 0, int skip_unused = 0, int used_row_tiles = -1,
                       const int *rt_base = nullptr, int n_rt_list = 0, GmmLaunch *info = nullptr)
 {
     if (info) *info = GmmLaunch();
-    if (n_rows <= 0) return JD_OK;
-    // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds jd_mlp_kernel's grid)
-    if (a->mlp) return launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, max_blocks, JD_MLP_OUT_LL, 0, info);
-    if (a->hybrid) {
-        const long long n = (long long)n_rows * a->n_gmm;
-        const dim3 grid((unsigned)((n + 255) / 256));
-        hipLaunchKernelGGL(jd_hybrid_kernel, grid, dim3(256), 0, st, d_feats, d_row_src, n_rows, b.log_prior,
-                           a->n_gmm, d_ll);
-        HIPCHK(hipGetLastError());
-        if (info) { info->kernel = JD_KERNEL_HYBRID; info->grid = grid.x; }
-        return JD_OK;
+    const ScorePlan p = gmm_plan(a, b, n_rows, max_blocks, used_row_tiles, rt_base != nullptr, n_rt_list);
+    if (p.verdict == SCORE_PLAN_NOTHING) return JD_OK;
+    if (p.verdict == SCORE_PLAN_LIST) return jd_fail(JD_EINVAL, "launch_gmm: tile lists are the D = 39 kernel's");
+#define GMM_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), p.lds_bytes, st, d_feats, d_row_src, n_rows, __VA_ARGS__)
+#define GMM_ARGS(par) par, b.det, b.n_mix, a->n_gmm, a->max_mix
+    switch (p.kernel) {
+    case JD_KERNEL_MLP: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0); break;
+    case JD_KERNEL_HYBRID: GMM_LAUNCH(jd_hybrid_kernel, b.log_prior, a->n_gmm, d_ll); break;
+    case JD_KERNEL_GMM_FAST39_16: GMM_LAUNCH(jd_gmm_fast39<GMM_GT_SMALL>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM_FAST39_64: GMM_LAUNCH(jd_gmm_fast39<GMM_GT>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM_FAST_16: GMM_LAUNCH(jd_gmm_fast<GMM_GT_SMALL>, GMM_ARGS(b.par_fast), a->D, p.dp, d_ll, skip_unused, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM_FAST_64: GMM_LAUNCH(jd_gmm_fast<GMM_GT>, GMM_ARGS(b.par_fast), a->D, p.dp, d_ll, skip_unused, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM39_16: GMM_LAUNCH(jd_gmm_kernel39<GMM_GT_SMALL>, GMM_ARGS(b.par), d_ll, skip_unused, b.logtab, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM39_64: GMM_LAUNCH(jd_gmm_kernel39<GMM_GT>, GMM_ARGS(b.par), d_ll, skip_unused, b.logtab, rt_base, n_rt_list); break;
+    case JD_KERNEL_GMM_GENERIC: GMM_LAUNCH(jd_gmm_kernel<0>, GMM_ARGS(b.par), a->D, d_ll, skip_unused, b.logtab); break;
+    default: return jd_fail(JD_EINVAL, "launch_gmm: no kernel %d", p.kernel);
     }
-    const bool fast_any = a->D != 39 && b.fast && b.par_fast;           // jd_gmm_fast: the D = 39 kernels' tiles
-    const bool tiles128 = a->D == 39 || fast_any;
-    const int rows_per_tile = tiles128 ? GMM_ROWS2 : GMM_ROWS;
-    if (rt_base && !tiles128) return jd_fail(JD_EINVAL, "launch_gmm: tile lists are the D = 39 kernel's");
-    const long long row_tiles = rt_base ? n_rt_list : (n_rows + rows_per_tile - 1) / rows_per_tile;
-    long long tiles = row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT);
-    // few rows (a streaming push, a tick of the broker): tiles of 16 states, four times as many and a quarter as long
-    const bool small_tiles = tiles128 && (used_row_tiles >= 0 ? (long long)used_row_tiles * ((a->n_gmm + GMM_GT - 1) / GMM_GT) : tiles) < 1024;
-    if (small_tiles) tiles = row_tiles * ((a->n_gmm + GMM_GT_SMALL - 1) / GMM_GT_SMALL);
-    dim3 grid((unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles));
-    int kernel;
-    if (a->D == 39 && b.fast && b.par_fast) {
-        const size_t sm = gmm_fast39_lds();
-        kernel = small_tiles ? JD_KERNEL_GMM_FAST39_16 : JD_KERNEL_GMM_FAST39_64;
-        if (small_tiles)
-            hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
-        else
-            hipLaunchKernelGGL(jd_gmm_fast39<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, rt_base, n_rt_list);
-    } else if (fast_any) {
-        const size_t sm = gmm_fast_lds();
-        const int DP = jd_fast_dp(a->D);
-        kernel = small_tiles ? JD_KERNEL_GMM_FAST_16 : JD_KERNEL_GMM_FAST_64;
-        if (small_tiles)
-            hipLaunchKernelGGL(jd_gmm_fast<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
-        else
-            hipLaunchKernelGGL(jd_gmm_fast<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par_fast, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, a->D, DP, d_ll, skip_unused, rt_base, n_rt_list);
-    } else if (a->D == 39) {
-        const size_t sm = gmm39_lds();
-        kernel = small_tiles ? JD_KERNEL_GMM39_16 : JD_KERNEL_GMM39_64;
-        if (small_tiles)
-            hipLaunchKernelGGL(jd_gmm_kernel39<GMM_GT_SMALL>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, b.logtab, rt_base, n_rt_list);
-        else
-            hipLaunchKernelGGL(jd_gmm_kernel39<GMM_GT>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
-                               b.n_mix, a->n_gmm, a->max_mix, d_ll, skip_unused, b.logtab, rt_base, n_rt_list);
-    } else {
-        const int dp = a->D | 1;
-        const size_t sm = (size_t)(GMM_ROWS * dp + GMM_ROWS * (GMM_GT + 1)) * sizeof(float);
-        kernel = JD_KERNEL_GMM_GENERIC;
-        hipLaunchKernelGGL(jd_gmm_kernel<0>, grid, dim3(256), sm, st, d_feats, d_row_src, n_rows, b.par, b.det,
-                           b.n_mix, a->n_gmm, a->max_mix, a->D, d_ll, skip_unused, b.logtab);
-    }
+#undef GMM_ARGS
+#undef GMM_LAUNCH
     HIPCHK(hipGetLastError());
-    if (info) { info->kernel = kernel; info->grid = grid.x; }
+    if (info) { info->kernel = p.kernel; info->grid = p.grid; }
     return JD_OK;
 }
 
@@ -200,10 +162,15 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 static int gmm_tiles128_occupancy(const jd_am *a, const AmDevBuf &b, int *per_cu)
 {
     *per_cu = 0;
-    if (a->hybrid) return JD_OK;
-    if (a->D == 39 && b.fast && b.par_fast) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_fast39<GMM_GT>, 256, gmm_fast39_lds()));
-    else if (a->D != 39 && b.fast && b.par_fast) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_fast<GMM_GT>, 256, gmm_fast_lds()));
-    else if (a->D == 39) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (const void *)jd_gmm_kernel39<GMM_GT>, 256, gmm39_lds()));
+    const ScoreLarge large = score_plan_large(a->D, a->hybrid, a->mlp, am_fast(b));
+    const void *kernel = nullptr;
+    switch (large.kernel) {
+    case JD_KERNEL_GMM_FAST39_64: kernel = (const void *)jd_gmm_fast39<GMM_GT>; break;
+    case JD_KERNEL_GMM_FAST_64: kernel = (const void *)jd_gmm_fast<GMM_GT>; break;
+    case JD_KERNEL_GMM39_64: kernel = (const void *)jd_gmm_kernel39<GMM_GT>; break;
+    default: return JD_OK;
+    }
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, 256, large.lds_bytes));
     return JD_OK;
 }
 
@@ -236,9 +203,26 @@ struct ScoreBufs {
         if (d_src) (void)hipFree(d_src);
         if (d_list) (void)hipFree(d_list);
     }
+    // frames [n_frames][D] and a row map [n_rows] (row_src; null: the identity) go up, beside room for n_out floats of output
+    int upload_rows(const jd_am *a, const float *frames, int n_frames, const int *row_src, int n_rows, size_t n_out)
+    {
+        const size_t D = (size_t)a->D;
+        std::vector<int> identity;
+        if (!row_src) {
+            identity.resize((size_t)n_rows);
+            std::iota(identity.begin(), identity.end(), 0);
+            row_src = identity.data();
+        }
+        HIPCHK(hipMalloc(&d_x, std::max<size_t>((size_t)n_frames, 1) * D * sizeof(float)));
+        HIPCHK(hipMalloc(&d_ll, n_out * sizeof(float)));
+        HIPCHK(hipMalloc(&d_src, (size_t)n_rows * sizeof(int)));
+        if (n_frames > 0) HIPCHK(hipMemcpy(d_x, frames, (size_t)n_frames * D * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_src, row_src, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+        return JD_OK;
+    }
 };
 
-// One launch_gmm call on buffers of its own (the device is set): frames [n_frames][D] and row_src [n_rows] go up, with the tile list
+// One launch_gmm call on buffers of its own (the device is set): frames [n_frames][D] and row_src [n_rows] (null: the identity) go up, with the tile list
 // rt_base [n_rt] (or null) and - prefilled - the caller's out [(guard_rows + n_rows + guard_rows)][G]; the table is written `guard_rows`
 // rows into the buffer, and the whole buffer comes back.  The arguments are the caller's to check (jd_debug_score_rows does).
 static int score_rows_on_device(const jd_am *a, int mode, const float *frames, int n_frames, const int *row_src, int n_rows, int skip_unused,
@@ -249,13 +233,9 @@ static int score_rows_on_device(const jd_am *a, int mode, const float *frames, i
     int rc = upload_am_gmm(a, s.b);
     if (rc) return rc;
     if (mode == JD_SCORE_FAST) { rc = upload_am_fast(a, s.b); if (rc) return rc; s.b.fast = 1; }
-    const size_t G = (size_t)a->n_gmm, D = (size_t)a->D;
-    const size_t n_x = std::max<size_t>((size_t)n_frames, 1) * D, n_out = ((size_t)n_rows + 2 * (size_t)guard_rows) * G;
-    HIPCHK(hipMalloc(&s.d_x, n_x * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_ll, n_out * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_src, (size_t)n_rows * sizeof(int)));
-    if (n_frames > 0) HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * D * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s.d_src, row_src, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+    const size_t G = (size_t)a->n_gmm, n_out = ((size_t)n_rows + 2 * (size_t)guard_rows) * G;
+    rc = s.upload_rows(a, frames, n_frames, row_src, n_rows, n_out);
+    if (rc) return rc;
     if (prefilled) HIPCHK(hipMemcpy(s.d_ll, out, n_out * sizeof(float), hipMemcpyHostToDevice));
     if (rt_base) {
         HIPCHK(hipMalloc(&s.d_list, (size_t)n_rt * sizeof(int)));
@@ -289,13 +269,8 @@ static int score_frames_mode(const jd_am *a, int32_t device, int32_t mode, const
     int rc = check_device(device);
     if (rc) return rc;
     if (n_frames == 0) return JD_OK;
-    std::vector<int> src((size_t)n_frames);
-    for (int i = 0; i < n_frames; ++i) src[i] = i;
-    return score_rows_on_device(a, mode, frames, n_frames, src.data(), n_frames, 0, 0, -1, nullptr, 0, 0, false, out, nullptr);
+    return score_rows_on_device(a, mode, frames, n_frames, nullptr, n_frames, 0, 0, -1, nullptr, 0, 0, false, out, nullptr);
 }
-
-// The scoring tile's rows of the kernel launch_gmm takes for these models and this mode (0: the hybrid kernel has none)
-static int score_tile_rows(const jd_am *a, int mode) { return a->hybrid ? 0 : (a->D == 39 || mode == JD_SCORE_FAST) ? GMM_ROWS2 : GMM_ROWS; }
 
 // What the kernels take for granted of a launch's rows (host arrays): every row_src entry in [-1, n_frames); a tile list's entries in
 // [0, n_rows) and their tiles apart; with skip_unused, the valid rows of every scored tile a prefix of it (jd_gmm.h: jd_gmm_kernel -
@@ -305,7 +280,7 @@ static int check_score_rows(const jd_am *a, int mode, int n_frames, const int *r
     for (int r = 0; r < n_rows; ++r)
         if (row_src[r] < -1 || row_src[r] >= n_frames)
             return jd_fail(JD_EINVAL, "jd_debug_score_rows: row_src[%d] = %d outside [-1, %d)", r, row_src[r], n_frames);
-    const int h = score_tile_rows(a, mode);
+    const int h = score_plan_tile_rows(a->D, a->hybrid, a->mlp, mode == JD_SCORE_FAST);   // (0: no tiles as far as skip_unused and lists go)
     if (h == 0) {                                                      // (launch_gmm scores every row of a hybrid model and would ignore the list)
         if (rt_base) return jd_fail(JD_EINVAL, "jd_debug_score_rows: tile lists are not for hybrid models (jd_hybrid_kernel has no tiles)");
         return JD_OK;
@@ -368,16 +343,11 @@ static int mlp_on_device(const jd_am *a, int device, const float *frames, int n_
     ScoreBufs s;
     rc = upload_am_gmm(a, s.b);
     if (rc) return rc;
-    const size_t D = (size_t)a->D, W = (size_t)(out_mode == JD_MLP_OUT_LAYER ? a->mlp_desc.width[layer] : a->n_gmm);
-    std::vector<int> src((size_t)n_frames);
-    for (int i = 0; i < n_frames; ++i) src[(size_t)i] = i;
-    HIPCHK(hipMalloc(&s.d_x, (size_t)n_frames * D * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_ll, (size_t)n_frames * W * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_src, (size_t)n_frames * sizeof(int)));
-    HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * D * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s.d_src, src.data(), (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice));
-    rc = launch_mlp(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, 0, out_mode, layer, nullptr);
+    const size_t W = (size_t)(out_mode == JD_MLP_OUT_LAYER ? a->mlp_desc.width[layer] : a->n_gmm);
+    rc = s.upload_rows(a, frames, n_frames, nullptr, n_frames, (size_t)n_frames * W);
     if (rc) return rc;
+    launch_mlp(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, gmm_plan(a, s.b, n_frames).grid, out_mode, layer);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, s.d_ll, (size_t)n_frames * W * sizeof(float), hipMemcpyDeviceToHost));
     return JD_OK;
@@ -426,13 +396,8 @@ extern "C" int jd_debug_mlp_time(const jd_am *a, int32_t device, const float *fr
     ScoreBufs s;
     rc = upload_am_gmm(a, s.b);
     if (rc) return rc;
-    std::vector<int> src((size_t)n_frames);
-    for (int i = 0; i < n_frames; ++i) src[(size_t)i] = i;
-    HIPCHK(hipMalloc(&s.d_x, (size_t)n_frames * a->D * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_ll, (size_t)n_frames * a->n_gmm * sizeof(float)));
-    HIPCHK(hipMalloc(&s.d_src, (size_t)n_frames * sizeof(int)));
-    HIPCHK(hipMemcpy(s.d_x, frames, (size_t)n_frames * a->D * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s.d_src, src.data(), (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice));
+    rc = s.upload_rows(a, frames, n_frames, nullptr, n_frames, (size_t)n_frames * a->n_gmm);
+    if (rc) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return jd_fail(JD_EHIP, "jd_debug_mlp_time: hipEventCreate"); }

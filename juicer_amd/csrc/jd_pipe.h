@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "jd_score_plan.h"      // SCORE_SMALL_BELOW: below how many tiles a scoring launch takes the small ones (pipe_piece_bounds)
+
 enum {
     PIPE_CHUNK = 128,                    // frames per command: what a slot runs before it looks at its mailbox again (jd_dec_quiesce waits that long)
     PIPE_PIECE_ROWS0 = 6144,             // rows per scoring launch where nothing is planned (JD_PIPE_DECOUPLE=0)
@@ -135,14 +137,15 @@ static inline size_t pipe_size(PipeState &P, const PipeSizeIn &in)
     return (size_t)P.K * (size_t)P.max_batch;
 }
 // Rows per scoring launch: the bounds plan_piece_rows (jd_plan.h) chooses between - 4096 to 8192 rows (DESIGN.md 3.4's sweep: shorter
-// pieces pay per launch, longer ones hold what waits behind them) - and the state groups of a row tile.  A launch of fewer than 1024
-// tiles is one of small (16-state) tiles (launch_gmm); where the longest piece is not, no piece is to fall below it.
+// pieces pay per launch, longer ones hold what waits behind them) - and the state groups of a row tile.  A launch of fewer than
+// SCORE_SMALL_BELOW tiles is one of small (group_small-state) tiles (jd_score_plan.h: score_plan); where the longest piece is not,
+// no piece is to fall below it.  (group, group_small, tile: the caller passes the same header's GMM_GT, GMM_GT_SMALL, GMM_ROWS2)
 struct PipePieceBounds { int lo, hi, groups; };
 static inline PipePieceBounds pipe_piece_bounds(int n_gmm, int group, int group_small, int tile)
 {
     PipePieceBounds b{4096, 8192, (n_gmm + group - 1) / group};
-    if ((long long)(b.hi / tile) * b.groups < 1024) b.groups = (n_gmm + group_small - 1) / group_small;
-    else b.lo = std::max(b.lo, (1024 + b.groups - 1) / b.groups * tile);
+    if ((long long)(b.hi / tile) * b.groups < SCORE_SMALL_BELOW) b.groups = (n_gmm + group_small - 1) / group_small;
+    else b.lo = std::max(b.lo, (SCORE_SMALL_BELOW + b.groups - 1) / b.groups * tile);
     return b;
 }
 // ... what was planned (0: nothing - the kernels of other tiles, JD_PIPE_DECOUPLE=0), unless JD_PIPE_PIECE says otherwise: a piece

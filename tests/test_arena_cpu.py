@@ -104,7 +104,7 @@ def test_arena_sizes_are_the_builds(golden):
                  "TOT_N == %d && MAXW == %d && HIST_MAX_BINS == %d && SW == %d" % (z["tot_n"], z["maxw"], z["hist_bins"], z["sw"])):
         assert text in src, text
     assert z["sw"] == define("jd_search.h", "SW") and z["maxw"] == 64 * z["sw"] and z["hist_bins"] == define("jd_device.hip", "HIST_MAX_BINS")
-    assert golden["wave_defaults"]["tile"] == define("jd_gmm.h", "GMM_ROWS2")
+    assert golden["wave_defaults"]["tile"] == define("jd_score_plan.h", "GMM_ROWS2")
     assert all("tile" not in c["in"] for c in golden["wave_cases"])
 
 

@@ -79,7 +79,7 @@ def test_res_plan_constants_are_the_builds(plans):
 
     sw = define("jd_search.h", "SW")
     assert consts == {"SW": sw, "WG_PER_CU": define("jd_search.h", "WG_PER_CU"), "SLOT_WG_PER_CU": define("jd_slot.h", "SLOT_WPE") * 4 // sw,
-                      "GMM_ROWS2": define("jd_gmm.h", "GMM_ROWS2"), "RES_RING_W": define("jd_host_resident.h", "RES_RING_W")}
+                      "GMM_ROWS2": define("jd_score_plan.h", "GMM_ROWS2"), "RES_RING_W": define("jd_host_resident.h", "RES_RING_W")}
 
 
 def test_res_plan_cases_cover_what_they_must(plans):
