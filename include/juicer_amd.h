@@ -280,6 +280,30 @@ int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t on_device, 
 int jd_debug_mlp_time(const jd_am *a, int32_t device, const float *frames, int32_t n_frames, int32_t max_blocks, int32_t warmup,
                       int32_t iters, float *ms);
 
+/* TIED hybrid and neural models: what a large-vocabulary hybrid ANN / HMM recogniser has - a context-dependent HMM set of any
+ * topology whose emitting states are tied to a few thousand states (senones), and one network output per tied state.
+ * `topology` is any set of GMM models (jd_am_load_mmf, jd_am_load_jmbi, jd_am_create_htk / _flat); it is only read during the call.
+ * The new models take its HMMs, their state tying (which tied state an emitting state scores with), the transition matrices with
+ * their tee models, the HMM names, jd_am_num_gmms and jd_am_max_states - and none of its Gaussians (jd_am_max_mix is 1, and
+ * jd_am_get_flat fills det alone: there are no means or variances, placeholders neither).  priors: one per tied state
+ * (jd_am_num_gmms(topology) values); an emitting state tied to g scores logpost[g] - log(priors[g]).  They are hybrid models: what
+ * hybrid models refuse (JD_FLOW_RESIDENT, JD_SCORE_FAST, jd_am_save_jmbi, tile lists) these refuse.  JD_EINVAL, naming the argument:
+ * a NULL argument, a `topology` that is itself hybrid or neural, a prior that is not positive.
+ * jd_am_create_hybrid_tied: the caller pushes vectors of jd_am_num_gmms log posteriors (jd_am_vec_size = jd_am_num_gmms).
+ * jd_am_create_mlp_tied: jd_am_create_mlp's arguments for the network; the caller pushes vectors of in_dim features.  in_dim and
+ * the hidden widths 1 .. 1024, the LAST width = jd_am_num_gmms(topology), 1 .. 16384 (JD_MLP_MAX_OUT).  jd_am_mlp_info,
+ * jd_am_mlp_forward(_host), jd_debug_mlp_activations, jd_debug_mlp_time, jd_am_score_frames and jd_debug_score_rows serve them.
+ * Numerics: layers as above.  logZ is NOT one serial chain over thousands of outputs but (csrc/jd_mlp.h) 128 interleaved partial
+ * chains - p[c] = the logAdd chain from JD_LOG_ZERO over z[c], z[c + 128], ... for c < min(128, P) - and the logAdd chain over
+ * p[0], p[1], ...; a constant of the numerics, whatever the rows, the launch or the device.  Host twin and device agree bit for bit.
+ * jd_am_save_mlp on such models writes JMLP version 2 - the same layout with states_per_model = 0 and n_phones = the number of
+ * outputs; no topology - which jd_am_load_mlp_tied reads beside a topology (JD_EINVAL when the outputs are not its tied states).
+ * Each loader answers the other's version with JD_EFORMAT and the name of the loader that reads it. */
+int jd_am_create_hybrid_tied(jd_am **out, const jd_am *topology, const float *priors);
+int jd_am_create_mlp_tied(jd_am **out, const jd_am *topology, const float *priors, int32_t in_dim, int32_t n_layers,
+                          const int32_t *width, const int32_t *act, const float *const *weight, const float *const *bias);
+int jd_am_load_mlp_tied(jd_am **out, const jd_am *topology, const char *path);
+
 /* Juicer's binary model cache "<mmf>.bin" (JMBI), preferred by juicer.cpp:778-784:
  * HTKModels::readBinary (HTKModels.cpp:1110-1233) + HTKFlatModels::init.  The derived values in
  * the file (sumLogVarPlusNObsLog2Pi, logCompWeights, transition logProbs) are used as stored. */
@@ -853,7 +877,8 @@ int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const floa
  * tiles that overlap; a tile list for hybrid models (launch_gmm would ignore it); and, launch_gmm's own refusal, a tile list for exact
  * scoring of D != 39.  Tile rows: 128 at D = 39
  * and with JD_SCORE_FAST, 64 for exact scoring of any other D, none for hybrid models (which ignore skip_unused; those with a network,
- * jd_am_create_mlp, included: jd_mlp_kernel's tiles of 16 rows are its own affair, and rows with row_src = -1 are written as 0.0f).
+ * jd_am_create_mlp and jd_am_create_mlp_tied, included: the 16-row tiles of jd_mlp_kernel / jd_mlp_tied_kernel are their own affair,
+ * and rows with row_src = -1 are written as 0.0f).
  * tests/test_gpu_score_rows.py holds every cell of the buffer to tests/score_rows_cases.py. */
 typedef enum jd_score_kernel {
     JD_KERNEL_NONE = 0,            /* nothing was launched                                  */
@@ -865,7 +890,8 @@ typedef enum jd_score_kernel {
     JD_KERNEL_GMM_FAST_16 = 6,     /* jd_gmm_fast<16>                                       */
     JD_KERNEL_GMM_FAST_64 = 7,     /* jd_gmm_fast<64>                                       */
     JD_KERNEL_HYBRID = 8,          /* jd_hybrid_kernel                                      */
-    JD_KERNEL_MLP = 9              /* jd_mlp_kernel: jd_am_create_mlp's models, 16-row tiles */
+    JD_KERNEL_MLP = 9,             /* jd_mlp_kernel: jd_am_create_mlp's models, 16-row tiles */
+    JD_KERNEL_MLP_TIED = 10        /* jd_mlp_tied_kernel: jd_am_create_mlp_tied's, 16-row tiles */
 } jd_score_kernel;
 int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
                         int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,

@@ -147,6 +147,7 @@ EXPORTS = [
     "jd_streams_final", "jd_stream_final_words", "jd_stream_final_models", "jd_dec_final_stats", "jd_streams_trace_models",
     "jd_am_create_mlp", "jd_am_mlp_info", "jd_am_save_mlp", "jd_am_load_mlp", "jd_am_mlp_forward", "jd_am_mlp_forward_host",
     "jd_debug_mlp_activations", "jd_debug_mlp_time",
+    "jd_am_create_hybrid_tied", "jd_am_create_mlp_tied", "jd_am_load_mlp_tied",
 ]
 
 _lib = None
@@ -516,6 +517,43 @@ class Models:
         return cls(h)
 
     @classmethod
+    def from_hybrid_tied(cls, topology: "Models", priors):
+        """Tied hybrid models (jd_am_create_hybrid_tied): the HMMs, state tying, transitions and names of `topology` - any GMM
+        models - with one log posterior per TIED STATE as the feature vector; priors: one per tied state (topology.n_gmms)."""
+        pr = _f32(priors)
+        assert pr.shape == (topology.n_gmms,)
+        h = C.c_void_p()
+        _check(lib().jd_am_create_hybrid_tied(C.byref(h), topology.h, _p(pr, C.c_float)))
+        return cls(h)
+
+    @classmethod
+    def from_mlp_tied(cls, topology: "Models", priors, layers):
+        """Tied neural models (jd_am_create_mlp_tied): from_hybrid_tied's models with the network that yields the tied states' log
+        posteriors; layers as from_mlp's, the last of topology.n_gmms outputs (up to 16384)."""
+        pr = _f32(priors)
+        assert pr.shape == (topology.n_gmms,)
+        ws = [np.ascontiguousarray(_f32(l[0])) for l in layers]
+        bs = [np.ascontiguousarray(_f32(l[1])) for l in layers]
+        n = len(layers)
+        assert n >= 1 and all(w.ndim == 2 and b.shape == (w.shape[0],) for w, b in zip(ws, bs))
+        assert all(ws[i].shape[1] == ws[i - 1].shape[0] for i in range(1, n))
+        width = _i32([w.shape[0] for w in ws])
+        act = _i32([int(l[2]) for l in layers[:-1]] + [ACT_LINEAR])
+        wp = (C.POINTER(C.c_float) * n)(*[_p(w, C.c_float) for w in ws])
+        bp = (C.POINTER(C.c_float) * n)(*[_p(b, C.c_float) for b in bs])
+        h = C.c_void_p()
+        _check(lib().jd_am_create_mlp_tied(C.byref(h), topology.h, _p(pr, C.c_float), C.c_int32(ws[0].shape[1]), C.c_int32(n),
+                                           _p(width, C.c_int32), _p(act, C.c_int32), wp, bp))
+        return cls(h)
+
+    @classmethod
+    def load_mlp_tied(cls, topology: "Models", path):
+        """Tied neural models from a JMLP version 2 file (jd_am_load_mlp_tied) beside the HMM set it was trained for."""
+        h = C.c_void_p()
+        _check(lib().jd_am_load_mlp_tied(C.byref(h), topology.h, os.fsencode(path)))
+        return cls(h)
+
+    @classmethod
     def load_mlp(cls, path):
         """Neural acoustic models from a JMLP file (jd_am_load_mlp)."""
         h = C.c_void_p()
@@ -617,6 +655,7 @@ def debug_log1pe(d, variant: int, device: int = -1):
 (KERNEL_NONE, KERNEL_GMM_GENERIC, KERNEL_GMM39_16, KERNEL_GMM39_64, KERNEL_GMM_FAST39_16, KERNEL_GMM_FAST39_64, KERNEL_GMM_FAST_16,
  KERNEL_GMM_FAST_64, KERNEL_HYBRID) = range(9)
 KERNEL_MLP = 9                     # jd_mlp_kernel (Models.from_mlp); beside KERNEL_NAMES, the list of the kernels of tests/score_rows_cases.py
+KERNEL_MLP_TIED = 10               # jd_mlp_tied_kernel (Models.from_mlp_tied)
 KERNEL_NAMES = ["none", "jd_gmm_kernel<0>", "jd_gmm_kernel39<16>", "jd_gmm_kernel39<64>", "jd_gmm_fast39<16>", "jd_gmm_fast39<64>",
                 "jd_gmm_fast<16>", "jd_gmm_fast<64>", "jd_hybrid_kernel"]
 

@@ -171,6 +171,7 @@ int main(int argc, char **argv)
 {
     const char *fsm = 0, *insyms = 0, *outsyms = 0, *amf = 0, *mmf = 0, *list = 0;
     const char *mlpf = 0, *monoList = 0;                                     // -mlpFName: a JMLP file (jd_am_load_mlp); its phones' names
+    const char *mlpTied = 0;                                                 // -mlpTiedFName: a JMLP version 2 file (jd_am_load_mlp_tied) beside a models file
     const char *gramFsm = 0, *gramInSyms = 0, *gramOutSyms = 0;              // juicer.cpp:128-130: separate C.L and G
     float mainBeam = 0, startBeam = 0, endBeam = 0, wordBeam = 0, lmScale = 1.0f, insPen = 0.0f;
     int maxHyps = 0, framesPerSec = 100, device = 0, batch = 64, useAdapter = 0, writeBinaryFiles = 0, nDevices = 0, pushing = 0, lazy = 0, nThreads = 0, lookaheadSets = 0;
@@ -194,6 +195,7 @@ int main(int argc, char **argv)
         else if (a == "-outSymsFName") outsyms = nxt(); else if (a == "-modelsFName") amf = nxt();
         else if (a == "-htkModelsFName") mmf = nxt();
         else if (a == "-mlpFName") mlpf = nxt();
+        else if (a == "-mlpTiedFName") mlpTied = nxt();
         else if (a == "-inputFName") list = nxt(); else if (a == "-mainBeam") mainBeam = (float)atof(nxt());
         else if (a == "-phoneStartBeam") startBeam = (float)atof(nxt()); else if (a == "-phoneEndBeam") endBeam = (float)atof(nxt());
         else if (a == "-wordEmitBeam") wordBeam = (float)atof(nxt()); else if (a == "-maxHyps") maxHyps = atoi(nxt());
@@ -217,10 +219,13 @@ int main(int argc, char **argv)
         else if (a == "-tiedListFName" || a == "-cdSepChars" || a == "-silMonophone" || a == "-pauseMonophone") (void)nxt();
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
-    if (!fsm || (!amf && !mmf && !mlpf) || !list) {
+    auto usage = [&]() {
         fprintf(stderr, "usage: jd_batch_test -fsmFName F (-htkModelsFName M.mmf | -modelsFName M.jdam | -mlpFName M.jmlp) -inputFName LIST [-mainBeam b]\n"
                         "       [-phoneStartBeam b]   (-mlpFName: a neural acoustic model, jd_am_save_mlp's file; the inputs are then feature vectors of the\n"
                         "        network's input size, and the device runs its forward pass)\n"
+                        "       [-mlpTiedFName M.jmlp   (beside -htkModelsFName or -modelsFName: a tied-state network, jd_am_save_mlp's file of a tied model -\n"
+                        "        the models file gives the HMMs, their state tying and their names, the network one output per tied state; the inputs are\n"
+                        "        feature vectors of the network's input size)]\n"
                         "       [-phoneEndBeam b] [-wordEmitBeam b] [-maxHyps n] [-lmScaleFactor s] [-insPenalty p] [-batch n] [-perFrameAdapter]\n"
                         "       [-outputFormat ref|trans|mlf|xmlf|verbose] [-writeBinaryFiles] [-refFName REF] [-removeSentMarks]\n"
                         "       [-sentStartWord W] [-sentEndWord W] [-outSymsFName SYMS] [-outputFName stdout|stderr|FILE]\n"
@@ -235,6 +240,14 @@ int main(int argc, char **argv)
                         "        not with -threads, -devices or -refFName)]\n"
                         "       [-monoListFName F] [-tiedListFName F] [-cdSepChars C] [-silMonophone P] [-pauseMonophone P]   (accepted, no effect:\n"
                         "        phones are printed by the HMM names of the models file - except -monoListFName with -mlpFName: line h names phone h)\n");
+    };
+    if (mlpTied && !amf && !mmf) {                                             // (a tied network holds no topology; -mlpFName is none)
+        fprintf(stderr, "jd_batch_test: -mlpTiedFName needs a models file beside it (-htkModelsFName or -modelsFName): the HMMs and their state tying\n");
+        usage();
+        return 1;
+    }
+    if (!fsm || (!amf && !mmf && !mlpf) || !list) {
+        usage();
         return 2;
     }
     if (lookaheadSets && !gramFsm) { fprintf(stderr, "jd_batch_test: -lookaheadSets needs -gramFsmFName (it is an option of the composition)\n"); return 1; }
@@ -287,6 +300,12 @@ int main(int argc, char **argv)
     } else if (mlpf) {
         if (jd_am_load_mlp(&am, mlpf)) die("jd_am_load_mlp");
     } else am = load_jdam(amf);
+    if (mlpTied) {                                              // the models file is the topology of a tied-state network
+        jd_am *top = am;
+        am = 0;
+        if (jd_am_load_mlp_tied(&am, top, mlpTied)) die("jd_am_load_mlp_tied");
+        jd_am_destroy(top);
+    }
     const int D = jd_am_vec_size(am);
     std::vector<std::string> hmmNames;         // PhoneLookup::getModelStr (juicer.cpp:606-621): the models' names
     if (modelLevel && mlpf && !mmf && monoList) {                               // (a JMLP file holds no names: line h of the monophone list is phone h)

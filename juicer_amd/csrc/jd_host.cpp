@@ -476,6 +476,90 @@ extern "C" int jd_am_create_mlp(jd_am **out, int32_t n_phones, const float *prio
     }
     return create_mlp_models(out, n_phones, priors, states_per_model, d, w.data(), b.data(), "jd_am_create_mlp");
 }
+// Tied hybrid models: the HMM set of `topology` - HMMs, hmm_gmm (the state tying), transition matrices with their trP / se / tee,
+// names, max_n - with one log posterior per TIED STATE in place of its Gaussians: an emitting state tied to g scores
+// x[g] - log(prior[g]) (jd_hybrid_kernel over n_gmm, as ever).  D: the feature vectors' size (n_gmm, or a network's in_dim).
+// The Gaussians are not copied and - unlike create_hybrid_models' - no per-dimension placeholders are kept either (n_gmm x D
+// floats three times over is 800 MB at 8192 tied states fed their own posteriors); nothing reads them in hybrid mode, and
+// upload_am_gmm uploads none for tied models.  The per-state tables are one neutral component each.
+static int create_hybrid_tied_models(jd_am **out, const jd_am *topology, const float *priors, int32_t D, const char *who)
+{
+    if (!out) return jd_fail(JD_EINVAL, "%s: out is null", who);
+    if (!topology) return jd_fail(JD_EINVAL, "%s: topology is null", who);
+    if (!priors) return jd_fail(JD_EINVAL, "%s: priors is null", who);
+    if (topology->hybrid)
+        return jd_fail(JD_EINVAL, "%s: topology holds hybrid or neural models; it is a set of GMM models (jd_am_load_mmf, jd_am_load_jmbi, jd_am_create_htk)", who);
+    if (D <= 0) return jd_fail(JD_EINVAL, "%s: bad argument", who);
+    const size_t G = (size_t)topology->n_gmm;
+    for (size_t g = 0; g < G; ++g)
+        if (!(priors[g] > 0.0f)) return jd_fail(JD_EINVAL, "%s: prior %zu is not positive", who, g);
+    jd_am *a = new jd_am();
+    a->D = D; a->n_gmm = topology->n_gmm; a->max_mix = 1;
+    a->n_hmm = topology->n_hmm; a->max_n = topology->max_n; a->n_tm = topology->n_tm;
+    a->n_mix.assign(G, 1);
+    a->det.assign(G, 0.0f); a->weight.assign(G, 1.0f); a->sum_log_var.assign(G, 0.0f); a->log_weight.assign(G, 0.0f);
+    a->hmm_n = topology->hmm_n; a->hmm_gmm = topology->hmm_gmm; a->hmm_tm = topology->hmm_tm; a->hmm_tee = topology->hmm_tee;
+    a->tm_n = topology->tm_n; a->trP = topology->trP; a->se = topology->se; a->transp = topology->transp;
+    a->hmm_name = topology->hmm_name;
+    a->hybrid = true; a->tied = true;
+    a->log_prior.resize(G);
+    for (size_t g = 0; g < G; ++g) a->log_prior[g] = std::log(priors[g]);          // (HTKModels.cpp:183 log(float), as create_hybrid_models)
+    *out = a;
+    return JD_OK;
+}
+extern "C" int jd_am_create_hybrid_tied(jd_am **out, const jd_am *topology, const float *priors)
+{
+    return create_hybrid_tied_models(out, topology, priors, topology ? topology->n_gmm : 1, "jd_am_create_hybrid_tied");
+}
+
+// Tied neural models: the above with the network whose outputs are the tied states' logits.  D = in_dim.
+static int create_mlp_tied_models(jd_am **out, const jd_am *topology, const float *priors, const JdMlpDesc &d, const float *w, const float *b,
+                                  const char *who)
+{
+    if (!topology) return jd_fail(JD_EINVAL, "%s: topology is null", who);
+    char why[240];
+    if (jd_mlp_check(d, topology->n_gmm, why, sizeof why, true)) return jd_fail(JD_EINVAL, "%s: %s", who, why);
+    jd_am *a = nullptr;
+    int rc = create_hybrid_tied_models(&a, topology, priors, d.in_dim, who);
+    if (rc) return rc;
+    a->mlp = true;
+    a->mlp_desc = d;
+    a->mlp_states_per_model = 0;
+    a->mlp_prior.assign(priors, priors + topology->n_gmm);
+    a->mlp_w.assign(w, w + jd_mlp_w_begin(d, d.n_layers));
+    a->mlp_b.assign(b, b + jd_mlp_b_begin(d, d.n_layers));
+    jd_mlp_pack(d, a->mlp_w.data(), a->mlp_b.data(), a->mlp_wp, a->mlp_bp);
+    *out = a;
+    return JD_OK;
+}
+extern "C" int jd_am_create_mlp_tied(jd_am **out, const jd_am *topology, const float *priors, int32_t in_dim, int32_t n_layers,
+                                     const int32_t *width, const int32_t *act, const float *const *weight, const float *const *bias)
+{
+    const char *who = "jd_am_create_mlp_tied";
+    if (!out) return jd_fail(JD_EINVAL, "%s: out is null", who);
+    if (!topology) return jd_fail(JD_EINVAL, "%s: topology is null", who);
+    if (!priors) return jd_fail(JD_EINVAL, "%s: priors is null", who);
+    if (!width || !weight || !bias || (n_layers > 1 && !act)) return jd_fail(JD_EINVAL, "%s: width, act, weight or bias is null", who);
+    if (topology->hybrid)
+        return jd_fail(JD_EINVAL, "%s: topology holds hybrid or neural models; it is a set of GMM models (jd_am_load_mmf, jd_am_load_jmbi, jd_am_create_htk)", who);
+    if (n_layers < 1 || n_layers > JD_MLP_MAX_LAYERS)
+        return jd_fail(JD_EINVAL, "%s: n_layers = %d outside 1 .. %d (JD_MLP_MAX_LAYERS)", who, n_layers, JD_MLP_MAX_LAYERS);
+    JdMlpDesc d;
+    d.in_dim = in_dim; d.n_layers = n_layers;
+    for (int32_t l = 0; l < n_layers; ++l) {
+        if (!weight[l] || !bias[l]) return jd_fail(JD_EINVAL, "%s: layer %d has no weights or biases", who, l);
+        d.width[l] = width[l];
+        d.act[l] = l < n_layers - 1 ? act[l] : JD_ACT_LINEAR;
+    }
+    char why[240];
+    if (jd_mlp_check(d, topology->n_gmm, why, sizeof why, true)) return jd_fail(JD_EINVAL, "%s: %s", who, why);
+    std::vector<float> w(jd_mlp_w_begin(d, n_layers)), b(jd_mlp_b_begin(d, n_layers));
+    for (int32_t l = 0; l < n_layers; ++l) {
+        memcpy(w.data() + jd_mlp_w_begin(d, l), weight[l], (size_t)d.width[l] * jd_mlp_k(d, l) * sizeof(float));
+        memcpy(b.data() + jd_mlp_b_begin(d, l), bias[l], (size_t)d.width[l] * sizeof(float));
+    }
+    return create_mlp_tied_models(out, topology, priors, d, w.data(), b.data(), who);
+}
 extern "C" int jd_am_mlp_info(const jd_am *a, int32_t *in_dim, int32_t *n_layers, int32_t *width, int32_t *act)
 {
     if (!a) return jd_fail(JD_EINVAL, "jd_am_mlp_info: null");
@@ -494,7 +578,8 @@ extern "C" int jd_am_save_mlp(const jd_am *a, const char *path)
     if (!a || !path) return jd_fail(JD_EINVAL, "jd_am_save_mlp: null argument");
     if (!a->mlp) return jd_fail(JD_ESTATE, "jd_am_save_mlp: these models hold no network");
     JdMlpFile f;
-    f.d = a->mlp_desc; f.n_phones = a->n_hmm; f.states_per_model = a->mlp_states_per_model;
+    f.d = a->mlp_desc; f.n_phones = a->tied ? a->n_gmm : a->n_hmm; f.states_per_model = a->mlp_states_per_model;
+    f.tied = a->tied;                                                  // (version 2: the network and the priors, no topology)
     f.priors = a->mlp_prior; f.w = a->mlp_w; f.b = a->mlp_b;
     std::vector<unsigned char> bytes;
     jd_mlp_file_write(f, bytes);
@@ -504,20 +589,45 @@ extern "C" int jd_am_save_mlp(const jd_am *a, const char *path)
     if (fclose(fd) != 0 || !ok) return jd_fail(JD_EFORMAT, "jd_am_save_mlp: error writing file %s", path);
     return JD_OK;
 }
-extern "C" int jd_am_load_mlp(jd_am **out, const char *path)
+// the bytes of a JMLP file, read as version 1 (jd_am_load_mlp) or 2 (tied: jd_am_load_mlp_tied)
+static int read_jmlp(const char *path, bool tied, JdMlpFile &f, const char *who)
 {
-    if (!out || !path) return jd_fail(JD_EINVAL, "jd_am_load_mlp: null argument");
     FILE *fd = fopen(path, "rb");
-    if (!fd) return jd_fail(JD_EFORMAT, "jd_am_load_mlp: error opening file %s", path);
+    if (!fd) return jd_fail(JD_EFORMAT, "%s: error opening file %s", who, path);
     std::vector<unsigned char> bytes;
     unsigned char chunk[65536];
     size_t n;
     while ((n = fread(chunk, 1, sizeof chunk, fd)) > 0) bytes.insert(bytes.end(), chunk, chunk + n);
     fclose(fd);
-    JdMlpFile f;
     char why[300];
-    if (jd_mlp_file_read(bytes.data(), bytes.size(), f, why, sizeof why)) return jd_fail(JD_EFORMAT, "%s: %s", path, why);
-    const int rc = create_mlp_models(out, f.n_phones, f.priors.data(), f.states_per_model, f.d, f.w.data(), f.b.data(), "jd_am_load_mlp");
+    if (jd_mlp_file_read(bytes.data(), bytes.size(), f, why, sizeof why, tied)) return jd_fail(JD_EFORMAT, "%s: %s", path, why);
+    return JD_OK;
+}
+extern "C" int jd_am_load_mlp_tied(jd_am **out, const jd_am *topology, const char *path)
+{
+    if (!out || !path) return jd_fail(JD_EINVAL, "jd_am_load_mlp_tied: null argument");
+    if (!topology) return jd_fail(JD_EINVAL, "jd_am_load_mlp_tied: topology is null");
+    if (topology->hybrid)
+        return jd_fail(JD_EINVAL, "jd_am_load_mlp_tied: topology holds hybrid or neural models; it is a set of GMM models (jd_am_load_mmf, jd_am_load_jmbi, jd_am_create_htk)");
+    JdMlpFile f;
+    int rc = read_jmlp(path, true, f, "jd_am_load_mlp_tied");
+    if (rc) return rc;
+    if (f.n_phones != topology->n_gmm)                                 // (a sound file beside another HMM set: the caller's mistake)
+        return jd_fail(JD_EINVAL, "jd_am_load_mlp_tied: %s has %d outputs, the topology %d tied states (n_gmm)", path, f.n_phones, topology->n_gmm);
+    rc = create_mlp_tied_models(out, topology, f.priors.data(), f.d, f.w.data(), f.b.data(), "jd_am_load_mlp_tied");
+    if (rc == JD_EINVAL) {                                             // (a prior that is not positive: the file's fault)
+        const std::string what = jd_last_error();
+        return jd_fail(JD_EFORMAT, "%s: %s", path, what.c_str());
+    }
+    return rc;
+}
+extern "C" int jd_am_load_mlp(jd_am **out, const char *path)
+{
+    if (!out || !path) return jd_fail(JD_EINVAL, "jd_am_load_mlp: null argument");
+    JdMlpFile f;
+    int rc = read_jmlp(path, false, f, "jd_am_load_mlp");
+    if (rc) return rc;
+    rc = create_mlp_models(out, f.n_phones, f.priors.data(), f.states_per_model, f.d, f.w.data(), f.b.data(), "jd_am_load_mlp");
     if (rc == JD_EINVAL) {                                             // (a prior that is not positive, a states_per_model outside 3 .. JD_MAXN)
         const std::string what = jd_last_error();
         return jd_fail(JD_EFORMAT, "%s: %s", path, what.c_str());
@@ -1180,8 +1290,8 @@ extern "C" int jd_am_load_jmbi(jd_am **out, const char *path)
 extern "C" int jd_am_save_jmbi(const jd_am *a, const char *path)
 {
     if (!a || !path) return jd_fail(JD_EINVAL, "jd_am_save_jmbi: null argument");
-    if (a->var.empty() || a->transp.empty()) return jd_fail(JD_ESTATE, "jd_am_save_jmbi: models hold no HTK-level parameters");
     if (a->hybrid) return jd_fail(JD_ESTATE, "jd_am_save_jmbi: hybrid models are not written (create them from the priors)");
+    if (a->var.empty() || a->transp.empty()) return jd_fail(JD_ESTATE, "jd_am_save_jmbi: models hold no HTK-level parameters");
     BinWriter w;
     w.f = fopen(path, "wb");
     if (!w.f) return jd_fail(JD_EFORMAT, "HTKModels::output - error opening file %s", path);

@@ -1,6 +1,7 @@
 // jd_host_scoring.h - the host side of the companion scoring kernels (included by jd_device.hip): the model parameters on the device,
 // launch_gmm - the launch of what jd_score_plan.h plans: which kernel (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast,
-// jd_dec_set_scoring's option; the generic and the hybrid kernel; jd_mlp_kernel for the models of jd_am_create_mlp), its tiles, grid and
+// jd_dec_set_scoring's option; the generic and the hybrid kernel; jd_mlp_kernel for the models of jd_am_create_mlp, jd_mlp_tied_kernel for
+// those of jd_am_create_mlp_tied), its tiles, grid and
 // LDS are decided there, on plain data, and tested on the CPU - jd_am_score_frames, jd_am_mlp_forward.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
 #pragma once
 
@@ -29,18 +30,20 @@ struct AmDevBuf {
 static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
 {
     const size_t gm = (size_t)a->n_gmm * a->max_mix, D = (size_t)a->D;
-    std::vector<float> par(gm * D * 2);
-    for (size_t i = 0; i < gm; ++i)
-        for (size_t j = 0; j < D; ++j) {
-            par[(i * D + j) * 2] = a->mean[i * D + j];
-            par[(i * D + j) * 2 + 1] = a->ivar[i * D + j];
-        }
-    HIPCHK(hipMalloc(&b.par, par.size() * sizeof(float)));
-    HIPCHK(hipMalloc(&b.det, gm * sizeof(float)));
-    HIPCHK(hipMalloc(&b.n_mix, (size_t)a->n_gmm * sizeof(int)));
-    HIPCHK(hipMemcpy(b.par, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b.det, a->det.data(), gm * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b.n_mix, a->n_mix.data(), (size_t)a->n_gmm * sizeof(int), hipMemcpyHostToDevice));
+    if (!a->tied) {                                                    // (tied hybrid models hold no Gaussians, placeholders neither: jd_host.cpp)
+        std::vector<float> par(gm * D * 2);
+        for (size_t i = 0; i < gm; ++i)
+            for (size_t j = 0; j < D; ++j) {
+                par[(i * D + j) * 2] = a->mean[i * D + j];
+                par[(i * D + j) * 2 + 1] = a->ivar[i * D + j];
+            }
+        HIPCHK(hipMalloc(&b.par, par.size() * sizeof(float)));
+        HIPCHK(hipMalloc(&b.det, gm * sizeof(float)));
+        HIPCHK(hipMalloc(&b.n_mix, (size_t)a->n_gmm * sizeof(int)));
+        HIPCHK(hipMemcpy(b.par, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.det, a->det.data(), gm * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.n_mix, a->n_mix.data(), (size_t)a->n_gmm * sizeof(int), hipMemcpyHostToDevice));
+    }
     {   // the table of jd_log1pe_table (both exact kernels)
         std::vector<JdLogTab> t(129);
         jd_fill_logtab(t.data());
@@ -58,6 +61,7 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
         HIPCHK(hipMemcpy(b.mlp_b, a->mlp_bp.data(), a->mlp_bp.size() * sizeof(float), hipMemcpyHostToDevice));
         // (above 64 KB of dynamic LDS a kernel has to be told; per device, and the same value every time)
         HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_LDS_MAX));
+        if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_LDS_MAX));
     }
     return JD_OK;
 }
@@ -107,13 +111,20 @@ static bool am_fast(const AmDevBuf &b) { return b.fast && b.par_fast; }         
 static ScorePlan gmm_plan(const jd_am *a, const AmDevBuf &b, int n_rows, int max_blocks = 0, int used_row_tiles = -1, bool has_list = false,
                           int n_rt_list = 0)
 {
-    return score_plan(ScorePlanIn{a->D, a->n_gmm, a->hybrid, a->mlp, am_fast(b), n_rows, max_blocks, used_row_tiles, has_list, n_rt_list});
+    return score_plan(ScorePlanIn{a->D, a->n_gmm, a->hybrid, a->mlp, am_fast(b), n_rows, max_blocks, used_row_tiles, has_list, n_rt_list,
+                                  a->mlp && a->tied});
 }
 
-// jd_mlp_kernel on rows [0, n_rows), on the plan's grid: d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
+// jd_mlp_kernel - for tied models jd_mlp_tied_kernel - on rows [0, n_rows), on the plan's grid: d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
 static void launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
                        unsigned grid, int out_mode, int layer)
 {
+    if (a->tied) {
+        const JdMlpDev m = jd_mlp_dev(a->mlp_desc, true);
+        hipLaunchKernelGGL(jd_mlp_tied_kernel, dim3(grid), dim3(256), jd_mlp_tied_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b,
+                           b.log_prior, b.logtab, m, d_out, out_mode, layer);
+        return;
+    }
     const JdMlpDev m = jd_mlp_dev(a->mlp_desc);
     hipLaunchKernelGGL(jd_mlp_kernel, dim3(grid), dim3(256), jd_mlp_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
                        b.logtab, m, d_out, out_mode, layer);
@@ -139,7 +150,8 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 #define GMM_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), p.lds_bytes, st, d_feats, d_row_src, n_rows, __VA_ARGS__)
 #define GMM_ARGS(par) par, b.det, b.n_mix, a->n_gmm, a->max_mix
     switch (p.kernel) {
-    case JD_KERNEL_MLP: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0); break;
+    case JD_KERNEL_MLP:
+    case JD_KERNEL_MLP_TIED: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0); break;
     case JD_KERNEL_HYBRID: GMM_LAUNCH(jd_hybrid_kernel, b.log_prior, a->n_gmm, d_ll); break;
     case JD_KERNEL_GMM_FAST39_16: GMM_LAUNCH(jd_gmm_fast39<GMM_GT_SMALL>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
     case JD_KERNEL_GMM_FAST39_64: GMM_LAUNCH(jd_gmm_fast39<GMM_GT>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
@@ -162,7 +174,7 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 static int gmm_tiles128_occupancy(const jd_am *a, const AmDevBuf &b, int *per_cu)
 {
     *per_cu = 0;
-    const ScoreLarge large = score_plan_large(a->D, a->hybrid, a->mlp, am_fast(b));
+    const ScoreLarge large = score_plan_large(a->D, a->hybrid, a->mlp, am_fast(b));   // (none for either kind of neural models)
     const void *kernel = nullptr;
     switch (large.kernel) {
     case JD_KERNEL_GMM_FAST39_64: kernel = (const void *)jd_gmm_fast39<GMM_GT>; break;
@@ -368,7 +380,7 @@ extern "C" int jd_am_mlp_forward_host(const jd_am *a, const float *frames, int32
     const int rc = mlp_args(a, frames, n_frames, logpost, "jd_am_mlp_forward_host");
     if (rc) return rc;
     const JdMlpHostMath math;
-    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math);
+    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
     return JD_OK;
 }
 extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t on_device, const float *frames, int32_t n_frames, int32_t layer,
@@ -380,7 +392,7 @@ extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t 
         return jd_fail(JD_EINVAL, "jd_debug_mlp_activations: layer %d outside [0, %d)", layer, a->mlp_desc.n_layers);
     if (on_device) return mlp_on_device(a, device, frames, n_frames, JD_MLP_OUT_LAYER, layer, out);
     const JdMlpHostMath math;
-    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math);
+    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
     return JD_OK;
 }
 

@@ -65,7 +65,10 @@ struct jd_am {
     // hybrid (ANN / LNA) scoring, HTKModels::Load(phones, priors, statesPerModel) HTKModels.cpp:74-218:
     // the feature vector holds one log posterior per model, output = x[model] - log prior (:481-512)
     bool hybrid = false;
-    std::vector<float> log_prior;                 // [n_hmm]
+    std::vector<float> log_prior;                 // [n_gmm] (jd_am_create_hybrid: n_gmm = n_hmm, one output per phone)
+    // tied hybrid models (jd_am_create_hybrid_tied / jd_am_create_mlp_tied): HMMs, transitions, tee models and state tying copied
+    // from a GMM model set, one output (log posterior) per TIED STATE - hmm_gmm indexes the outputs as it indexes the GMMs
+    bool tied = false;
     // neural acoustic models (jd_am_create_mlp, jd_mlp.h): hybrid models whose log posteriors the device computes from feature
     // vectors of D = in_dim values with this network (mlp_w / mlp_b as given, mlp_wp / mlp_bp packed for jd_mlp_kernel)
     bool mlp = false;

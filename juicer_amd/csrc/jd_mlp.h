@@ -32,6 +32,21 @@
 // so that a wave's load of one (n tile, k group) is 1 KB contiguous, and the padding is +0.0f.  Biases are padded to Np with 0.
 // The ACTIVATIONS' padding in LDS is -0.0f: a padded step is then fmaf(-0, +0, c) = c for every c, a -0 included.
 //
+// TIED models (jd_am_create_mlp_tied: one output per tied state - senone - of an HMM set of any topology).  Layers, activations
+// and the linear chain are the same; two things differ:
+//   limits    the LAST width is 1 .. JD_MLP_MAX_OUT = 16384 (in_dim and the hidden widths stay 1 .. JD_MLP_MAX_DIM): the output
+//             layer's logits do not live in LDS (16 x 16384 floats = 1 MB) but in the tile's own rows of the likelihood table, so
+//             that the LDS holds the widest of in_dim and the HIDDEN layers, plus the partials below.
+//   output    logZ over several thousand outputs is not one serial chain.  JD_MLP_LZ_CHAINS = 128 - a constant: never a function
+//             of rows, launch, grid, device or network - interleaved partial chains
+//               p[c] = logAdd chain from JD_MLP_LOG_ZERO over z[c], z[c + 128], z[c + 256], ...  (ascending)   for c < min(128, P)
+//               logZ = logAdd chain from JD_MLP_LOG_ZERO over p[0], p[1], ...                    (ascending; empty chains, c >= P,
+//                      are not combined)
+//             then logpost[j] = z[j] - logZ and ll[j] = logpost[j] - log_prior[j], one float operation each, as above.
+//             (128: a workgroup's four waves cover 8 n tiles of 16 outputs a turn, so chain j mod 128 belongs to one wave, which
+//             meets its elements in ascending order and keeps the partial in a register beside the accumulator.)
+// jd_mlp_forward_row / jd_mlp_forward_host take the model kind as their last argument (false: the serial chain, bit for bit as ever).
+//
 // JMLP file (little-endian, no padding; jd_am_save_mlp / jd_am_load_mlp):
 //   char   magic[4] = "JMLP"
 //   u32    version = 1
@@ -42,6 +57,9 @@
 //   per layer l:  f32 weight[width[l]][K_l], f32 bias[width[l]]        (K_0 = in_dim, K_l = width[l - 1])
 // A file that ends early, carries another magic or version, describes a network the check refuses, or is longer than its header
 // says is JD_EFORMAT.
+// Version 2 is a TIED model's network (jd_am_save_mlp on such a model / jd_am_load_mlp_tied): the same layout with
+// states_per_model = 0 and n_phones = the number of outputs (tied states), up to JD_MLP_MAX_OUT.  It holds no topology: the loader
+// is given the HMM set.  Each loader refuses the other's version and names the loader that reads it.
 #ifndef JD_MLP_H
 #define JD_MLP_H
 
@@ -59,6 +77,8 @@
 
 #define JD_MLP_MAX_DIM 1024
 #define JD_MLP_MAX_LAYERS 16
+#define JD_MLP_MAX_OUT 16384        // the last width of a TIED model (jd_am_create_mlp_tied): its logits live in the likelihood table
+#define JD_MLP_LZ_CHAINS 128        // a tied model's logZ: interleaved partial chains (a constant of the numerics)
 #define JD_MLP_ROWS 16              // rows of a workgroup's tile (the MFMA's M)
 #define JD_MLP_NT 16                // outputs of an n tile (the MFMA's N)
 #define JD_MLP_KG 16                // inputs of a k group: four k-steps of 4
@@ -88,7 +108,8 @@ static inline size_t jd_mlp_b_begin(const JdMlpDesc &d, int l)
 }
 
 // 0, or what is wrong with the description (msg names the limit)
-static inline int jd_mlp_check(const JdMlpDesc &d, int n_phones, char *msg, size_t cap)
+// (tied: the models of jd_am_create_mlp_tied - the last width is bounded by JD_MLP_MAX_OUT and n_phones counts tied states)
+static inline int jd_mlp_check(const JdMlpDesc &d, int n_phones, char *msg, size_t cap, bool tied = false)
 {
     if (d.n_layers < 1 || d.n_layers > JD_MLP_MAX_LAYERS) {
         snprintf(msg, cap, "n_layers = %d outside 1 .. %d (JD_MLP_MAX_LAYERS)", d.n_layers, JD_MLP_MAX_LAYERS);
@@ -99,7 +120,12 @@ static inline int jd_mlp_check(const JdMlpDesc &d, int n_phones, char *msg, size
         return 2;
     }
     for (int l = 0; l < d.n_layers; ++l) {
-        if (d.width[l] < 1 || d.width[l] > JD_MLP_MAX_DIM) {
+        if (tied && l == d.n_layers - 1) {
+            if (d.width[l] < 1 || d.width[l] > JD_MLP_MAX_OUT) {
+                snprintf(msg, cap, "width[%d] = %d outside 1 .. %d (JD_MLP_MAX_OUT: the last width of a tied model)", l, d.width[l], JD_MLP_MAX_OUT);
+                return 3;
+            }
+        } else if (d.width[l] < 1 || d.width[l] > JD_MLP_MAX_DIM) {
             snprintf(msg, cap, "width[%d] = %d outside 1 .. %d (JD_MLP_MAX_DIM: the activations of a 16-row tile stay in LDS)", l, d.width[l], JD_MLP_MAX_DIM);
             return 3;
         }
@@ -113,7 +139,8 @@ static inline int jd_mlp_check(const JdMlpDesc &d, int n_phones, char *msg, size
         return 5;
     }
     if (d.width[d.n_layers - 1] != n_phones) {
-        snprintf(msg, cap, "the last width, %d, is not n_phones = %d", d.width[d.n_layers - 1], n_phones);
+        if (tied) snprintf(msg, cap, "the last width, %d, is not the topology's number of tied states, n_gmm = %d", d.width[d.n_layers - 1], n_phones);
+        else snprintf(msg, cap, "the last width, %d, is not n_phones = %d", d.width[d.n_layers - 1], n_phones);
         return 6;
     }
     return 0;
@@ -125,7 +152,8 @@ struct JdMlpDev {
     int32_t width[JD_MLP_MAX_LAYERS], act[JD_MLP_MAX_LAYERS];
     uint32_t w_off[JD_MLP_MAX_LAYERS + 1], b_off[JD_MLP_MAX_LAYERS + 1];      // packed; [n_layers]: the sizes
 };
-static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d)
+// (tied: jd_mlp_tied_kernel's - the last layer's outputs are not held in LDS and do not widen the stride)
+static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d, bool tied = false)
 {
     JdMlpDev m;
     memset(&m, 0, sizeof m);
@@ -135,7 +163,7 @@ static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d)
         m.width[l] = d.width[l]; m.act[l] = d.act[l];
         m.w_off[l + 1] = m.w_off[l] + (uint32_t)jd_mlp_pad16(d.width[l]) * (uint32_t)jd_mlp_pad16(jd_mlp_k(d, l));
         m.b_off[l + 1] = m.b_off[l] + (uint32_t)jd_mlp_pad16(d.width[l]);
-        if (jd_mlp_pad16(d.width[l]) > widest) widest = jd_mlp_pad16(d.width[l]);
+        if (!(tied && l == d.n_layers - 1) && jd_mlp_pad16(d.width[l]) > widest) widest = jd_mlp_pad16(d.width[l]);
     }
     m.stride = widest + JD_MLP_LDS_PAD;
     return m;
@@ -143,6 +171,9 @@ static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d)
 // two activation buffers, the tile's row_src entries and its rows' logZ
 static inline size_t jd_mlp_lds_bytes(const JdMlpDev &m) { return ((size_t)2 * JD_MLP_ROWS * m.stride + 2 * JD_MLP_ROWS) * 4; }
 #define JD_MLP_LDS_MAX ((size_t)(2 * JD_MLP_ROWS * (JD_MLP_MAX_DIM + JD_MLP_LDS_PAD) + 2 * JD_MLP_ROWS) * 4)
+// jd_mlp_tied_kernel's (m = jd_mlp_dev(d, true)): the same, and the tile's partial chains [16][JD_MLP_LZ_CHAINS]
+static inline size_t jd_mlp_tied_lds_bytes(const JdMlpDev &m) { return jd_mlp_lds_bytes(m) + (size_t)JD_MLP_ROWS * JD_MLP_LZ_CHAINS * 4; }
+#define JD_MLP_TIED_LDS_MAX (JD_MLP_LDS_MAX + (size_t)JD_MLP_ROWS * JD_MLP_LZ_CHAINS * 4)
 
 // where input k of an activation row sits in LDS: a k group's 16 values k-step-minor, so that a lane's four k-steps (k = 4 e + q,
 // e = 0 .. 3, for its q = lane >> 4) are one 16-byte read
@@ -192,9 +223,10 @@ static inline void jd_mlp_unpack(const JdMlpDesc &d, const float *wp, const floa
 
 // ---- the host twin.  One row x[in_dim].  stop_layer in [0, n_layers): out[width[stop_layer]] = the activations behind that layer
 // (the raw logits for the last).  stop_layer = -1: out[n_phones] = the log posteriors (log_prior null) or the hybrid scores.
+// tied: logZ by JD_MLP_LZ_CHAINS interleaved partial chains (the models of jd_am_create_mlp_tied), else the one serial chain.
 template <class M>
 static inline void jd_mlp_forward_row(const JdMlpDesc &d, const float *w, const float *b, const float *log_prior, const float *x, int stop_layer,
-                                      float *out, const M &math)
+                                      float *out, const M &math, bool tied = false)
 {
     std::vector<float> cur(x, x + d.in_dim), nxt;
     for (int l = 0; l < d.n_layers; ++l) {
@@ -215,7 +247,15 @@ static inline void jd_mlp_forward_row(const JdMlpDesc &d, const float *w, const 
     }
     const int P = d.width[d.n_layers - 1];
     float lz = JD_MLP_LOG_ZERO;
-    for (int j = 0; j < P; ++j) lz = math.log_add(lz, cur[(size_t)j]);
+    if (tied) {
+        const int C = P < JD_MLP_LZ_CHAINS ? P : JD_MLP_LZ_CHAINS;
+        for (int c = 0; c < C; ++c) {
+            float p = JD_MLP_LOG_ZERO;
+            for (int j = c; j < P; j += JD_MLP_LZ_CHAINS) p = math.log_add(p, cur[(size_t)j]);
+            lz = math.log_add(lz, p);
+        }
+    } else
+        for (int j = 0; j < P; ++j) lz = math.log_add(lz, cur[(size_t)j]);
     for (int j = 0; j < P; ++j) {
         const float lp = cur[(size_t)j] - lz;
         out[j] = log_prior ? lp - log_prior[j] : lp;
@@ -224,10 +264,10 @@ static inline void jd_mlp_forward_row(const JdMlpDesc &d, const float *w, const 
 // n rows of x [n][in_dim]; out [n][width[stop_layer]] / [n][n_phones]
 template <class M>
 static inline void jd_mlp_forward_host(const JdMlpDesc &d, const float *w, const float *b, const float *log_prior, const float *x, int n,
-                                       int stop_layer, float *out, const M &math)
+                                       int stop_layer, float *out, const M &math, bool tied = false)
 {
     const int ow = stop_layer >= 0 ? d.width[stop_layer] : d.width[d.n_layers - 1];
-    for (int r = 0; r < n; ++r) jd_mlp_forward_row(d, w, b, log_prior, x + (size_t)r * d.in_dim, stop_layer, out + (size_t)r * ow, math);
+    for (int r = 0; r < n; ++r) jd_mlp_forward_row(d, w, b, log_prior, x + (size_t)r * d.in_dim, stop_layer, out + (size_t)r * ow, math, tied);
 }
 
 // ---- the JMLP file as bytes
@@ -235,12 +275,13 @@ struct JdMlpFile {
     JdMlpDesc d;
     int32_t n_phones = 0, states_per_model = 0;
     std::vector<float> priors, w, b;              // [n_phones]; the layers' weights / biases one after the other
+    bool tied = false;                            // version 2: a tied model's network (states_per_model = 0, n_phones = the outputs)
 };
 static inline void jd_mlp_file_write(const JdMlpFile &f, std::vector<unsigned char> &out)
 {
     out.clear();
     auto put = [&](const void *p, size_t n) { const unsigned char *c = (const unsigned char *)p; out.insert(out.end(), c, c + n); };
-    const uint32_t version = 1;
+    const uint32_t version = f.tied ? 2 : 1;
     put("JMLP", 4); put(&version, 4);
     put(&f.n_phones, 4); put(&f.states_per_model, 4); put(&f.d.in_dim, 4); put(&f.d.n_layers, 4);
     put(f.d.width, 4 * (size_t)f.d.n_layers); put(f.d.act, 4 * (size_t)f.d.n_layers);
@@ -250,23 +291,27 @@ static inline void jd_mlp_file_write(const JdMlpFile &f, std::vector<unsigned ch
         put(f.b.data() + jd_mlp_b_begin(f.d, l), 4 * (size_t)f.d.width[l]);
     }
 }
-// 0, or what is wrong with the bytes
-static inline int jd_mlp_file_read(const unsigned char *p, size_t n, JdMlpFile &f, char *msg, size_t cap)
+// 0, or what is wrong with the bytes (tied: the reader of version 2, jd_am_load_mlp_tied's; else of version 1)
+static inline int jd_mlp_file_read(const unsigned char *p, size_t n, JdMlpFile &f, char *msg, size_t cap, bool tied = false)
 {
     size_t at = 0;
     auto get = [&](void *q, size_t k) { if (n - at < k) return false; memcpy(q, p + at, k); at += k; return true; };
     char magic[4]; uint32_t version = 0;
     if (!get(magic, 4) || memcmp(magic, "JMLP", 4) != 0) { snprintf(msg, cap, "not a JMLP file (magic)"); return 1; }
-    if (!get(&version, 4) || version != 1) { snprintf(msg, cap, "JMLP version %u (this build reads 1)", version); return 2; }
+    if (!get(&version, 4) || (version != 1 && version != 2)) { snprintf(msg, cap, "JMLP version %u (this build reads 1 and 2)", version); return 2; }
+    if (version == 2 && !tied) { snprintf(msg, cap, "JMLP version 2: a tied-state network without a topology (jd_am_load_mlp_tied reads it beside an HMM set)"); return 2; }
+    if (version == 1 && tied) { snprintf(msg, cap, "JMLP version 1: a phone network with its own topology (jd_am_load_mlp reads it)"); return 2; }
     f = JdMlpFile();
+    f.tied = tied;
     if (!get(&f.n_phones, 4) || !get(&f.states_per_model, 4) || !get(&f.d.in_dim, 4) || !get(&f.d.n_layers, 4)) { snprintf(msg, cap, "JMLP header truncated"); return 3; }
-    if (f.d.n_layers < 1 || f.d.n_layers > JD_MLP_MAX_LAYERS || f.n_phones < 1 || f.n_phones > JD_MLP_MAX_DIM) {
+    if (f.d.n_layers < 1 || f.d.n_layers > JD_MLP_MAX_LAYERS || f.n_phones < 1 || f.n_phones > (tied ? JD_MLP_MAX_OUT : JD_MLP_MAX_DIM) ||
+        (tied && f.states_per_model != 0)) {
         snprintf(msg, cap, "JMLP header: n_layers = %d, n_phones = %d", f.d.n_layers, f.n_phones);
         return 4;
     }
     if (!get(f.d.width, 4 * (size_t)f.d.n_layers) || !get(f.d.act, 4 * (size_t)f.d.n_layers)) { snprintf(msg, cap, "JMLP header truncated"); return 3; }
     char why[200];
-    if (jd_mlp_check(f.d, f.n_phones, why, sizeof why)) { snprintf(msg, cap, "JMLP header: %s", why); return 4; }
+    if (jd_mlp_check(f.d, f.n_phones, why, sizeof why, tied)) { snprintf(msg, cap, "JMLP header: %s", why); return 4; }
     f.priors.resize((size_t)f.n_phones);
     f.w.resize(jd_mlp_w_begin(f.d, f.d.n_layers));
     f.b.resize(jd_mlp_b_begin(f.d, f.d.n_layers));

@@ -17,6 +17,9 @@
 // The logits of the last layer land in LDS; lane r of the first wave runs row r's logAdd chain (serial by definition: no tree), and
 // all threads write (z - logZ) - log_prior, coalesced.  A row with row_src < 0 is written as 0.0f (as jd_hybrid_kernel does); a tile
 // whose rows are all unused does no arithmetic.  The grid strides over the row tiles (launch_gmm's max_blocks).
+//
+// jd_mlp_tied_kernel, at the end of this file, is the same pass for the models of jd_am_create_mlp_tied: an output layer of up to
+// 16384 tied states whose logits live in the tile's rows of the table, and logZ by 128 interleaved chains.
 #pragma once
 
 typedef float jd_mlp_f4 __attribute__((ext_vector_type(4)));
@@ -183,6 +186,149 @@ __global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ f
             if (r0 + r < n_rows) {
                 const float lp = in[r * S + j] - slz[r];
                 out[(size_t)(r0 + r) * P + j] = (ssrc[r] < 0) ? 0.0f : (out_mode == JD_MLP_OUT_LL ? lp - log_prior[j] : lp);
+            }
+        }
+    }
+}
+
+// ---- tied models (jd_am_create_mlp_tied): the same tile of 16 rows through the same hidden layers - ping-pong activations in LDS,
+// jd_mlp_chain, K never split - and an OUTPUT layer of up to JD_MLP_MAX_OUT = 16384 tied states, whose logits do not fit in LDS
+// (16 x 16384 floats = 1 MB).  They go to the tile's own rows of `out`: those rows are this launch's alone (launch_gmm keeps no
+// memory of its own), and the same workgroup normalises them in place.  m = jd_mlp_dev(desc, true): its stride covers in_dim and the
+// hidden widths; during the output layer only the layer's input buffer is read.
+//
+// logZ (jd_mlp.h: JD_MLP_LZ_CHAINS = 128 interleaved partial chains, then the chain of the partials).  A workgroup's four waves
+// cover 8 n tiles = 128 outputs a turn: wave w takes tiles 2 w + 8 t and 2 w + 1 + 8 t, so a lane's two accumulator columns are
+// always outputs j = 32 w + (lane & 15) (+ 16) mod 128 - chains that belong to this lane alone, met in ascending order.  The partials
+// of its 4 rows x 2 chains stay in registers beside the accumulators, one logAdd per logit as it leaves the MFMA; outputs at or
+// beyond P are not added and a chain c >= P stays empty.  The partials go to LDS [16][128], lane r of the first wave runs row r's chain
+// over them (128 steps: serial by definition), and all threads read the tile's logits back and write (z - logZ) - log_prior.
+// The logits are kept in memory whatever the width: the result does not depend on where they were held.
+__global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
+                                                          const float *__restrict__ wp, const float *__restrict__ bp,
+                                                          const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
+                                                          const JdMlpDev m, float *out, int out_mode, int layer)
+{
+    extern __shared__ __align__(16) char smem[];
+    const int S = m.stride;
+    float *buf0 = (float *)smem, *buf1 = buf0 + JD_MLP_ROWS * S;      // [16][S] each
+    int *ssrc = (int *)(buf1 + JD_MLP_ROWS * S);                       // [16] the tile's row_src (-1 behind n_rows)
+    float *slz = (float *)(ssrc + JD_MLP_ROWS);                        // [16] logZ
+    float *sp = slz + JD_MLP_ROWS;                                     // [16][JD_MLP_LZ_CHAINS] the partial chains
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = m.n_layers, P = m.width[L - 1];
+    const int n_rt = (n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
+    for (int rt = blockIdx.x; rt < n_rt; rt += gridDim.x) {
+        const int r0 = rt * JD_MLP_ROWS;
+        const int rows = min(JD_MLP_ROWS, n_rows - r0);                // the tile's rows inside the table: nothing behind them is touched
+        __syncthreads();                                               // the previous tile's readers are done
+        if (tid < JD_MLP_ROWS) ssrc[tid] = (tid < rows) ? row_src[r0 + tid] : -1;
+        __syncthreads();
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < JD_MLP_ROWS; ++r) any |= ssrc[r] >= 0;
+        if (!any) {                                                    // (workgroup-uniform)
+            if (out_mode == JD_MLP_OUT_LL)
+                for (int r = 0; r < rows; ++r)
+                    for (int j = tid; j < P; j += 256) out[(size_t)(r0 + r) * P + j] = 0.0f;
+            continue;
+        }
+        {   // the input rows, padded with -0 to the k group
+            const int K = m.in_dim, Kp = (K + 15) & ~15;
+            for (int e = tid; e < JD_MLP_ROWS * Kp; e += 256) {
+                const int r = e / Kp, k = e - r * Kp;
+                const int src = ssrc[r];
+                buf0[r * S + jd_mlp_act_pos(k)] = (k < K) ? (src >= 0 ? feats[(size_t)src * K + k] : 0.0f) : -0.0f;
+            }
+        }
+        __syncthreads();
+        float *in = buf0, *nx = buf1;
+        bool done = false;
+        for (int l = 0; l < L - 1 && !done; ++l) {                     // the hidden layers, as jd_mlp_kernel runs them
+            const int K = l ? m.width[l - 1] : m.in_dim, KG = (K + 15) >> 4, N = m.width[l], n_nt = (N + 15) >> 4;
+            const int act = m.act[l];
+            const float *B = bp + m.b_off[l];
+            const jd_mlp_f4 *W = (const jd_mlp_f4 *)(wp + m.w_off[l]) + lane;
+            const jd_mlp_f4 *ap = (const jd_mlp_f4 *)(in + (lane & 15) * S + 4 * (lane >> 4));
+            for (int nt0 = wid * 2; nt0 < n_nt; nt0 += 8) {                            // (wave-uniform)
+                const bool two = nt0 + 1 < n_nt;
+                const float bias0 = B[nt0 * JD_MLP_NT + (lane & 15)];
+                const float bias1 = two ? B[(nt0 + 1) * JD_MLP_NT + (lane & 15)] : 0.0f;
+                jd_mlp_f4 c0 = {bias0, bias0, bias0, bias0}, c1 = {bias1, bias1, bias1, bias1};
+                const jd_mlp_f4 *w0 = W + (size_t)nt0 * KG * 64;
+                if (two) jd_mlp_chain<true>(ap, w0, w0 + (size_t)KG * 64, KG, c0, c1);
+                else jd_mlp_chain<false>(ap, w0, w0, KG, c0, c1);
+                jd_mlp_store_tile(c0, nt0, N, act, false, nx, S, lane);
+                if (two) jd_mlp_store_tile(c1, nt0 + 1, N, act, false, nx, S, lane);
+            }
+            __syncthreads();
+            if (out_mode == JD_MLP_OUT_LAYER && l == layer) {
+                for (int e = tid; e < JD_MLP_ROWS * N; e += 256) {
+                    const int r = e / N, j = e - r * N;
+                    if (r < rows) out[(size_t)(r0 + r) * N + j] = nx[r * S + jd_mlp_act_pos(j)];
+                }
+                done = true;
+            }
+            float *t = in; in = nx; nx = t;
+        }
+        if (done) continue;
+        {   // the output layer: logits to the tile's rows of out, the partial chains in registers
+            const int K = L > 1 ? m.width[L - 2] : m.in_dim, KG = (K + 15) >> 4, n_nt = (P + 15) >> 4;
+            const float *B = bp + m.b_off[L - 1];
+            const jd_mlp_f4 *W = (const jd_mlp_f4 *)(wp + m.w_off[L - 1]) + lane;
+            const jd_mlp_f4 *ap = (const jd_mlp_f4 *)(in + (lane & 15) * S + 4 * (lane >> 4));
+            const int col = lane & 15, q = lane >> 4;
+            const bool raw = out_mode == JD_MLP_OUT_LAYER;             // (layer = L - 1: the raw logits are the result)
+            float pz0[4] = {LZ, LZ, LZ, LZ}, pz1[4] = {LZ, LZ, LZ, LZ};
+            for (int nt0 = wid * 2; nt0 < n_nt; nt0 += 8) {                            // (wave-uniform)
+                const bool two = nt0 + 1 < n_nt;
+                const int j0 = nt0 * JD_MLP_NT + col, j1 = j0 + JD_MLP_NT;
+                const float bias0 = B[j0];                                             // (biases are padded to the n tile)
+                const float bias1 = two ? B[j1] : 0.0f;
+                jd_mlp_f4 c0 = {bias0, bias0, bias0, bias0}, c1 = {bias1, bias1, bias1, bias1};
+                const jd_mlp_f4 *w0 = W + (size_t)nt0 * KG * 64;
+                if (two) jd_mlp_chain<true>(ap, w0, w0 + (size_t)KG * 64, KG, c0, c1);
+                else jd_mlp_chain<false>(ap, w0, w0, KG, c0, c1);
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int r = 4 * q + reg;
+                    if (j0 < P) {
+                        if (r < rows) out[(size_t)(r0 + r) * P + j0] = c0[reg];
+                        if (!raw) pz0[reg] = jd_log_add(pz0[reg], c0[reg], logtab);
+                    }
+                    if (two && j1 < P) {
+                        if (r < rows) out[(size_t)(r0 + r) * P + j1] = c1[reg];
+                        if (!raw) pz1[reg] = jd_log_add(pz1[reg], c1[reg], logtab);
+                    }
+                }
+            }
+            if (raw) continue;
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                sp[(4 * q + reg) * JD_MLP_LZ_CHAINS + wid * 32 + col] = pz0[reg];
+                sp[(4 * q + reg) * JD_MLP_LZ_CHAINS + wid * 32 + 16 + col] = pz1[reg];
+            }
+        }
+        __syncthreads();                                               // the partials (LDS) are there
+        if (tid < JD_MLP_ROWS) {
+            const int C = min(P, JD_MLP_LZ_CHAINS);
+            float lz = LZ;
+            for (int c = 0; c < C; ++c) lz = jd_log_add(lz, sp[tid * JD_MLP_LZ_CHAINS + c], logtab);
+            slz[tid] = lz;
+        }
+        // This barrier is also what makes the tile's logits - written to `out` by other lanes of this workgroup - visible to the reads
+        // below: __syncthreads() is a workgroup-scope release / acquire fence around s_barrier (every wave waits for its own stores,
+        // vmcnt(0), before it arrives), and a workgroup's waves share one CU and its vector L1, which writes through.  Nothing wider
+        // is needed: no other workgroup reads or writes these rows during the launch.
+        __syncthreads();
+        for (int r = 0; r < rows; ++r) {
+            const float lz = slz[r];
+            const bool unused = ssrc[r] < 0;
+            float *o = out + (size_t)(r0 + r) * P;
+            for (int j = tid; j < P; j += 256) {
+                const float lp = o[j] - lz;
+                o[j] = unused ? 0.0f : (out_mode == JD_MLP_OUT_LL ? lp - log_prior[j] : lp);
             }
         }
     }

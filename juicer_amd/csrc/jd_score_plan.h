@@ -1,5 +1,5 @@
 // jd_score_plan.h - what a scoring launch is, as a function of plain data (no HIP, no models: compiled and tested on the CPU,
-// tests/test_score_plan_cpu.py): which of the scoring kernels (jd_gmm.h, jd_mlp_kernel.h, jd_hybrid_kernel) serves the models and
+// tests/test_score_plan_cpu.py, tests/test_mlp_tied_cpu.py): which of the scoring kernels (jd_gmm.h, jd_mlp_kernel.h, jd_hybrid_kernel) serves the models and
 // the option, its tile, how many tiles the rows make, the grid and the dynamic LDS.  launch_gmm (jd_host_scoring.h) turns the
 // result into the launch; gmm_tiles128_occupancy and check_score_rows ask it for the kernel of a large launch and for the tile's
 // rows; the pipeline's piece bounds (jd_pipe.h: pipe_piece_bounds) take the tile constants and the threshold from here.
@@ -37,13 +37,14 @@ struct ScoreKernels {
     int tile_rows = 0;                    // 0: jd_hybrid_kernel has no tiles
     bool state_tiles = false;             // tiles of rows x states (the GMM kernels); else every row is scored whole
     bool tiles128 = false;                // ... of GMM_ROWS2 rows: two widths, skip lists
-    size_t lds_bytes = 0;                 // (jd_mlp_kernel: the network's, jd_mlp.h: jd_mlp_lds_bytes)
+    size_t lds_bytes = 0;                 // (jd_mlp_kernel / jd_mlp_tied_kernel: the network's, jd_mlp.h: jd_mlp_lds_bytes / jd_mlp_tied_lds_bytes)
     int dp = 0;                           // jd_gmm_fast: jd_fast_dp(D); jd_gmm_kernel<0>: D | 1
 };
-static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast)
+// (tied: jd_am_create_mlp_tied's models among those with a network - jd_mlp_tied_kernel)
+static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast, bool tied = false)
 {
     ScoreKernels k;
-    if (mlp) { k.kernel = k.kernel_small = JD_KERNEL_MLP; k.tile_rows = JD_MLP_ROWS; return k; }
+    if (mlp) { k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED : JD_KERNEL_MLP; k.tile_rows = JD_MLP_ROWS; return k; }
     if (hybrid) { k.kernel = k.kernel_small = JD_KERNEL_HYBRID; return k; }
     k.state_tiles = true;
     k.tiles128 = D == 39 || fast;
@@ -79,6 +80,7 @@ struct ScorePlanIn {
     int max_blocks;                       // > 0 bounds the grid (the kernels stride over the tiles); not jd_hybrid_kernel's
     int used_row_tiles;                   // >= 0: the row tiles that are not skipped (else: all of them)
     bool has_list; int n_rt_list;         // score the listed row tiles only (the kernels of 128-row tiles)
+    bool tied = false;                    // mlp, and the network's outputs are tied states (jd_am_create_mlp_tied): jd_mlp_tied_kernel
 };
 
 enum ScorePlanVerdict {
@@ -90,7 +92,7 @@ enum ScorePlanVerdict {
 struct ScorePlan {                        // (what follows the point a verdict other than ok was reached stays 0)
     ScorePlanVerdict verdict = SCORE_PLAN_OK;
     int kernel = JD_KERNEL_NONE;
-    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel; 64 or 128
+    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel, jd_mlp_tied_kernel; 64 or 128
     int tile_states = 0;                  // 16 or 64; 0: no state tiles
     long long row_tiles = 0, tiles = 0;   // jd_hybrid_kernel: no row tiles, and its tiles are blocks of 256 cells
     unsigned grid = 0;
@@ -102,9 +104,10 @@ static inline ScorePlan score_plan(const ScorePlanIn &in)
 {
     ScorePlan p;
     if (in.n_rows <= 0) { p.verdict = SCORE_PLAN_NOTHING; return p; }
-    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast);
+    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast, in.tied);
     const int max_blocks = in.max_blocks;
-    // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds jd_mlp_kernel's grid)
+    // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds the grid of
+    // jd_mlp_kernel and jd_mlp_tied_kernel)
     if (in.mlp) {
         const int tiles = (in.n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
         p.kernel = k.kernel;

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Time of the neural acoustic models' scoring launch (launch_gmm's MLP branch: jd_mlp_kernel) against the same forward pass in
-torch f32 on the same device (GPU box):  python tools/mlp_bench.py [--iters N] [--warmup W] [--json]
-8192 rows (a batch's table) and 64 rows (a streaming push) of 351 -> 512 -> 512 -> 45, sigmoid.  Device events around each launch
+torch f32 on the same device (GPU box):  python tools/mlp_bench.py [--tied] [--iters N] [--warmup W] [--json]
+8192 rows (a batch's table) and 64 rows (a streaming push) of 351 -> 512 -> 512 -> 45, sigmoid; with --tied, of the tied-state
+networks 351 -> 1024 -> 1024 -> 3000 and 351 -> 1024 -> 1024 -> 8192, sigmoid (jd_am_create_mlp_tied: jd_mlp_tied_kernel).  Device events around each launch
 (jd_debug_mlp_time), the median of `iters` warm launches; torch: events around linear / sigmoid / log_softmax, the same median.
 FLOP = 2 x rows x weights (the products' multiply-adds; activations and the log-softmax are not counted)."""
 import argparse
@@ -18,15 +19,32 @@ from juicer_amd import capi  # noqa: E402
 IN_DIM, WIDTHS = 351, (512, 512, 45)
 
 
-def make(seed=0):
+TIED_WIDTHS = ((1024, 1024, 3000), (1024, 1024, 8192))          # 3000: the tied states of BASELINE configs[1]
+
+
+def make(seed=0, widths=WIDTHS):
     rng = np.random.default_rng(seed)
     layers, k = [], IN_DIM
-    for i, n in enumerate(WIDTHS):
+    for i, n in enumerate(widths):
         layers.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32),
-                       capi.ACT_SIGMOID if i < len(WIDTHS) - 1 else capi.ACT_LINEAR))
+                       capi.ACT_SIGMOID if i < len(widths) - 1 else capi.ACT_LINEAR))
         k = n
-    pr = rng.uniform(0.5, 2.0, WIDTHS[-1])
+    pr = rng.uniform(0.5, 2.0, widths[-1])
     return layers, (pr / pr.sum()).astype(np.float32)
+
+
+def flat_topology(n_gmm):
+    """GMM models of n_gmm tied states, one 3-state HMM each: the least topology that carries n_gmm outputs"""
+    from juicer_amd import synth
+    hg = np.full((n_gmm, 3), -1, np.int32)
+    hg[:, 1] = np.arange(n_gmm)
+    tp = np.zeros((1, 3, 3), np.float32)
+    tp[0, 0, 1], tp[0, 1, 1], tp[0, 1, 2] = 1.0, 0.5, 0.5
+    am = synth.SynthAM(D=1, n_gmm=n_gmm, max_mix=1, n_mix=np.ones(n_gmm, np.int32), weight=np.ones((n_gmm, 1), np.float32),
+                       mean=np.zeros((n_gmm, 1, 1), np.float32), var=np.ones((n_gmm, 1, 1), np.float32), n_hmm=n_gmm, max_n=3,
+                       hmm_nstates=np.full(n_gmm, 3, np.int32), hmm_gmm=hg, hmm_tm=np.zeros(n_gmm, np.int32), n_tm=1,
+                       tm_nstates=np.full(1, 3, np.int32), transp=tp)
+    return capi.Models.from_htk(am)
 
 
 def torch_ms(layers, log_prior, x, warmup, iters):
@@ -61,29 +79,33 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--tied", action="store_true", help="the tied-state networks (jd_mlp_tied_kernel)")
     args = ap.parse_args()
     assert args.iters >= 20, "the median of at least 20 warm launches"
     if not torch.cuda.is_available():
         sys.exit("mlp_bench: no GPU (a time is a measurement on the device)")
     torch.backends.cuda.matmul.allow_tf32 = False
-    layers, pr = make()
-    models = capi.Models.from_mlp(pr, 3, layers)
-    weights = sum(w.size for w, _, _ in layers)
     res = []
-    for rows in (8192, 64):
-        x = np.random.default_rng(rows).standard_normal((rows, IN_DIM)).astype(np.float32)
-        ms = float(np.median(models.mlp_time(x, warmup=args.warmup, iters=args.iters)))
-        t_ms, t_out = torch_ms(layers, np.log(pr), x, args.warmup, args.iters)
-        ours = models.score_frames(x)
-        flop = 2.0 * rows * weights
-        res.append(dict(rows=rows, ms=ms, tflops=flop / ms / 1e9, torch_ms=t_ms, torch_tflops=flop / t_ms / 1e9, ratio=ms / t_ms,
-                        max_abs_diff_vs_torch=float(np.abs(ours - t_out).max())))
+    for widths in (TIED_WIDTHS if args.tied else (WIDTHS,)):
+        layers, pr = make(widths=widths)
+        models = capi.Models.from_mlp_tied(flat_topology(widths[-1]), pr, layers) if args.tied else capi.Models.from_mlp(pr, 3, layers)
+        weights = sum(w.size for w, _, _ in layers)
+        for rows in (8192, 64):
+            x = np.random.default_rng(rows).standard_normal((rows, IN_DIM)).astype(np.float32)
+            ms = float(np.median(models.mlp_time(x, warmup=args.warmup, iters=args.iters)))
+            t_ms, t_out = torch_ms(layers, np.log(pr), x, args.warmup, args.iters)
+            ours = models.score_frames(x)
+            flop = 2.0 * rows * weights
+            res.append(dict(net="-".join(str(v) for v in (IN_DIM,) + tuple(widths)), rows=rows, iters=args.iters, ms=ms, tflops=flop / ms / 1e9,
+                            torch_ms=t_ms, torch_tflops=flop / t_ms / 1e9, ratio=ms / t_ms,
+                            max_abs_diff_vs_torch=float(np.abs(ours - t_out).max())))
     if args.json:
         print(json.dumps(res))
     else:
         for r in res:
-            print("%5d rows: jd_mlp_kernel %.4f ms (%.2f TFLOP/s)   torch f32 %.4f ms (%.2f TFLOP/s)   ratio %.2f   max |diff| %.2e"
-                  % (r["rows"], r["ms"], r["tflops"], r["torch_ms"], r["torch_tflops"], r["ratio"], r["max_abs_diff_vs_torch"]))
+            print("%s, %5d rows: %s %.4f ms (%.2f TFLOP/s)   torch f32 %.4f ms (%.2f TFLOP/s)   ratio %.2f   max |diff| %.2e"
+                  % (r["net"], r["rows"], "jd_mlp_tied_kernel" if args.tied else "jd_mlp_kernel", r["ms"], r["tflops"], r["torch_ms"],
+                     r["torch_tflops"], r["ratio"], r["max_abs_diff_vs_torch"]))
 
 
 if __name__ == "__main__":
