@@ -304,6 +304,28 @@ int jd_am_create_mlp_tied(jd_am **out, const jd_am *topology, const float *prior
                           const int32_t *width, const int32_t *act, const float *const *weight, const float *const *bias);
 int jd_am_load_mlp_tied(jd_am **out, const jd_am *topology, const char *path);
 
+/* bf16 neural models: reduced precision is a property of the MODEL, not a decoder mode.  jd_am_mlp_to_bf16 makes, from models with
+ * a network (plain or tied; `src` is only read), new models of the same kind - same topology, priors, names and limits - whose
+ * weights are src's rounded to bf16 (round to nearest even); biases and log priors stay f32.  Every entry point serves them with no
+ * mode set (batches, scoring ahead, streaming pushes, jd_streams_push, the broker, jd_multi_*, the C++ adapter), on their own kernels
+ * (bf16 matrix instructions, 32-row tiles, half the weight bytes); what hybrid models refuse they refuse, JD_SCORE_FAST included.
+ * Converting a bf16 model again gives an equal model.  JD_EINVAL for a NULL argument, JD_ESTATE for models without a network.
+ * Numerics (csrc/jd_mlp_bf16.h defines them; jd_am_mlp_forward_host and jd_debug_mlp_activations(on_device = 0) run the host twin):
+ * every layer's input - the caller's features too - is rounded to bf16; a linear output is (float)(bias + sum_k x[k] w[k]) with the
+ * sum in double; RELU / SIGMOID as above in f32; a hidden activation is rounded to bf16 (jd_debug_mlp_activations returns that
+ * value: the low 16 bits of each float are zero); the logits stay f32, and logZ, z - logZ and - log(prior) are exactly those above.
+ * The DEVICE is held to the twin by a bound in the linear part - |device - double sum| <= 2 (K + 1) 2^-23 (|bias| + sum_k |x[k] w[k]|):
+ * the order and rounding of the sums inside a bf16 matrix instruction are not documented - and bit for bit in the rest: the log
+ * posteriors are the logZ chain over the device's own logits, a hidden activation handed on is the bf16 value
+ * jd_debug_mlp_activations(on_device = 1) returns, and a row's result depends on that row alone, whatever the batch or the launch
+ * (pushes equal batches).  jd_am_save_mlp on a bf16 model writes an ordinary JMLP file (version 1 or 2) holding the rounded
+ * weights as f32: loading it gives f32 models, converting those gives back equal bf16 models.  jd_am_mlp_info is unchanged.
+ * jd_am_mlp_precision: JD_MLP_F32, JD_MLP_BF16, or -1 for models without a network. */
+#define JD_MLP_F32  0
+#define JD_MLP_BF16 1
+int jd_am_mlp_to_bf16(const jd_am *src, jd_am **out);
+int32_t jd_am_mlp_precision(const jd_am *a);
+
 /* Juicer's binary model cache "<mmf>.bin" (JMBI), preferred by juicer.cpp:778-784:
  * HTKModels::readBinary (HTKModels.cpp:1110-1233) + HTKFlatModels::init.  The derived values in
  * the file (sumLogVarPlusNObsLog2Pi, logCompWeights, transition logProbs) are used as stored. */
@@ -877,8 +899,9 @@ int jd_debug_log_add(int32_t device, int32_t variant, const float *x, const floa
  * tiles that overlap; a tile list for hybrid models (launch_gmm would ignore it); and, launch_gmm's own refusal, a tile list for exact
  * scoring of D != 39.  Tile rows: 128 at D = 39
  * and with JD_SCORE_FAST, 64 for exact scoring of any other D, none for hybrid models (which ignore skip_unused; those with a network,
- * jd_am_create_mlp and jd_am_create_mlp_tied, included: the 16-row tiles of jd_mlp_kernel / jd_mlp_tied_kernel are their own affair,
- * and rows with row_src = -1 are written as 0.0f).
+ * jd_am_create_mlp and jd_am_create_mlp_tied, included: the 16-row tiles of jd_mlp_kernel / jd_mlp_tied_kernel - 32-row tiles of
+ * jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel for jd_am_mlp_to_bf16's models - are their own affair, and rows with row_src = -1 are
+ * written as 0.0f).
  * tests/test_gpu_score_rows.py holds every cell of the buffer to tests/score_rows_cases.py. */
 typedef enum jd_score_kernel {
     JD_KERNEL_NONE = 0,            /* nothing was launched                                  */
@@ -891,7 +914,9 @@ typedef enum jd_score_kernel {
     JD_KERNEL_GMM_FAST_64 = 7,     /* jd_gmm_fast<64>                                       */
     JD_KERNEL_HYBRID = 8,          /* jd_hybrid_kernel                                      */
     JD_KERNEL_MLP = 9,             /* jd_mlp_kernel: jd_am_create_mlp's models, 16-row tiles */
-    JD_KERNEL_MLP_TIED = 10        /* jd_mlp_tied_kernel: jd_am_create_mlp_tied's, 16-row tiles */
+    JD_KERNEL_MLP_TIED = 10,       /* jd_mlp_tied_kernel: jd_am_create_mlp_tied's, 16-row tiles */
+    JD_KERNEL_MLP_BF16 = 11,       /* jd_mlp_bf16_kernel: jd_am_mlp_to_bf16 of jd_am_create_mlp's models, 32-row tiles */
+    JD_KERNEL_MLP_TIED_BF16 = 12   /* jd_mlp_tied_bf16_kernel: jd_am_mlp_to_bf16 of jd_am_create_mlp_tied's, 32-row tiles */
 } jd_score_kernel;
 int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
                         int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,

@@ -148,6 +148,7 @@ EXPORTS = [
     "jd_am_create_mlp", "jd_am_mlp_info", "jd_am_save_mlp", "jd_am_load_mlp", "jd_am_mlp_forward", "jd_am_mlp_forward_host",
     "jd_debug_mlp_activations", "jd_debug_mlp_time",
     "jd_am_create_hybrid_tied", "jd_am_create_mlp_tied", "jd_am_load_mlp_tied",
+    "jd_am_mlp_to_bf16", "jd_am_mlp_precision",
 ]
 
 _lib = None
@@ -563,6 +564,18 @@ class Models:
     def save_mlp(self, path):
         _check(lib().jd_am_save_mlp(self.h, os.fsencode(path)))
 
+    def to_bf16(self) -> "Models":
+        """New models of the same kind whose network weights are these models' rounded to bf16 (jd_am_mlp_to_bf16): every entry
+        point serves them, on the bf16 kernels, with no mode set."""
+        h = C.c_void_p()
+        _check(lib().jd_am_mlp_to_bf16(self.h, C.byref(h)))
+        return type(self)(h)
+
+    @property
+    def mlp_precision(self) -> int:
+        """MLP_F32, MLP_BF16, or -1 for models without a network (jd_am_mlp_precision)."""
+        return int(lib().jd_am_mlp_precision(self.h))
+
     def mlp_info(self):
         """(in_dim, [width], [act]) of the network (jd_am_mlp_info)."""
         d, n = C.c_int32(0), C.c_int32(0)
@@ -656,6 +669,9 @@ def debug_log1pe(d, variant: int, device: int = -1):
  KERNEL_GMM_FAST_64, KERNEL_HYBRID) = range(9)
 KERNEL_MLP = 9                     # jd_mlp_kernel (Models.from_mlp); beside KERNEL_NAMES, the list of the kernels of tests/score_rows_cases.py
 KERNEL_MLP_TIED = 10               # jd_mlp_tied_kernel (Models.from_mlp_tied)
+KERNEL_MLP_BF16 = 11               # jd_mlp_bf16_kernel (Models.to_bf16 of from_mlp's models)
+KERNEL_MLP_TIED_BF16 = 12          # jd_mlp_tied_bf16_kernel (... of from_mlp_tied's)
+MLP_F32, MLP_BF16 = 0, 1           # Models.mlp_precision
 KERNEL_NAMES = ["none", "jd_gmm_kernel<0>", "jd_gmm_kernel39<16>", "jd_gmm_kernel39<64>", "jd_gmm_fast39<16>", "jd_gmm_fast39<64>",
                 "jd_gmm_fast<16>", "jd_gmm_fast<64>", "jd_hybrid_kernel"]
 

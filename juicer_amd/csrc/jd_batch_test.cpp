@@ -171,6 +171,7 @@ int main(int argc, char **argv)
 {
     const char *fsm = 0, *insyms = 0, *outsyms = 0, *amf = 0, *mmf = 0, *list = 0;
     const char *mlpf = 0, *monoList = 0;                                     // -mlpFName: a JMLP file (jd_am_load_mlp); its phones' names
+    bool mlpBf16 = false;                                                    // -mlpBf16: the network in bf16 (jd_am_mlp_to_bf16, after loading)
     const char *mlpTied = 0;                                                 // -mlpTiedFName: a JMLP version 2 file (jd_am_load_mlp_tied) beside a models file
     const char *gramFsm = 0, *gramInSyms = 0, *gramOutSyms = 0;              // juicer.cpp:128-130: separate C.L and G
     float mainBeam = 0, startBeam = 0, endBeam = 0, wordBeam = 0, lmScale = 1.0f, insPen = 0.0f;
@@ -196,6 +197,7 @@ int main(int argc, char **argv)
         else if (a == "-htkModelsFName") mmf = nxt();
         else if (a == "-mlpFName") mlpf = nxt();
         else if (a == "-mlpTiedFName") mlpTied = nxt();
+        else if (a == "-mlpBf16") mlpBf16 = true;
         else if (a == "-inputFName") list = nxt(); else if (a == "-mainBeam") mainBeam = (float)atof(nxt());
         else if (a == "-phoneStartBeam") startBeam = (float)atof(nxt()); else if (a == "-phoneEndBeam") endBeam = (float)atof(nxt());
         else if (a == "-wordEmitBeam") wordBeam = (float)atof(nxt()); else if (a == "-maxHyps") maxHyps = atoi(nxt());
@@ -226,6 +228,8 @@ int main(int argc, char **argv)
                         "       [-mlpTiedFName M.jmlp   (beside -htkModelsFName or -modelsFName: a tied-state network, jd_am_save_mlp's file of a tied model -\n"
                         "        the models file gives the HMMs, their state tying and their names, the network one output per tied state; the inputs are\n"
                         "        feature vectors of the network's input size)]\n"
+                        "       [-mlpBf16   (beside -mlpFName or -mlpTiedFName: the network's weights rounded to bf16 after loading, jd_am_mlp_to_bf16 -\n"
+                        "        the bf16 kernels score)]\n"
                         "       [-phoneEndBeam b] [-wordEmitBeam b] [-maxHyps n] [-lmScaleFactor s] [-insPenalty p] [-batch n] [-perFrameAdapter]\n"
                         "       [-outputFormat ref|trans|mlf|xmlf|verbose] [-writeBinaryFiles] [-refFName REF] [-removeSentMarks]\n"
                         "       [-sentStartWord W] [-sentEndWord W] [-outSymsFName SYMS] [-outputFName stdout|stderr|FILE]\n"
@@ -243,6 +247,11 @@ int main(int argc, char **argv)
     };
     if (mlpTied && !amf && !mmf) {                                             // (a tied network holds no topology; -mlpFName is none)
         fprintf(stderr, "jd_batch_test: -mlpTiedFName needs a models file beside it (-htkModelsFName or -modelsFName): the HMMs and their state tying\n");
+        usage();
+        return 1;
+    }
+    if (mlpBf16 && !mlpf && !mlpTied) {
+        fprintf(stderr, "jd_batch_test: -mlpBf16 needs a network file beside it (-mlpFName or -mlpTiedFName)\n");
         usage();
         return 1;
     }
@@ -305,6 +314,12 @@ int main(int argc, char **argv)
         am = 0;
         if (jd_am_load_mlp_tied(&am, top, mlpTied)) die("jd_am_load_mlp_tied");
         jd_am_destroy(top);
+    }
+    if (mlpBf16) {
+        jd_am *f32 = am;
+        am = 0;
+        if (jd_am_mlp_to_bf16(f32, &am)) die("jd_am_mlp_to_bf16");
+        jd_am_destroy(f32);
     }
     const int D = jd_am_vec_size(am);
     std::vector<std::string> hmmNames;         // PhoneLookup::getModelStr (juicer.cpp:606-621): the models' names

@@ -95,6 +95,7 @@ __device__ __forceinline__ int rank_in(unsigned long long bal)
 // ------------------------------------------------------------------- scoring kernels
 #include "jd_gmm.h"
 #include "jd_mlp_kernel.h"      // neural acoustic models: the fused forward pass (jd_mlp.h: the network as data, the host twin)
+#include "jd_mlp_bf16_kernel.h" // ... and of their bf16 form (jd_mlp_bf16.h: the contract, the packing, the twin)
 
 // --------------------------------------------------------------- search kernels
 #include "jd_search.h"

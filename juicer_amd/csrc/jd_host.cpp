@@ -572,6 +572,23 @@ extern "C" int jd_am_mlp_info(const jd_am *a, int32_t *in_dim, int32_t *n_layers
     }
     return JD_OK;
 }
+// bf16 models (jd_mlp_bf16.h): a copy of src - topology, priors, names - whose weights are rounded and packed for the bf16 kernels
+extern "C" int jd_am_mlp_to_bf16(const jd_am *src, jd_am **out)
+{
+    if (!src || !out) return jd_fail(JD_EINVAL, "jd_am_mlp_to_bf16: null argument");
+    if (!src->mlp) return jd_fail(JD_ESTATE, "jd_am_mlp_to_bf16: these models hold no network (jd_am_create_mlp / jd_am_load_mlp make the ones that do)");
+    jd_am *a = new jd_am(*src);
+    a->mlp_precision = JD_MLP_BF16;
+    for (float &w : a->mlp_w) w = jd_bf16_round(w);
+    jd_mlp_bf16_pack(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), a->mlp_wq, a->mlp_bp);
+    a->mlp_wp.clear(); a->mlp_wp.shrink_to_fit();
+    *out = a;
+    return JD_OK;
+}
+extern "C" int32_t jd_am_mlp_precision(const jd_am *a)
+{
+    return (a && a->mlp) ? a->mlp_precision : -1;
+}
 // the JMLP file (jd_mlp.h holds the layout)
 extern "C" int jd_am_save_mlp(const jd_am *a, const char *path)
 {

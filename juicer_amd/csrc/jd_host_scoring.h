@@ -23,6 +23,7 @@ struct AmDevBuf {
     int fast = 0;                   // launch_gmm scores with jd_gmm_fast39 (D = 39) / jd_gmm_fast
     float *log_prior = nullptr;
     float *mlp_w = nullptr, *mlp_b = nullptr;   // jd_am_create_mlp's models: the packed network (jd_mlp_pack)
+    unsigned short *mlp_wq = nullptr;           // jd_am_mlp_to_bf16's: the weights packed as bf16 (jd_mlp_bf16_pack; mlp_w is null, mlp_b padded to 32)
     JdLogTab *logtab = nullptr;
     int device = -1;
 };
@@ -54,7 +55,14 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
         HIPCHK(hipMalloc(&b.log_prior, a->log_prior.size() * sizeof(float)));
         HIPCHK(hipMemcpy(b.log_prior, a->log_prior.data(), a->log_prior.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (a->mlp) {
+    if (a->mlp && a->mlp_precision == JD_MLP_BF16) {
+        HIPCHK(hipMalloc(&b.mlp_wq, a->mlp_wq.size() * sizeof(unsigned short)));
+        HIPCHK(hipMalloc(&b.mlp_b, a->mlp_bp.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(b.mlp_wq, a->mlp_wq.data(), a->mlp_wq.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.mlp_b, a->mlp_bp.data(), a->mlp_bp.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_BF16_LDS_MAX));
+        else HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_BF16_LDS_MAX));
+    } else if (a->mlp) {
         HIPCHK(hipMalloc(&b.mlp_w, a->mlp_wp.size() * sizeof(float)));
         HIPCHK(hipMalloc(&b.mlp_b, a->mlp_bp.size() * sizeof(float)));
         HIPCHK(hipMemcpy(b.mlp_w, a->mlp_wp.data(), a->mlp_wp.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -98,6 +106,7 @@ static void free_am_gmm(AmDevBuf &b)
     if (b.log_prior) (void)hipFree(b.log_prior);
     if (b.mlp_w) (void)hipFree(b.mlp_w);
     if (b.mlp_b) (void)hipFree(b.mlp_b);
+    if (b.mlp_wq) (void)hipFree(b.mlp_wq);
     b = AmDevBuf();
 }
 
@@ -112,13 +121,23 @@ static ScorePlan gmm_plan(const jd_am *a, const AmDevBuf &b, int n_rows, int max
                           int n_rt_list = 0)
 {
     return score_plan(ScorePlanIn{a->D, a->n_gmm, a->hybrid, a->mlp, am_fast(b), n_rows, max_blocks, used_row_tiles, has_list, n_rt_list,
-                                  a->mlp && a->tied});
+                                  a->mlp && a->tied, a->mlp && a->mlp_precision == JD_MLP_BF16});
 }
 
 // jd_mlp_kernel - for tied models jd_mlp_tied_kernel - on rows [0, n_rows), on the plan's grid: d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
 static void launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
                        unsigned grid, int out_mode, int layer)
 {
+    if (a->mlp_precision == JD_MLP_BF16) {                             // (jd_am_mlp_to_bf16's models: the kernels of 32-row tiles)
+        const JdMlpDev m = jd_mlp_bf16_dev(a->mlp_desc);
+        if (a->tied)
+            hipLaunchKernelGGL(jd_mlp_tied_bf16_kernel, dim3(grid), dim3(256), jd_mlp_tied_bf16_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_wq,
+                               b.mlp_b, b.log_prior, b.logtab, m, d_out, out_mode, layer);
+        else
+            hipLaunchKernelGGL(jd_mlp_bf16_kernel, dim3(grid), dim3(256), jd_mlp_bf16_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_wq, b.mlp_b,
+                               b.log_prior, b.logtab, m, d_out, out_mode, layer);
+        return;
+    }
     if (a->tied) {
         const JdMlpDev m = jd_mlp_dev(a->mlp_desc, true);
         hipLaunchKernelGGL(jd_mlp_tied_kernel, dim3(grid), dim3(256), jd_mlp_tied_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b,
@@ -151,6 +170,8 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
 #define GMM_ARGS(par) par, b.det, b.n_mix, a->n_gmm, a->max_mix
     switch (p.kernel) {
     case JD_KERNEL_MLP:
+    case JD_KERNEL_MLP_BF16:
+    case JD_KERNEL_MLP_TIED_BF16:
     case JD_KERNEL_MLP_TIED: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0); break;
     case JD_KERNEL_HYBRID: GMM_LAUNCH(jd_hybrid_kernel, b.log_prior, a->n_gmm, d_ll); break;
     case JD_KERNEL_GMM_FAST39_16: GMM_LAUNCH(jd_gmm_fast39<GMM_GT_SMALL>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
@@ -380,7 +401,8 @@ extern "C" int jd_am_mlp_forward_host(const jd_am *a, const float *frames, int32
     const int rc = mlp_args(a, frames, n_frames, logpost, "jd_am_mlp_forward_host");
     if (rc) return rc;
     const JdMlpHostMath math;
-    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
+    if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
+    else jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
     return JD_OK;
 }
 extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t on_device, const float *frames, int32_t n_frames, int32_t layer,
@@ -392,7 +414,8 @@ extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t 
         return jd_fail(JD_EINVAL, "jd_debug_mlp_activations: layer %d outside [0, %d)", layer, a->mlp_desc.n_layers);
     if (on_device) return mlp_on_device(a, device, frames, n_frames, JD_MLP_OUT_LAYER, layer, out);
     const JdMlpHostMath math;
-    jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
+    if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
+    else jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
     return JD_OK;
 }
 

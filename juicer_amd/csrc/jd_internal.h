@@ -10,6 +10,7 @@
 
 #include "juicer_amd.h"
 #include "jd_mlp.h"             // neural acoustic models: the network as plain data, its packing, the host twin
+#include "jd_mlp_bf16.h"        // ... and their bf16 form: the rounding, its packing, its twin
 
 #define JD_MAXN 8          // max HMM states (incl. entry/exit) the search kernel handles
 
@@ -75,6 +76,11 @@ struct jd_am {
     JdMlpDesc mlp_desc;
     int32_t mlp_states_per_model = 0;
     std::vector<float> mlp_prior, mlp_w, mlp_b, mlp_wp, mlp_bp;
+    // bf16 models (jd_am_mlp_to_bf16, jd_mlp_bf16.h): mlp_w holds the ROUNDED weights as f32 - the twin, the file writer and
+    // jd_am_mlp_info need no second path - mlp_wq them packed as bf16 for jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel (mlp_wp is
+    // empty), mlp_bp the biases padded to its n tile pairs
+    int32_t mlp_precision = JD_MLP_F32;
+    std::vector<uint16_t> mlp_wq;
     // HMM names (HTKModels::getHMMName, for phone output): the MMF's ~h names / JMBI's JMHM names; empty when the models
     // were built from arrays
     std::vector<std::string> hmm_name;            // [n_hmm] or empty

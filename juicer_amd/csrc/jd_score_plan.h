@@ -11,6 +11,7 @@
 
 #include "../../include/juicer_amd.h"   // JD_KERNEL_* (by its place: jd_pipe.h's includers search csrc alone)
 #include "jd_mlp.h"            // JD_MLP_ROWS: the rows of jd_mlp_kernel's tile
+#include "jd_mlp_bf16.h"       // JD_MLP_BF16_ROWS: the rows of jd_mlp_bf16_kernel's tile, and its LDS
 
 #define GMM_ROWS 64             // stream-frames per tile of jd_gmm_kernel<0> (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -40,10 +41,18 @@ struct ScoreKernels {
     size_t lds_bytes = 0;                 // (jd_mlp_kernel / jd_mlp_tied_kernel: the network's, jd_mlp.h: jd_mlp_lds_bytes / jd_mlp_tied_lds_bytes)
     int dp = 0;                           // jd_gmm_fast: jd_fast_dp(D); jd_gmm_kernel<0>: D | 1
 };
-// (tied: jd_am_create_mlp_tied's models among those with a network - jd_mlp_tied_kernel)
-static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast, bool tied = false)
+// (tied: jd_am_create_mlp_tied's models among those with a network - jd_mlp_tied_kernel; bf16: jd_am_mlp_to_bf16's among those -
+// jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel, tiles of JD_MLP_BF16_ROWS rows; lds_bytes is then the bound the kernel is told,
+// JD_MLP_BF16_LDS_MAX / JD_MLP_TIED_BF16_LDS_MAX, and the launch takes the network's own, jd_mlp_bf16.h)
+static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast, bool tied = false, bool bf16 = false)
 {
     ScoreKernels k;
+    if (mlp && bf16) {
+        k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED_BF16 : JD_KERNEL_MLP_BF16;
+        k.tile_rows = JD_MLP_BF16_ROWS;
+        k.lds_bytes = tied ? JD_MLP_TIED_BF16_LDS_MAX : JD_MLP_BF16_LDS_MAX;
+        return k;
+    }
     if (mlp) { k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED : JD_KERNEL_MLP; k.tile_rows = JD_MLP_ROWS; return k; }
     if (hybrid) { k.kernel = k.kernel_small = JD_KERNEL_HYBRID; return k; }
     k.state_tiles = true;
@@ -81,6 +90,7 @@ struct ScorePlanIn {
     int used_row_tiles;                   // >= 0: the row tiles that are not skipped (else: all of them)
     bool has_list; int n_rt_list;         // score the listed row tiles only (the kernels of 128-row tiles)
     bool tied = false;                    // mlp, and the network's outputs are tied states (jd_am_create_mlp_tied): jd_mlp_tied_kernel
+    bool bf16 = false;                    // mlp, and the model is a bf16 one (jd_am_mlp_to_bf16): jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel
 };
 
 enum ScorePlanVerdict {
@@ -92,7 +102,7 @@ enum ScorePlanVerdict {
 struct ScorePlan {                        // (what follows the point a verdict other than ok was reached stays 0)
     ScorePlanVerdict verdict = SCORE_PLAN_OK;
     int kernel = JD_KERNEL_NONE;
-    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel, jd_mlp_tied_kernel; 64 or 128
+    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel, jd_mlp_tied_kernel; 32: their bf16 kernels; 64 or 128
     int tile_states = 0;                  // 16 or 64; 0: no state tiles
     long long row_tiles = 0, tiles = 0;   // jd_hybrid_kernel: no row tiles, and its tiles are blocks of 256 cells
     unsigned grid = 0;
@@ -104,12 +114,12 @@ static inline ScorePlan score_plan(const ScorePlanIn &in)
 {
     ScorePlan p;
     if (in.n_rows <= 0) { p.verdict = SCORE_PLAN_NOTHING; return p; }
-    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast, in.tied);
+    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast, in.tied, in.bf16);
     const int max_blocks = in.max_blocks;
     // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds the grid of
-    // jd_mlp_kernel and jd_mlp_tied_kernel)
+    // jd_mlp_kernel and jd_mlp_tied_kernel and of their bf16 kernels)
     if (in.mlp) {
-        const int tiles = (in.n_rows + JD_MLP_ROWS - 1) / JD_MLP_ROWS;
+        const int tiles = (in.n_rows + k.tile_rows - 1) / k.tile_rows;
         p.kernel = k.kernel;
         p.row_tiles = p.tiles = tiles;
         p.grid = (unsigned)((max_blocks > 0 && tiles > max_blocks) ? max_blocks : tiles);

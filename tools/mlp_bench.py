@@ -1,10 +1,13 @@
 #!/usr/bin/env python
 """Time of the neural acoustic models' scoring launch (launch_gmm's MLP branch: jd_mlp_kernel) against the same forward pass in
-torch f32 on the same device (GPU box):  python tools/mlp_bench.py [--tied] [--iters N] [--warmup W] [--json]
+torch f32 on the same device (GPU box):  python tools/mlp_bench.py [--tied] [--bf16 [--runs R]] [--iters N] [--warmup W] [--json]
 8192 rows (a batch's table) and 64 rows (a streaming push) of 351 -> 512 -> 512 -> 45, sigmoid; with --tied, of the tied-state
 networks 351 -> 1024 -> 1024 -> 3000 and 351 -> 1024 -> 1024 -> 8192, sigmoid (jd_am_create_mlp_tied: jd_mlp_tied_kernel).  Device events around each launch
 (jd_debug_mlp_time), the median of `iters` warm launches; torch: events around linear / sigmoid / log_softmax, the same median.
-FLOP = 2 x rows x weights (the products' multiply-adds; activations and the log-softmax are not counted)."""
+FLOP = 2 x rows x weights (the products' multiply-adds; activations and the log-softmax are not counted).
+--bf16: beside them the bf16 model of the same network (jd_am_mlp_to_bf16: jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel) and torch in
+bf16 - the f32 and the bf16 kernel alternate, R runs each (at least 3); the median over the runs' medians, and their spread
+(least .. greatest), are reported."""
 import argparse
 import json
 import os
@@ -47,11 +50,15 @@ def flat_topology(n_gmm):
     return capi.Models.from_htk(am)
 
 
-def torch_ms(layers, log_prior, x, warmup, iters):
+def flop_of(rows, weights):
+    return 2.0 * rows * weights
+
+
+def torch_ms(layers, log_prior, x, warmup, iters, dtype=torch.float32):
     dev = torch.device("cuda")
-    ws = [(torch.from_numpy(w).to(dev), torch.from_numpy(b).to(dev)) for w, b, _ in layers]
+    ws = [(torch.from_numpy(w).to(dev).to(dtype), torch.from_numpy(b).to(dev).to(dtype)) for w, b, _ in layers]
     lp = torch.from_numpy(log_prior).to(dev)
-    xd = torch.from_numpy(x).to(dev)
+    xd = torch.from_numpy(x).to(dev).to(dtype)
 
     def fwd():
         a = xd
@@ -59,7 +66,7 @@ def torch_ms(layers, log_prior, x, warmup, iters):
             a = torch.nn.functional.linear(a, w, b)
             if i < len(ws) - 1:
                 a = torch.sigmoid(a)
-        return torch.log_softmax(a, dim=1) - lp
+        return torch.log_softmax(a.float(), dim=1) - lp
 
     ms = []
     with torch.no_grad():
@@ -80,7 +87,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--tied", action="store_true", help="the tied-state networks (jd_mlp_tied_kernel)")
+    ap.add_argument("--bf16", action="store_true", help="also the bf16 model of the same network and torch in bf16")
+    ap.add_argument("--runs", type=int, default=3, help="--bf16: runs of each kernel, alternating")
     args = ap.parse_args()
+    assert args.runs >= 3, "at least three runs each"
     assert args.iters >= 20, "the median of at least 20 warm launches"
     if not torch.cuda.is_available():
         sys.exit("mlp_bench: no GPU (a time is a measurement on the device)")
@@ -96,11 +106,35 @@ def main():
             t_ms, t_out = torch_ms(layers, np.log(pr), x, args.warmup, args.iters)
             ours = models.score_frames(x)
             flop = 2.0 * rows * weights
+            if args.bf16:
+                q = models.to_bf16()
+                f32_runs, bf16_runs = [ms], []
+                for r in range(args.runs):
+                    if r:
+                        f32_runs.append(float(np.median(models.mlp_time(x, warmup=args.warmup, iters=args.iters))))
+                    bf16_runs.append(float(np.median(q.mlp_time(x, warmup=args.warmup, iters=args.iters))))
+                tb_ms, tb_out = torch_ms(layers, np.log(pr), x, args.warmup, args.iters, torch.bfloat16)
+                res.append(dict(net="-".join(str(v) for v in (IN_DIM,) + tuple(widths)), rows=rows, iters=args.iters, runs=args.runs,
+                                f32_ms=float(np.median(f32_runs)), f32_spread=[min(f32_runs), max(f32_runs)],
+                                bf16_ms=float(np.median(bf16_runs)), bf16_spread=[min(bf16_runs), max(bf16_runs)],
+                                bf16_tflops=flop_of(rows, weights) / float(np.median(bf16_runs)) / 1e9,
+                                speedup=float(np.median(f32_runs)) / float(np.median(bf16_runs)), torch_f32_ms=t_ms, torch_bf16_ms=tb_ms,
+                                ratio_vs_torch_bf16=float(np.median(bf16_runs)) / tb_ms,
+                                max_abs_diff_bf16_vs_f32=float(np.abs(q.score_frames(x) - ours).max()),
+                                max_abs_diff_torch_bf16_vs_f32=float(np.abs(tb_out - t_out).max())))
+                continue
             res.append(dict(net="-".join(str(v) for v in (IN_DIM,) + tuple(widths)), rows=rows, iters=args.iters, ms=ms, tflops=flop / ms / 1e9,
                             torch_ms=t_ms, torch_tflops=flop / t_ms / 1e9, ratio=ms / t_ms,
                             max_abs_diff_vs_torch=float(np.abs(ours - t_out).max())))
     if args.json:
         print(json.dumps(res))
+    elif args.bf16:
+        for r in res:
+            print("%s, %5d rows: f32 kernel %.4f ms [%.4f .. %.4f]   bf16 kernel %.4f ms [%.4f .. %.4f] (%.2f TFLOP/s)   f32 / bf16 %.2f   "
+                  "torch f32 %.4f ms, bf16 %.4f ms   bf16 kernel / torch bf16 %.2f   max |bf16 - f32| %.2e (torch's %.2e)"
+                  % (r["net"], r["rows"], r["f32_ms"], *r["f32_spread"], r["bf16_ms"], *r["bf16_spread"], r["bf16_tflops"], r["speedup"],
+                     r["torch_f32_ms"], r["torch_bf16_ms"], r["ratio_vs_torch_bf16"], r["max_abs_diff_bf16_vs_f32"],
+                     r["max_abs_diff_torch_bf16_vs_f32"]))
     else:
         for r in res:
             print("%s, %5d rows: %s %.4f ms (%.2f TFLOP/s)   torch f32 %.4f ms (%.2f TFLOP/s)   ratio %.2f   max |diff| %.2e"
