@@ -326,6 +326,32 @@ int jd_am_load_mlp_tied(jd_am **out, const jd_am *topology, const char *path);
 int jd_am_mlp_to_bf16(const jd_am *src, jd_am **out);
 int32_t jd_am_mlp_precision(const jd_am *a);
 
+/* SPLICED neural models: the window of frames that a hybrid network takes is gathered on the device, in the input stage of the
+ * network's kernel.  Splicing is a property of the MODEL, like bf16: jd_am_mlp_splice makes, from models with a network (plain or
+ * tied, f32 or bf16; `src` is only read), new models with the same network, topology, priors and precision whose feature vectors
+ * are single FRAMES of D = in_dim / C values, C = left + right + 1.  The network's input for frame t of an utterance of T frames is
+ *   x[c D + d] = frame[clamp(t + c - left, 0, T - 1)][d]     c = 0 .. C - 1
+ * - the oldest frame first, the first and the last frame repeated at the edges - and after the gather the arithmetic is the parent's:
+ * a spliced model on raw frames gives, BIT FOR BIT (host twin and device, f32 and bf16), what its parent gives on the same frames
+ * spliced by the caller.  Splicing and jd_am_mlp_to_bf16 commute.  (0, 0) is accepted and behaves like the parent.
+ * JD_EINVAL, naming the cause: models without a network, a negative left or right, an in_dim that is no multiple of C, models
+ * that are spliced already.
+ * jd_am_vec_size and jd_dec_info report D; jd_am_mlp_info still reports the network's in_dim.  jd_am_mlp_context: (left, right),
+ * (0, 0) for an unspliced network, JD_EINVAL for models without one.  jd_am_save_mlp writes the ordinary JMLP file of the network
+ * (version 1 or 2): the format has no context field, the caller splices again after loading.
+ * What serves them: jd_am_mlp_forward(_host), jd_debug_mlp_activations, jd_debug_mlp_time and jd_am_score_frames (the frames of a
+ * call are ONE utterance), jd_debug_score_rows_span, jd_decode_batch(_device) in the default flow and in JD_FLOW_SERIAL with or
+ * without jd_dec_prefetch_scores (an utterance is frames [ustart, ustart + ulen) of the buffer: windows clamp to it), jd_multi_*,
+ * and jd_stream_init / _push / _finish for one stream, hence the C++ adapter.  A live stream holds back the last `right` frames
+ * pushed: a frame is scored and searched once `right` more have arrived (a push may search nothing), jd_stream_finish searches the
+ * rest with the right edge clamped, and every count of frames the streaming calls report - chunks, PARTIAL_DECODING's schedule,
+ * times in traces, jd_streams_best / _final - is one of SEARCHED frames.  jd_stream_held_frames: frames pushed and not yet searched
+ * (0 for every other kind of model).
+ * Refused with JD_EINVAL, naming splicing: jd_streams_push with a stream of such a decoder, jd_broker_create on one, and
+ * jd_debug_score_rows (jd_debug_score_rows_span takes the spans); JD_FLOW_RESIDENT refuses them as it does every hybrid model. */
+int jd_am_mlp_splice(const jd_am *src, int32_t left, int32_t right, jd_am **out);
+int jd_am_mlp_context(const jd_am *a, int32_t *left, int32_t *right);
+
 /* Juicer's binary model cache "<mmf>.bin" (JMBI), preferred by juicer.cpp:778-784:
  * HTKModels::readBinary (HTKModels.cpp:1110-1233) + HTKFlatModels::init.  The derived values in
  * the file (sumLogVarPlusNObsLog2Pi, logCompWeights, transition logProbs) are used as stored. */
@@ -439,6 +465,9 @@ int jd_stream_init(jd_dec *d, int32_t s);
  * (DecoderSingleTest.cpp:267-295) carry no information beyond the frames
  * themselves, so the adapter folds them into pushes. */
 int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames);
+/* A stream of SPLICED models (jd_am_mlp_splice) holds the last `right` frames back until their windows are there: *held = the frames
+ * pushed to stream s and not yet searched (jd_stream_finish searches them); 0 for every other kind of model. */
+int jd_stream_held_frames(jd_dec *d, int32_t s, int32_t *held);
 /* IDecoder::finish() (Decoder.h:28). */
 int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out);
 /* jd_stream_push for several streams at once (each at most once per call): ONE scoring launch and ONE search launch
@@ -916,11 +945,23 @@ typedef enum jd_score_kernel {
     JD_KERNEL_MLP = 9,             /* jd_mlp_kernel: jd_am_create_mlp's models, 16-row tiles */
     JD_KERNEL_MLP_TIED = 10,       /* jd_mlp_tied_kernel: jd_am_create_mlp_tied's, 16-row tiles */
     JD_KERNEL_MLP_BF16 = 11,       /* jd_mlp_bf16_kernel: jd_am_mlp_to_bf16 of jd_am_create_mlp's models, 32-row tiles */
-    JD_KERNEL_MLP_TIED_BF16 = 12   /* jd_mlp_tied_bf16_kernel: jd_am_mlp_to_bf16 of jd_am_create_mlp_tied's, 32-row tiles */
+    JD_KERNEL_MLP_TIED_BF16 = 12,  /* jd_mlp_tied_bf16_kernel: jd_am_mlp_to_bf16 of jd_am_create_mlp_tied's, 32-row tiles */
+    JD_KERNEL_MLP_SPLICED = 13,            /* jd_mlp_spliced_kernel: jd_am_mlp_splice of a model that runs JD_KERNEL_MLP */
+    JD_KERNEL_MLP_TIED_SPLICED = 14,       /* jd_mlp_tied_spliced_kernel: ... JD_KERNEL_MLP_TIED */
+    JD_KERNEL_MLP_BF16_SPLICED = 15,       /* jd_mlp_bf16_spliced_kernel: ... JD_KERNEL_MLP_BF16 */
+    JD_KERNEL_MLP_TIED_BF16_SPLICED = 16   /* jd_mlp_tied_bf16_spliced_kernel: ... JD_KERNEL_MLP_TIED_BF16 */
 } jd_score_kernel;
 int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
                         int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
                         int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid);
+/* ... for SPLICED models (jd_am_mlp_splice), whose rows carry a span beside row_src: row r's window is the frames
+ * clamp(row_src[r] + c - left, row_lo[r], row_hi[r]), c = 0 .. left + right - its utterance's bounds in `frames` (n_frames x D raw
+ * frames).  Each row_lo / row_hi entry of a used row is checked against [0, n_frames), and row_lo <= row_hi; the other arguments and
+ * refusals are jd_debug_score_rows', which itself refuses spliced models and names this call.  JD_EINVAL for any other model. */
+int jd_debug_score_rows_span(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                             const int32_t *row_lo, const int32_t *row_hi, int32_t n_rows, int32_t skip_unused, int32_t max_blocks,
+                             int32_t used_row_tiles, const int32_t *rt_base, int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel,
+                             int32_t *grid);
 /* ... and of the histogram pruning (Histogram.cpp:64-100 / 134-158).  jd_debug_hist_bin: the search kernels' bin of s[i]
  * (jd_hist_bin: s rounded half away from zero in double, minus hist_min), -1 when it falls below hist_min, JD_EHIST above
  * hist_max; device -1 runs the host twin; every s[i] must lie in (-2^31, 2^31) (no NaN, no infinity: JD_EINVAL).  jd_debug_hist_threshold: the kernels' one-wave calcThresh (hist_threshold) for

@@ -20,7 +20,7 @@ BATCH_TEST = os.path.join(HERE, "jd_batch_test")
 BATCH_SRC = os.path.join(CSRC, "jd_batch_test.cpp")
 SOURCES = [os.path.join(CSRC, "jd_host.cpp"), os.path.join(CSRC, "jd_device.hip"), os.path.join(CSRC, "jd_multi.cpp"),
            os.path.join(CSRC, "jd_compose.hip"), os.path.join(CSRC, "jd_broker.cpp")]
-HEADERS_EXTRA = [os.path.join(CSRC, f) for f in ("jd_search.h", "jd_prep.h", "jd_lazy.h", "jd_labelsets.h", "jd_gmm.h", "jd_gc.h", "jd_resident.h", "jd_slot.h", "jd_host_resident.h", "jd_host_scoring.h", "jd_score_plan.h", "jd_plan.h", "jd_arena.h", "jd_ahead.h", "jd_pipe.h", "jd_push.h", "jd_client.h", "jd_host_launch.h", "jd_host_stream.h", "jd_host_paths.h", "jd_paths.h", "jd_best.h", "jd_final.h", "jd_mlp.h", "jd_mlp_kernel.h", "jd_mlp_bf16.h", "jd_mlp_bf16_kernel.h")]
+HEADERS_EXTRA = [os.path.join(CSRC, f) for f in ("jd_search.h", "jd_prep.h", "jd_lazy.h", "jd_labelsets.h", "jd_gmm.h", "jd_gc.h", "jd_resident.h", "jd_slot.h", "jd_host_resident.h", "jd_host_scoring.h", "jd_score_plan.h", "jd_plan.h", "jd_arena.h", "jd_ahead.h", "jd_pipe.h", "jd_push.h", "jd_client.h", "jd_host_launch.h", "jd_host_stream.h", "jd_host_paths.h", "jd_paths.h", "jd_best.h", "jd_final.h", "jd_mlp.h", "jd_mlp_kernel.h", "jd_mlp_bf16.h", "jd_mlp_bf16_kernel.h", "jd_splice.h")]
 HEADERS = [os.path.join(CSRC, "jd_internal.h"), os.path.join(ROOT, "include", "juicer_amd.h"),
            os.path.join(ROOT, "include", "juicer_amd_decoder.hpp"), BATCH_SRC]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

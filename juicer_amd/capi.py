@@ -149,6 +149,7 @@ EXPORTS = [
     "jd_debug_mlp_activations", "jd_debug_mlp_time",
     "jd_am_create_hybrid_tied", "jd_am_create_mlp_tied", "jd_am_load_mlp_tied",
     "jd_am_mlp_to_bf16", "jd_am_mlp_precision",
+    "jd_am_mlp_splice", "jd_am_mlp_context", "jd_debug_score_rows_span", "jd_stream_held_frames",
 ]
 
 _lib = None
@@ -571,6 +572,20 @@ class Models:
         _check(lib().jd_am_mlp_to_bf16(self.h, C.byref(h)))
         return type(self)(h)
 
+    def splice(self, left: int, right: int) -> "Models":
+        """New models with the same network, topology, priors and precision whose feature vectors are single frames of
+        in_dim / (left + right + 1) values: the window of left + 1 + right frames is gathered on the device (jd_am_mlp_splice)."""
+        h = C.c_void_p()
+        _check(lib().jd_am_mlp_splice(self.h, C.c_int32(left), C.c_int32(right), C.byref(h)))
+        return type(self)(h)
+
+    @property
+    def mlp_context(self):
+        """(left, right) of spliced models, (0, 0) of an unspliced network (jd_am_mlp_context)."""
+        left, right = C.c_int32(0), C.c_int32(0)
+        _check(lib().jd_am_mlp_context(self.h, C.byref(left), C.byref(right)))
+        return left.value, right.value
+
     @property
     def mlp_precision(self) -> int:
         """MLP_F32, MLP_BF16, or -1 for models without a network (jd_am_mlp_precision)."""
@@ -671,16 +686,17 @@ KERNEL_MLP = 9                     # jd_mlp_kernel (Models.from_mlp); beside KER
 KERNEL_MLP_TIED = 10               # jd_mlp_tied_kernel (Models.from_mlp_tied)
 KERNEL_MLP_BF16 = 11               # jd_mlp_bf16_kernel (Models.to_bf16 of from_mlp's models)
 KERNEL_MLP_TIED_BF16 = 12          # jd_mlp_tied_bf16_kernel (... of from_mlp_tied's)
+KERNEL_MLP_SPLICED, KERNEL_MLP_TIED_SPLICED, KERNEL_MLP_BF16_SPLICED, KERNEL_MLP_TIED_BF16_SPLICED = 13, 14, 15, 16   # Models.splice of the four
 MLP_F32, MLP_BF16 = 0, 1           # Models.mlp_precision
 KERNEL_NAMES = ["none", "jd_gmm_kernel<0>", "jd_gmm_kernel39<16>", "jd_gmm_kernel39<64>", "jd_gmm_fast39<16>", "jd_gmm_fast39<64>",
                 "jd_gmm_fast<16>", "jd_gmm_fast<64>", "jd_hybrid_kernel"]
 
 
 def debug_score_rows(models: "Models", frames, row_src, out, mode: int = SCORE_EXACT, skip_unused: int = 0, max_blocks: int = 0,
-                     used_row_tiles: int = -1, rt_base=None, guard_rows: int = 0, device: int = 0):
+                     used_row_tiles: int = -1, rt_base=None, guard_rows: int = 0, device: int = 0, row_lo=None, row_hi=None):
     """One launch of the scoring kernels with the decoder's own launch arguments (jd_debug_score_rows): out is the caller's
     PREFILLED [(guard_rows + n_rows + guard_rows), n_gmm] buffer.  Returns (the buffer as the launch left it - a copy -, the
-    kernel that ran (KERNEL_*), its grid)."""
+    kernel that ran (KERNEL_*), its grid).  row_lo / row_hi: the rows' spans, for spliced models (jd_debug_score_rows_span)."""
     x, src = _f32(frames), _i32(row_src)
     buf = np.array(out, dtype=np.float32, order="C", copy=True)
     n_rows = src.shape[0]
@@ -688,6 +704,15 @@ def debug_score_rows(models: "Models", frames, row_src, out, mode: int = SCORE_E
     assert x.shape[0] == 0 or x.shape[1] == models.vec_size
     lst = None if rt_base is None else _i32(rt_base)
     k, g = C.c_int32(0), C.c_int32(0)
+    if row_lo is not None or row_hi is not None:
+        lo, hi = _i32(row_lo), _i32(row_hi)
+        assert lo.shape == src.shape and hi.shape == src.shape
+        _check(lib().jd_debug_score_rows_span(models.h, C.c_int32(device), C.c_int32(mode), _p(x, C.c_float), C.c_int32(x.shape[0]),
+                                              _p(src, C.c_int32), _p(lo, C.c_int32), _p(hi, C.c_int32), C.c_int32(n_rows),
+                                              C.c_int32(skip_unused), C.c_int32(max_blocks), C.c_int32(used_row_tiles),
+                                              None if lst is None else _p(lst, C.c_int32), C.c_int32(0 if lst is None else lst.shape[0]),
+                                              C.c_int32(guard_rows), _p(buf, C.c_float), C.byref(k), C.byref(g)))
+        return buf, k.value, g.value
     _check(lib().jd_debug_score_rows(models.h, C.c_int32(device), C.c_int32(mode), _p(x, C.c_float), C.c_int32(x.shape[0]),
                                      _p(src, C.c_int32), C.c_int32(n_rows), C.c_int32(skip_unused), C.c_int32(max_blocks),
                                      C.c_int32(used_row_tiles), None if lst is None else _p(lst, C.c_int32),
@@ -760,6 +785,13 @@ class Decoder:
     def stream_push(self, s: int, frames):
         x = _f32(frames)
         _check(lib().jd_stream_push(self.h, C.c_int32(s), _p(x, C.c_float), C.c_int32(x.shape[0])))
+
+    def stream_held_frames(self, s: int = 0) -> int:
+        """Frames pushed to stream s and not yet searched: a stream of spliced models (Models.splice) holds the last `right`
+        frames back; 0 for every other kind of model (jd_stream_held_frames)."""
+        n = C.c_int32(0)
+        _check(lib().jd_stream_held_frames(self.h, C.c_int32(s), C.byref(n)))
+        return n.value
 
     def stream_finish(self, s: int = 0) -> Hyp:
         h = CHyp()

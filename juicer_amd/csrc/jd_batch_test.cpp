@@ -173,6 +173,7 @@ int main(int argc, char **argv)
     const char *mlpf = 0, *monoList = 0;                                     // -mlpFName: a JMLP file (jd_am_load_mlp); its phones' names
     bool mlpBf16 = false;                                                    // -mlpBf16: the network in bf16 (jd_am_mlp_to_bf16, after loading)
     const char *mlpTied = 0;                                                 // -mlpTiedFName: a JMLP version 2 file (jd_am_load_mlp_tied) beside a models file
+    const char *mlpSplice = 0;                                               // -mlpSplice L,R: the window gathered on the device (jd_am_mlp_splice, after loading, before -mlpBf16)
     const char *gramFsm = 0, *gramInSyms = 0, *gramOutSyms = 0;              // juicer.cpp:128-130: separate C.L and G
     float mainBeam = 0, startBeam = 0, endBeam = 0, wordBeam = 0, lmScale = 1.0f, insPen = 0.0f;
     int maxHyps = 0, framesPerSec = 100, device = 0, batch = 64, useAdapter = 0, writeBinaryFiles = 0, nDevices = 0, pushing = 0, lazy = 0, nThreads = 0, lookaheadSets = 0;
@@ -198,6 +199,7 @@ int main(int argc, char **argv)
         else if (a == "-mlpFName") mlpf = nxt();
         else if (a == "-mlpTiedFName") mlpTied = nxt();
         else if (a == "-mlpBf16") mlpBf16 = true;
+        else if (a == "-mlpSplice") mlpSplice = nxt();
         else if (a == "-inputFName") list = nxt(); else if (a == "-mainBeam") mainBeam = (float)atof(nxt());
         else if (a == "-phoneStartBeam") startBeam = (float)atof(nxt()); else if (a == "-phoneEndBeam") endBeam = (float)atof(nxt());
         else if (a == "-wordEmitBeam") wordBeam = (float)atof(nxt()); else if (a == "-maxHyps") maxHyps = atoi(nxt());
@@ -230,6 +232,9 @@ int main(int argc, char **argv)
                         "        feature vectors of the network's input size)]\n"
                         "       [-mlpBf16   (beside -mlpFName or -mlpTiedFName: the network's weights rounded to bf16 after loading, jd_am_mlp_to_bf16 -\n"
                         "        the bf16 kernels score)]\n"
+                        "       [-mlpSplice L,R   (beside -mlpFName or -mlpTiedFName: the network's window of L + 1 + R frames is gathered on the device,\n"
+                        "        jd_am_mlp_splice - the inputs are then RAW vectors of in_dim / (L + R + 1) values, one per frame; applied after loading and\n"
+                        "        before -mlpBf16; not with -threads)]\n"
                         "       [-phoneEndBeam b] [-wordEmitBeam b] [-maxHyps n] [-lmScaleFactor s] [-insPenalty p] [-batch n] [-perFrameAdapter]\n"
                         "       [-outputFormat ref|trans|mlf|xmlf|verbose] [-writeBinaryFiles] [-refFName REF] [-removeSentMarks]\n"
                         "       [-sentStartWord W] [-sentEndWord W] [-outSymsFName SYMS] [-outputFName stdout|stderr|FILE]\n"
@@ -254,6 +259,20 @@ int main(int argc, char **argv)
         fprintf(stderr, "jd_batch_test: -mlpBf16 needs a network file beside it (-mlpFName or -mlpTiedFName)\n");
         usage();
         return 1;
+    }
+    int spliceL = 0, spliceR = 0;
+    if (mlpSplice) {
+        char tail = 0;
+        if (!mlpf && !mlpTied) {
+            fprintf(stderr, "jd_batch_test: -mlpSplice needs a network file beside it (-mlpFName or -mlpTiedFName)\n");
+            usage();
+            return 1;
+        }
+        if (sscanf(mlpSplice, "%d,%d%c", &spliceL, &spliceR, &tail) != 2) {
+            fprintf(stderr, "jd_batch_test: -mlpSplice %s: two frame counts, L,R\n", mlpSplice);
+            usage();
+            return 1;
+        }
     }
     if (!fsm || (!amf && !mmf && !mlpf) || !list) {
         usage();
@@ -314,6 +333,12 @@ int main(int argc, char **argv)
         am = 0;
         if (jd_am_load_mlp_tied(&am, top, mlpTied)) die("jd_am_load_mlp_tied");
         jd_am_destroy(top);
+    }
+    if (mlpSplice) {
+        jd_am *parent = am;
+        am = 0;
+        if (jd_am_mlp_splice(parent, spliceL, spliceR, &am)) die("jd_am_mlp_splice");
+        jd_am_destroy(parent);
     }
     if (mlpBf16) {
         jd_am *f32 = am;

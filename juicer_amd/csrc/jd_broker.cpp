@@ -331,6 +331,9 @@ extern "C" int jd_broker_create(jd_broker **out, jd_dec *dec, int32_t n_clients)
     int rc = jd_dec_info(dec, &ms, &D);
     if (rc) return rc;
     if (n_clients > ms) return jd_fail(JD_EINVAL, "jd_broker_create: %d clients on a decoder of %d streams", n_clients, ms);
+    if (jd_dec_spliced && jd_dec_spliced(dec))
+        return jd_fail(JD_EINVAL, "jd_broker_create: the decoder's models are spliced (jd_am_mlp_splice), and splicing is served one stream at a time "
+                       "(jd_stream_push), not by a broker");
     int32_t level = 0;
     rc = jd_dec_get_output_level(dec, &level);
     if (rc) return rc;

@@ -274,6 +274,9 @@ struct jd_dec {
     float *d_ll[3] = {nullptr, nullptr, nullptr};
     size_t ll_cap = 0;                    // floats per table
     int *d_row_src[3] = {nullptr, nullptr, nullptr}; size_t row_src_cap[3] = {0, 0, 0};   // row -> source frame tables, one per likelihood table
+    // spliced models (jd_splice.h): the rows' spans beside them, and the host's copy a transfer reads (else null / empty)
+    JdSpan *d_row_span[3] = {nullptr, nullptr, nullptr}; size_t row_span_cap[3] = {0, 0, 0};
+    std::vector<JdSpan> h_row_span[3];
     int *d_T = nullptr;
     hipStream_t s_gmm = nullptr, s_search = nullptr;
     unsigned *h_park = nullptr; int *d_park = nullptr;   // jd_park_kernel's words (host-mapped state; arrival counts and quotas by XCD)
@@ -412,6 +415,7 @@ extern "C" void jd_dec_destroy(jd_dec *d)
     d->pf_q.clear();
     if (d->h_resident) (void)hipHostFree(d->h_resident);
     if (d->d_push) (void)hipFree(d->d_push);
+    for (int i = 0; i < 3; ++i) if (d->d_row_span[i]) (void)hipFree(d->d_row_span[i]);
     if (d->h_stage) (void)hipHostFree(d->h_stage);
     if (d->h_pmany) (void)hipHostFree(d->h_pmany);
     if (d->h_best) (void)hipHostFree(d->h_best);
@@ -1076,7 +1080,22 @@ static int ensure_rows(jd_dec *d, int i, size_t rows)
         HIPCHK(hipMalloc(&d->d_row_src[i], rows * sizeof(int)));
         d->row_src_cap[i] = rows;
     }
+    if (d->am->mlp_spliced && rows > d->row_span_cap[i]) {
+        if (d->d_row_span[i]) (void)hipFree(d->d_row_span[i]);
+        d->d_row_span[i] = nullptr; d->row_span_cap[i] = 0;
+        HIPCHK(hipMalloc(&d->d_row_span[i], rows * sizeof(JdSpan)));
+        d->row_span_cap[i] = rows;
+    }
     return JD_OK;
+}
+// a spliced model's spans beside row table i (from entry `at`); null for every other model: what launch_gmm takes
+static const JdSpan *row_span(const jd_dec *d, int i, size_t at = 0) { return d->am->mlp_spliced ? d->d_row_span[i] + at : nullptr; }
+// ... of a wave's plan, sent behind its row table on stream st (splice_wave_spans; nothing to do for any other model)
+static hipError_t send_wave_spans(jd_dec *d, int i, const WavePlan &P, const int64_t *ustart, hipStream_t st)
+{
+    if (!d->am->mlp_spliced) return hipSuccess;
+    splice_wave_spans(P, ustart, &d->h_row_span[i]);
+    return hipMemcpyAsync(d->d_row_span[i], d->h_row_span[i].data(), P.n_rows_all * sizeof(JdSpan), hipMemcpyHostToDevice, st);
 }
 // table i holds `floats`, its row table `rows` entries (grown, never shrunk)
 static int ensure_table(jd_dec *d, int i, size_t floats, size_t rows)
@@ -1119,8 +1138,10 @@ static int pf_launch(jd_dec *d)
         if (ensure_rows(d, buf, F.plan.n_rows_all) != JD_OK) { (void)hipGetLastError(); break; }
         if (hipEventCreate(&F.ev0) != hipSuccess || hipEventCreate(&F.ev1) != hipSuccess) { (void)hipGetLastError(); F.drop_events(); break; }
         if (hipMemcpyAsync(d->d_row_src[buf], F.plan.row_src.data(), F.plan.n_rows_all * sizeof(int), hipMemcpyHostToDevice, d->s_gmm) != hipSuccess ||
+            send_wave_spans(d, buf, F.plan, F.ustart.data(), d->s_gmm) != hipSuccess ||
             hipEventRecord(F.ev0, d->s_gmm) != hipSuccess ||
-            launch_gmm(d->am, d->amb, F.feats, d->d_row_src[buf], F.plan.chunk_rows[0], d->d_ll[buf], d->s_gmm, 0, true) != JD_OK ||
+            launch_gmm(d->am, d->amb, F.feats, d->d_row_src[buf], F.plan.chunk_rows[0], d->d_ll[buf], d->s_gmm, 0, true, -1, nullptr, 0, nullptr,
+                       row_span(d, buf)) != JD_OK ||
             hipEventRecord(F.ev1, d->s_gmm) != hipSuccess) {
             (void)hipGetLastError(); F.drop_events(); break;
         }
@@ -1268,7 +1289,7 @@ static int wave_score_chunk(jd_dec *d, Wave &W, int c)
     // registers, so its workgroups start as the search's clusters finish - they fill the tail)
     if (P.chunk_rows[(size_t)c] == 0) { HIPCHK(hipEventRecord(W.ge.v[(size_t)c], d->s_gmm)); return JD_OK; }
     const int r = launch_gmm(d->am, d->amb, W.feats, d->d_row_src[W.b0] + P.chunk_row0[(size_t)c], P.chunk_rows[(size_t)c], d->d_ll[W.b0 ^ (c & 1)],
-                             d->s_gmm, 0, true);
+                             d->s_gmm, 0, true, -1, nullptr, 0, nullptr, row_span(d, W.b0, P.chunk_row0[(size_t)c]));
     if (r) return r;
     HIPCHK(hipEventRecord(W.ge.v[(size_t)c], d->s_gmm));
     return JD_OK;
@@ -1357,8 +1378,10 @@ static int decode_wave(jd_dec *d, int nb, const float *d_feats, const int64_t *u
     // the caller's features may have been produced asynchronously on its stream (NULL = the
     // default stream): the decoder's own streams are non-blocking, so order against it explicitly
     HIPCHK(hipStreamSynchronize(user_stream));
-    if (!W.claim.mine)
+    if (!W.claim.mine) {
         HIPCHK(hipMemcpyAsync(d->d_row_src[W.b0], P.row_src.data(), P.n_rows_all * sizeof(int), hipMemcpyHostToDevice, d->s_gmm));
+        HIPCHK(send_wave_spans(d, W.b0, P, ustart, d->s_gmm));
+    }
     rc = wave_start_or_resume(d, W);
     if (rc) return rc;
     W.gs.v.assign((size_t)n_chunks, nullptr); W.ge.v.assign((size_t)n_chunks, nullptr);
@@ -1811,6 +1834,7 @@ extern "C" int jd_dec_debug_cells(jd_dec *d, int32_t enable, int64_t *cells_read
     return JD_OK;
 }
 
+int jd_dec_spliced(const jd_dec *d) { return d && d->am->mlp_spliced ? 1 : 0; }
 extern "C" int jd_dec_info(const jd_dec *d, int32_t *max_streams, int32_t *vec_size)
 {
     if (!d) return jd_fail(JD_EINVAL, "jd_dec_info: null");

@@ -589,6 +589,30 @@ extern "C" int32_t jd_am_mlp_precision(const jd_am *a)
 {
     return (a && a->mlp) ? a->mlp_precision : -1;
 }
+// spliced models (jd_splice.h): a copy of src - network, topology, priors, precision - whose feature vectors are single frames
+extern "C" int jd_am_mlp_splice(const jd_am *src, int32_t left, int32_t right, jd_am **out)
+{
+    if (!src || !out) return jd_fail(JD_EINVAL, "jd_am_mlp_splice: null argument");
+    if (!src->mlp) return jd_fail(JD_EINVAL, "jd_am_mlp_splice: these models hold no network (jd_am_create_mlp / jd_am_load_mlp make the ones that do)");
+    if (src->mlp_spliced)
+        return jd_fail(JD_EINVAL, "jd_am_mlp_splice: these models are spliced already, with context (%d, %d): splice their parent", src->mlp_left, src->mlp_right);
+    char why[200];
+    int D = 0;
+    if (jd_splice_check(src->mlp_desc.in_dim, left, right, &D, why, sizeof why)) return jd_fail(JD_EINVAL, "jd_am_mlp_splice: %s", why);
+    jd_am *a = new jd_am(*src);
+    a->mlp_spliced = true; a->mlp_left = left; a->mlp_right = right;
+    a->D = D;
+    *out = a;
+    return JD_OK;
+}
+extern "C" int jd_am_mlp_context(const jd_am *a, int32_t *left, int32_t *right)
+{
+    if (!a) return jd_fail(JD_EINVAL, "jd_am_mlp_context: null");
+    if (!a->mlp) return jd_fail(JD_EINVAL, "jd_am_mlp_context: these models hold no network (jd_am_create_mlp / jd_am_load_mlp make the ones that do)");
+    if (left) *left = a->mlp_left;
+    if (right) *right = a->mlp_right;
+    return JD_OK;
+}
 // the JMLP file (jd_mlp.h holds the layout)
 extern "C" int jd_am_save_mlp(const jd_am *a, const char *path)
 {

@@ -1,7 +1,8 @@
 // jd_host_scoring.h - the host side of the companion scoring kernels (included by jd_device.hip): the model parameters on the device,
 // launch_gmm - the launch of what jd_score_plan.h plans: which kernel (jd_gmm_kernel39, the default; jd_gmm_fast39 / jd_gmm_fast,
 // jd_dec_set_scoring's option; the generic and the hybrid kernel; jd_mlp_kernel for the models of jd_am_create_mlp, jd_mlp_tied_kernel for
-// those of jd_am_create_mlp_tied), its tiles, grid and
+// those of jd_am_create_mlp_tied, their bf16 kernels, and the spliced flavours of the four for jd_am_mlp_splice's models, whose rows carry
+// a span beside row_src - jd_splice.h), its tiles, grid and
 // LDS are decided there, on plain data, and tested on the CPU - jd_am_score_frames, jd_am_mlp_forward.  Reference: HTKFlatModels::calcGMMOutput + logAdd, src/HTKFlatModels.cpp:190-293.
 #pragma once
 
@@ -60,7 +61,10 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
         HIPCHK(hipMalloc(&b.mlp_b, a->mlp_bp.size() * sizeof(float)));
         HIPCHK(hipMemcpy(b.mlp_wq, a->mlp_wq.data(), a->mlp_wq.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b.mlp_b, a->mlp_bp.data(), a->mlp_bp.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_BF16_LDS_MAX));
+        const int span_b = (int)jd_splice_lds_bytes(JD_MLP_BF16_ROWS);
+        if (a->mlp_spliced && a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_bf16_spliced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_BF16_LDS_MAX + span_b));
+        else if (a->mlp_spliced) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_bf16_spliced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_BF16_LDS_MAX + span_b));
+        else if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_BF16_LDS_MAX));
         else HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_BF16_LDS_MAX));
     } else if (a->mlp) {
         HIPCHK(hipMalloc(&b.mlp_w, a->mlp_wp.size() * sizeof(float)));
@@ -68,8 +72,13 @@ static int upload_am_gmm(const jd_am *a, AmDevBuf &b)
         HIPCHK(hipMemcpy(b.mlp_w, a->mlp_wp.data(), a->mlp_wp.size() * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b.mlp_b, a->mlp_bp.data(), a->mlp_bp.size() * sizeof(float), hipMemcpyHostToDevice));
         // (above 64 KB of dynamic LDS a kernel has to be told; per device, and the same value every time)
-        HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_LDS_MAX));
-        if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_LDS_MAX));
+        const int span_b = (int)jd_splice_lds_bytes(JD_MLP_ROWS);
+        if (a->mlp_spliced && a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_spliced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_LDS_MAX + span_b));
+        else if (a->mlp_spliced) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_spliced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_LDS_MAX + span_b));
+        else {
+            HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_LDS_MAX));
+            if (a->tied) HIPCHK(hipFuncSetAttribute((const void *)jd_mlp_tied_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)JD_MLP_TIED_LDS_MAX));
+        }
     }
     return JD_OK;
 }
@@ -121,32 +130,38 @@ static ScorePlan gmm_plan(const jd_am *a, const AmDevBuf &b, int n_rows, int max
                           int n_rt_list = 0)
 {
     return score_plan(ScorePlanIn{a->D, a->n_gmm, a->hybrid, a->mlp, am_fast(b), n_rows, max_blocks, used_row_tiles, has_list, n_rt_list,
-                                  a->mlp && a->tied, a->mlp && a->mlp_precision == JD_MLP_BF16});
+                                  a->mlp && a->tied, a->mlp && a->mlp_precision == JD_MLP_BF16, a->mlp && a->mlp_spliced});
 }
 
 // jd_mlp_kernel - for tied models jd_mlp_tied_kernel - on rows [0, n_rows), on the plan's grid: d_out as out_mode says (JD_MLP_OUT_LL: the likelihood table)
+// d_span: the rows' spans (jd_splice.h) for a spliced model - its kernels are the spliced flavours of the same four - and null for every other
 static void launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows, float *d_out, hipStream_t st,
-                       unsigned grid, int out_mode, int layer)
+                       unsigned grid, int out_mode, int layer, const JdSpan *d_span)
 {
+    const bool spl = a->mlp_spliced;
     if (a->mlp_precision == JD_MLP_BF16) {                             // (jd_am_mlp_to_bf16's models: the kernels of 32-row tiles)
-        const JdMlpDev m = jd_mlp_bf16_dev(a->mlp_desc);
-        if (a->tied)
-            hipLaunchKernelGGL(jd_mlp_tied_bf16_kernel, dim3(grid), dim3(256), jd_mlp_tied_bf16_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_wq,
-                               b.mlp_b, b.log_prior, b.logtab, m, d_out, out_mode, layer);
-        else
-            hipLaunchKernelGGL(jd_mlp_bf16_kernel, dim3(grid), dim3(256), jd_mlp_bf16_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_wq, b.mlp_b,
-                               b.log_prior, b.logtab, m, d_out, out_mode, layer);
+        JdMlpDev m = jd_mlp_bf16_dev(a->mlp_desc);
+        if (spl) m = jd_splice_dev(m, a->mlp_left, a->mlp_right);
+        const size_t span_b = spl ? jd_splice_lds_bytes(JD_MLP_BF16_ROWS) : 0;
+        const auto kernel = a->tied ? (spl ? jd_mlp_tied_bf16_spliced_kernel : jd_mlp_tied_bf16_kernel) : (spl ? jd_mlp_bf16_spliced_kernel : jd_mlp_bf16_kernel);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), (a->tied ? jd_mlp_tied_bf16_lds_bytes(m) : jd_mlp_bf16_lds_bytes(m)) + span_b, st, d_feats, d_row_src,
+                           n_rows, b.mlp_wq, b.mlp_b, b.log_prior, b.logtab, m, d_out, out_mode, layer, d_span);
         return;
     }
+    const size_t span_b = spl ? jd_splice_lds_bytes(JD_MLP_ROWS) : 0;
     if (a->tied) {
-        const JdMlpDev m = jd_mlp_dev(a->mlp_desc, true);
-        hipLaunchKernelGGL(jd_mlp_tied_kernel, dim3(grid), dim3(256), jd_mlp_tied_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b,
-                           b.log_prior, b.logtab, m, d_out, out_mode, layer);
+        JdMlpDev m = jd_mlp_dev(a->mlp_desc, true);
+        if (spl) m = jd_splice_dev(m, a->mlp_left, a->mlp_right);
+        const auto kernel = spl ? jd_mlp_tied_spliced_kernel : jd_mlp_tied_kernel;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), jd_mlp_tied_lds_bytes(m) + span_b, st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
+                           b.logtab, m, d_out, out_mode, layer, d_span);
         return;
     }
-    const JdMlpDev m = jd_mlp_dev(a->mlp_desc);
-    hipLaunchKernelGGL(jd_mlp_kernel, dim3(grid), dim3(256), jd_mlp_lds_bytes(m), st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior,
-                       b.logtab, m, d_out, out_mode, layer);
+    JdMlpDev m = jd_mlp_dev(a->mlp_desc);
+    if (spl) m = jd_splice_dev(m, a->mlp_left, a->mlp_right);
+    const auto kernel = spl ? jd_mlp_spliced_kernel : jd_mlp_kernel;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), jd_mlp_lds_bytes(m) + span_b, st, d_feats, d_row_src, n_rows, b.mlp_w, b.mlp_b, b.log_prior, b.logtab,
+                       m, d_out, out_mode, layer, d_span);
 }
 
 // max_blocks > 0 bounds the grid (the kernel strides over the tiles): next to the search, a
@@ -158,11 +173,14 @@ static void launch_mlp(const jd_am *a, const AmDevBuf &b, const float *d_feats, 
 // rt_base (device, or null) / n_rt_list: score these row tiles (first rows) only - the kernels of 128-row tiles (D = 39; jd_gmm_fast)
 // info (or null): what was launched (jd_debug_score_rows)
 // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds jd_mlp_kernel's grid)
+// d_span (device): span[r] beside d_row_src[r] for a spliced model (jd_splice.h), null for every other
 static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, const int *d_row_src, int n_rows,
                       float *d_ll, hipStream_t st, int max_blocks = 0, int skip_unused = 0, int used_row_tiles = -1,
-                      const int *rt_base = nullptr, int n_rt_list = 0, GmmLaunch *info = nullptr)
+                      const int *rt_base = nullptr, int n_rt_list = 0, GmmLaunch *info = nullptr, const JdSpan *d_span = nullptr)
 {
     if (info) *info = GmmLaunch();
+    if ((a->mlp && a->mlp_spliced) != (d_span != nullptr))
+        return jd_fail(JD_EINVAL, "launch_gmm: the rows' spans are a spliced model's (jd_am_mlp_splice), and such a model's launch needs them");
     const ScorePlan p = gmm_plan(a, b, n_rows, max_blocks, used_row_tiles, rt_base != nullptr, n_rt_list);
     if (p.verdict == SCORE_PLAN_NOTHING) return JD_OK;
     if (p.verdict == SCORE_PLAN_LIST) return jd_fail(JD_EINVAL, "launch_gmm: tile lists are the D = 39 kernel's");
@@ -172,7 +190,11 @@ static int launch_gmm(const jd_am *a, const AmDevBuf &b, const float *d_feats, c
     case JD_KERNEL_MLP:
     case JD_KERNEL_MLP_BF16:
     case JD_KERNEL_MLP_TIED_BF16:
-    case JD_KERNEL_MLP_TIED: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0); break;
+    case JD_KERNEL_MLP_SPLICED:
+    case JD_KERNEL_MLP_TIED_SPLICED:
+    case JD_KERNEL_MLP_BF16_SPLICED:
+    case JD_KERNEL_MLP_TIED_BF16_SPLICED:
+    case JD_KERNEL_MLP_TIED: launch_mlp(a, b, d_feats, d_row_src, n_rows, d_ll, st, p.grid, JD_MLP_OUT_LL, 0, d_span); break;
     case JD_KERNEL_HYBRID: GMM_LAUNCH(jd_hybrid_kernel, b.log_prior, a->n_gmm, d_ll); break;
     case JD_KERNEL_GMM_FAST39_16: GMM_LAUNCH(jd_gmm_fast39<GMM_GT_SMALL>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
     case JD_KERNEL_GMM_FAST39_64: GMM_LAUNCH(jd_gmm_fast39<GMM_GT>, GMM_ARGS(b.par_fast), d_ll, skip_unused, rt_base, n_rt_list); break;
@@ -225,6 +247,7 @@ struct ScoreBufs {
     AmDevBuf b;
     float *d_x = nullptr, *d_ll = nullptr;
     int *d_src = nullptr, *d_list = nullptr;
+    JdSpan *d_span = nullptr;       // a spliced model's rows (else null)
     ScoreBufs() = default;
     ScoreBufs(const ScoreBufs &) = delete;
     ScoreBufs &operator=(const ScoreBufs &) = delete;
@@ -235,10 +258,19 @@ struct ScoreBufs {
         if (d_ll) (void)hipFree(d_ll);
         if (d_src) (void)hipFree(d_src);
         if (d_list) (void)hipFree(d_list);
+        if (d_span) (void)hipFree(d_span);
     }
-    // frames [n_frames][D] and a row map [n_rows] (row_src; null: the identity) go up, beside room for n_out floats of output
-    int upload_rows(const jd_am *a, const float *frames, int n_frames, const int *row_src, int n_rows, size_t n_out)
+    // frames [n_frames][D] and a row map [n_rows] (row_src; null: the identity) go up, beside room for n_out floats of output;
+    // for a spliced model the rows' spans {row_lo[r], row_hi[r]} too (null: the frames are ONE utterance, {0, n_frames - 1})
+    int upload_rows(const jd_am *a, const float *frames, int n_frames, const int *row_src, int n_rows, size_t n_out, const int *row_lo = nullptr,
+                    const int *row_hi = nullptr)
     {
+        if (a->mlp && a->mlp_spliced) {
+            std::vector<JdSpan> span((size_t)n_rows, JdSpan{0, std::max(0, n_frames - 1)});
+            if (row_lo) for (int r = 0; r < n_rows; ++r) span[(size_t)r] = JdSpan{row_lo[r], row_hi[r]};
+            HIPCHK(hipMalloc(&d_span, std::max<size_t>(span.size(), 1) * sizeof(JdSpan)));
+            if (n_rows > 0) HIPCHK(hipMemcpy(d_span, span.data(), span.size() * sizeof(JdSpan), hipMemcpyHostToDevice));
+        }
         const size_t D = (size_t)a->D;
         std::vector<int> identity;
         if (!row_src) {
@@ -258,16 +290,17 @@ struct ScoreBufs {
 // One launch_gmm call on buffers of its own (the device is set): frames [n_frames][D] and row_src [n_rows] (null: the identity) go up, with the tile list
 // rt_base [n_rt] (or null) and - prefilled - the caller's out [(guard_rows + n_rows + guard_rows)][G]; the table is written `guard_rows`
 // rows into the buffer, and the whole buffer comes back.  The arguments are the caller's to check (jd_debug_score_rows does).
+// (row_lo / row_hi: a spliced model's spans; null: the frames are one utterance)
 static int score_rows_on_device(const jd_am *a, int mode, const float *frames, int n_frames, const int *row_src, int n_rows, int skip_unused,
                                 int max_blocks, int used_row_tiles, const int *rt_base, int n_rt, int guard_rows, bool prefilled, float *out,
-                                GmmLaunch *info)
+                                GmmLaunch *info, const int *row_lo = nullptr, const int *row_hi = nullptr)
 {
     ScoreBufs s;
     int rc = upload_am_gmm(a, s.b);
     if (rc) return rc;
     if (mode == JD_SCORE_FAST) { rc = upload_am_fast(a, s.b); if (rc) return rc; s.b.fast = 1; }
     const size_t G = (size_t)a->n_gmm, n_out = ((size_t)n_rows + 2 * (size_t)guard_rows) * G;
-    rc = s.upload_rows(a, frames, n_frames, row_src, n_rows, n_out);
+    rc = s.upload_rows(a, frames, n_frames, row_src, n_rows, n_out, row_lo, row_hi);
     if (rc) return rc;
     if (prefilled) HIPCHK(hipMemcpy(s.d_ll, out, n_out * sizeof(float), hipMemcpyHostToDevice));
     if (rt_base) {
@@ -275,7 +308,7 @@ static int score_rows_on_device(const jd_am *a, int mode, const float *frames, i
         HIPCHK(hipMemcpy(s.d_list, rt_base, (size_t)n_rt * sizeof(int), hipMemcpyHostToDevice));
     }
     rc = launch_gmm(a, s.b, s.d_x, s.d_src, n_rows, s.d_ll + (size_t)guard_rows * G, 0, max_blocks, skip_unused, used_row_tiles, s.d_list,
-                    rt_base ? n_rt : 0, info);
+                    rt_base ? n_rt : 0, info, s.d_span);
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, s.d_ll, n_out * sizeof(float), hipMemcpyDeviceToHost));
@@ -340,10 +373,45 @@ static int check_score_rows(const jd_am *a, int mode, int n_frames, const int *r
     return JD_OK;
 }
 
-// launch_gmm with a caller's own arguments, as the decoder's paths call it (include/juicer_amd.h)
+// launch_gmm with a caller's own arguments, as the decoder's paths call it (include/juicer_amd.h); jd_debug_score_rows_span: the same
+// with the rows' spans, a spliced model's (row_lo / row_hi null: any other model's)
+static int debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                            int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
+                            int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid, const int32_t *row_lo, const int32_t *row_hi);
 extern "C" int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
                                    int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
                                    int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid)
+{
+    if (a && a->mlp && a->mlp_spliced) {
+        if (kernel) *kernel = JD_KERNEL_NONE;
+        if (grid) *grid = 0;
+        return jd_fail(JD_EINVAL, "jd_debug_score_rows: these models are spliced (jd_am_mlp_splice) and a row needs its span: jd_debug_score_rows_span takes it");
+    }
+    return debug_score_rows(a, device, mode, frames, n_frames, row_src, n_rows, skip_unused, max_blocks, used_row_tiles, rt_base, n_rt, guard_rows, out, kernel,
+                            grid, nullptr, nullptr);
+}
+extern "C" int jd_debug_score_rows_span(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                                        const int32_t *row_lo, const int32_t *row_hi, int32_t n_rows, int32_t skip_unused, int32_t max_blocks,
+                                        int32_t used_row_tiles, const int32_t *rt_base, int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel,
+                                        int32_t *grid)
+{
+    if (kernel) *kernel = JD_KERNEL_NONE;
+    if (grid) *grid = 0;
+    if (!a || !(a->mlp && a->mlp_spliced))
+        return jd_fail(JD_EINVAL, "jd_debug_score_rows_span: spans are a spliced model's (jd_am_mlp_splice); jd_debug_score_rows serves every other");
+    if (n_rows > 0 && (!row_lo || !row_hi)) return jd_fail(JD_EINVAL, "jd_debug_score_rows_span: bad argument");
+    for (int r = 0; r < n_rows; ++r) {
+        if (row_src && row_src[r] < 0) continue;                       // (an unused row's span is not read)
+        if (row_lo[r] < 0 || row_lo[r] >= n_frames) return jd_fail(JD_EINVAL, "jd_debug_score_rows_span: row_lo[%d] = %d outside [0, %d)", r, row_lo[r], n_frames);
+        if (row_hi[r] < 0 || row_hi[r] >= n_frames) return jd_fail(JD_EINVAL, "jd_debug_score_rows_span: row_hi[%d] = %d outside [0, %d)", r, row_hi[r], n_frames);
+        if (row_lo[r] > row_hi[r]) return jd_fail(JD_EINVAL, "jd_debug_score_rows_span: row_lo[%d] = %d above row_hi[%d] = %d", r, row_lo[r], r, row_hi[r]);
+    }
+    return debug_score_rows(a, device, mode, frames, n_frames, row_src, n_rows, skip_unused, max_blocks, used_row_tiles, rt_base, n_rt, guard_rows, out, kernel,
+                            grid, row_lo, row_hi);
+}
+static int debug_score_rows(const jd_am *a, int32_t device, int32_t mode, const float *frames, int32_t n_frames, const int32_t *row_src,
+                            int32_t n_rows, int32_t skip_unused, int32_t max_blocks, int32_t used_row_tiles, const int32_t *rt_base,
+                            int32_t n_rt, int32_t guard_rows, float *out, int32_t *kernel, int32_t *grid, const int32_t *row_lo, const int32_t *row_hi)
 {
     if (kernel) *kernel = JD_KERNEL_NONE;
     if (grid) *grid = 0;
@@ -360,7 +428,7 @@ extern "C" int jd_debug_score_rows(const jd_am *a, int32_t device, int32_t mode,
     if (n_rows == 0) return JD_OK;
     GmmLaunch info;
     rc = score_rows_on_device(a, mode, frames, n_frames, row_src, n_rows, skip_unused, max_blocks, used_row_tiles, rt_base, n_rt, guard_rows, true,
-                              out, &info);
+                              out, &info, row_lo, row_hi);
     if (rc) return rc;
     if (kernel) *kernel = info.kernel;
     if (grid) *grid = (int32_t)info.grid;
@@ -379,7 +447,7 @@ static int mlp_on_device(const jd_am *a, int device, const float *frames, int n_
     const size_t W = (size_t)(out_mode == JD_MLP_OUT_LAYER ? a->mlp_desc.width[layer] : a->n_gmm);
     rc = s.upload_rows(a, frames, n_frames, nullptr, n_frames, (size_t)n_frames * W);
     if (rc) return rc;
-    launch_mlp(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, gmm_plan(a, s.b, n_frames).grid, out_mode, layer);
+    launch_mlp(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, gmm_plan(a, s.b, n_frames).grid, out_mode, layer, s.d_span);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, s.d_ll, (size_t)n_frames * W * sizeof(float), hipMemcpyDeviceToHost));
@@ -401,7 +469,10 @@ extern "C" int jd_am_mlp_forward_host(const jd_am *a, const float *frames, int32
     const int rc = mlp_args(a, frames, n_frames, logpost, "jd_am_mlp_forward_host");
     if (rc) return rc;
     const JdMlpHostMath math;
-    if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
+    if (a->mlp_spliced)                                                // (the frames are one utterance: jd_splice.h)
+        jd_splice_forward_host(a->mlp_desc, a->mlp_left, a->mlp_right, a->mlp_precision == JD_MLP_BF16, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames,
+                               -1, logpost, math, a->tied);
+    else if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
     else jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, -1, logpost, math, a->tied);
     return JD_OK;
 }
@@ -414,7 +485,10 @@ extern "C" int jd_debug_mlp_activations(const jd_am *a, int32_t device, int32_t 
         return jd_fail(JD_EINVAL, "jd_debug_mlp_activations: layer %d outside [0, %d)", layer, a->mlp_desc.n_layers);
     if (on_device) return mlp_on_device(a, device, frames, n_frames, JD_MLP_OUT_LAYER, layer, out);
     const JdMlpHostMath math;
-    if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
+    if (a->mlp_spliced)
+        jd_splice_forward_host(a->mlp_desc, a->mlp_left, a->mlp_right, a->mlp_precision == JD_MLP_BF16, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames,
+                               layer, out, math, a->tied);
+    else if (a->mlp_precision == JD_MLP_BF16) jd_mlp_bf16_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
     else jd_mlp_forward_host(a->mlp_desc, a->mlp_w.data(), a->mlp_b.data(), nullptr, frames, n_frames, layer, out, math, a->tied);
     return JD_OK;
 }
@@ -438,7 +512,7 @@ extern "C" int jd_debug_mlp_time(const jd_am *a, int32_t device, const float *fr
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return jd_fail(JD_EHIP, "jd_debug_mlp_time: hipEventCreate"); }
     for (int i = 0; i < warmup + iters && rc == JD_OK; ++i) {
         bool ok = hipEventRecord(e0, 0) == hipSuccess;
-        rc = launch_gmm(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, max_blocks);
+        rc = launch_gmm(a, s.b, s.d_x, s.d_src, n_frames, s.d_ll, 0, max_blocks, 0, -1, nullptr, 0, nullptr, s.d_span);
         float t = 0.0f;
         ok = ok && rc == JD_OK && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
         if (rc == JD_OK && !ok) rc = jd_fail(JD_EHIP, "jd_debug_mlp_time: timing a launch failed");

@@ -154,16 +154,15 @@ static int trace_partial_many(jd_dec *d, const std::vector<int> &ss, int32_t *fo
     return rc_all;
 }
 
-extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames)
+// Score and search frames [row0, row0 + n_frames) of the host buffer `frames` on stream s, chunk by chunk: jd_stream_push's frames
+// (row0 = 0, span null) or, for a spliced model, the rows that a push plan releases from its staging buffer (jd_splice.h: span is their
+// common span there; a chunk sends up the piece of the buffer its windows read, splice_rows_window, and its rows' spans are that piece).
+static int push_rows(jd_dec *d, int32_t s, const float *frames, int32_t row0, int32_t n_frames, const JdSpan *span)
 {
-    const PushCheck chk = push_check_one(d ? &d->push : nullptr, s, frames != nullptr, n_frames);
-    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_stream_push before jd_stream_init");
-    if (chk.verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_stream_push: bad argument");
-    int rc = check_device(d->device);
-    if (rc) return rc;
+    int rc = JD_OK;
     PushStream &P = d->push[(size_t)s];
-    if (n_frames > 0) P.open = 1;
     const int D = d->am->D, G = d->am->n_gmm, Fc = d->Fc;
+    const int left = d->am->mlp_left, right = d->am->mlp_right;       // (0, 0 for every unspliced model)
     const bool verbose = push_verbose();
     hipStream_t st = d->s_search;
     pf_discard(d);                                                     // (the streaming path scores into table 0)
@@ -173,18 +172,26 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
         if (verbose)
             fprintf(stderr, "push: chunk stream %d Fc %d left %d interval %d last_collect %d T %d -> n %d\n", s, Fc, n_frames - done, d->partial_interval,
                     P.last_collect, P.T, n);
-        if ((size_t)n * D > d->push_cap) { rc = dregrow(&d->d_push, &d->push_cap, (size_t)Fc * D, false); if (rc) return rc; }
-        HIPCHK(hipMemcpyAsync(d->d_push, frames + (size_t)done * D, (size_t)n * D * sizeof(float),
+        int b0 = row0 + done, b1 = b0 + n;                             // the frames that go up: the chunk's own, or its windows'
+        if (span) splice_rows_window(left, right, *span, row0 + done, n, &b0, &b1);
+        const int n_up = b1 - b0;
+        if ((size_t)n_up * D > d->push_cap) { rc = dregrow(&d->d_push, &d->push_cap, (size_t)(Fc + left + right) * D, false); if (rc) return rc; }
+        HIPCHK(hipMemcpyAsync(d->d_push, frames + (size_t)b0 * D, (size_t)n_up * D * sizeof(float),
                               hipMemcpyHostToDevice, st));
         std::vector<int> src((size_t)Fc, -1);
-        for (int i = 0; i < n; ++i) src[(size_t)i] = i;
+        for (int i = 0; i < n; ++i) src[(size_t)i] = row0 + done + i - b0;
         if ((size_t)Fc > d->row_src_cap[0]) { rc = dregrow(&d->d_row_src[0], &d->row_src_cap[0], (size_t)Fc, false); if (rc) return rc; }
         HIPCHK(hipMemcpyAsync(d->d_row_src[0], src.data(), (size_t)Fc * sizeof(int), hipMemcpyHostToDevice, st));
+        if (span) {
+            d->h_row_span[0].assign((size_t)Fc, JdSpan{0, n_up - 1});
+            if ((size_t)Fc > d->row_span_cap[0]) { rc = dregrow(&d->d_row_span[0], &d->row_span_cap[0], (size_t)Fc, false); if (rc) return rc; }
+            HIPCHK(hipMemcpyAsync(d->d_row_span[0], d->h_row_span[0].data(), (size_t)Fc * sizeof(JdSpan), hipMemcpyHostToDevice, st));
+        }
         const int f0 = P.T;
         const int Tnew = f0 + n;
         HIPCHK(hipMemcpyAsync(d->d_T + s, &Tnew, sizeof(int), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(jd_set_T_kernel, dim3(1), dim3(64), 0, st, d->d_ctl, s, 1, d->d_T + s);
-        rc = launch_gmm(d->am, d->amb, d->d_push, d->d_row_src[0], n, d->d_ll[0], st);
+        rc = launch_gmm(d->am, d->amb, d->d_push, d->d_row_src[0], n, d->d_ll[0], st, 0, 0, -1, nullptr, 0, nullptr, span ? d->d_row_span[0] : nullptr);
         if (rc) return rc;
         if (d->partial_interval <= 0) {
             rc = launch_search(d, std::vector<int2>(1, make_int2(s, 0)), d->d_ll[0], (long long)Fc * G, f0, Tnew, st);
@@ -223,6 +230,44 @@ extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t
             if (a.T >= Tnew) break;
         }
     }
+    return JD_OK;
+}
+
+// A push of a spliced model's stream (jd_splice.h: splice_push_plan): the kept frames go in front of the new ones, the rows the plan
+// releases - none, perhaps - are scored and searched, and the stream keeps what a later window still reads.  finishing: jd_stream_finish's
+// call, no new frames - the frames held back become rows with the right edge clamped.
+static int push_spliced(jd_dec *d, int32_t s, const float *frames, int32_t n_frames, bool finishing)
+{
+    PushStream &P = d->push[(size_t)s];
+    const size_t D = (size_t)d->am->D;
+    const SplicePush plan = splice_push_plan(d->am->mlp_left, d->am->mlp_right, P.pushed, n_frames, finishing);
+    std::vector<float> buf((size_t)plan.n_buf * D);
+    memcpy(buf.data(), P.held.data() + (P.held.size() - (size_t)plan.n_front * D), (size_t)plan.n_front * D * sizeof(float));
+    if (n_frames > 0) memcpy(buf.data() + (size_t)plan.n_front * D, frames, (size_t)n_frames * D * sizeof(float));
+    const int rc = plan.n_rows > 0 ? push_rows(d, s, buf.data(), plan.row_buf, plan.n_rows, &plan.span) : JD_OK;
+    // (on a failure the stream is dirty and jd_stream_finish reports it: the record still says what was pushed)
+    P.pushed += n_frames;
+    P.held.assign(buf.end() - (ptrdiff_t)((size_t)plan.n_keep * D), buf.end());
+    return rc;
+}
+
+extern "C" int jd_stream_push(jd_dec *d, int32_t s, const float *frames, int32_t n_frames)
+{
+    const PushCheck chk = push_check_one(d ? &d->push : nullptr, s, frames != nullptr, n_frames);
+    if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_stream_push before jd_stream_init");
+    if (chk.verdict != PUSH_ARG_OK) return jd_fail(JD_EINVAL, "jd_stream_push: bad argument");
+    const int rc = check_device(d->device);
+    if (rc) return rc;
+    if (n_frames > 0) d->push[(size_t)s].open = 1;
+    if (d->am->mlp_spliced) return n_frames > 0 ? push_spliced(d, s, frames, n_frames, false) : JD_OK;
+    return push_rows(d, s, frames, 0, n_frames, nullptr);
+}
+
+extern "C" int jd_stream_held_frames(jd_dec *d, int32_t s, int32_t *held)
+{
+    if (!d || s < 0 || s >= d->max_streams || !held) return jd_fail(JD_EINVAL, "jd_stream_held_frames: bad argument");
+    const PushStream &P = d->push[(size_t)s];
+    *held = (d->am->mlp_spliced && P.started) ? P.pushed - P.T : 0;
     return JD_OK;
 }
 
@@ -322,6 +367,8 @@ extern "C" int jd_streams_push(jd_dec *d, int32_t n, const int32_t *streams, con
     if (chk.verdict == PUSH_ARG_BAD_STREAM) return jd_fail(JD_EINVAL, "jd_streams_push: bad stream %d (each stream once)", chk.stream);
     if (chk.verdict == PUSH_ARG_NOT_STARTED) return jd_fail(JD_ESTATE, "jd_streams_push before jd_stream_init (stream %d)", chk.stream);
     if (rows == 0) return JD_OK;
+    if (d->am->mlp_spliced)
+        return jd_fail(JD_EINVAL, "jd_streams_push: this decoder's models are spliced (jd_am_mlp_splice), and splicing is served one stream at a time: jd_stream_push");
     if (chk.verdict == PUSH_ARG_TOO_MANY_ROWS) return jd_fail(JD_EINVAL, "jd_streams_push: more than 2^31 frames in one call");
     hipStream_t st = d->s_search;
     pf_discard(d);                                                     // (the streaming path scores into table 0)
@@ -810,6 +857,10 @@ extern "C" int jd_stream_finish(jd_dec *d, int32_t s, jd_hyp *out)
     if (!d->push[(size_t)s].started) return jd_fail(JD_ESTATE, "jd_stream_finish before jd_stream_init");
     int rc = check_device(d->device);
     if (rc) return rc;
+    if (d->am->mlp_spliced && d->push[(size_t)s].pushed > d->push[(size_t)s].T && !d->stream_dirty[(size_t)s]) {
+        rc = push_spliced(d, s, nullptr, 0, true);                     // the frames held back: rows now, the right edge clamped
+        if (rc) return rc;
+    }
     if (d->push[(size_t)s].T == 0) {                                   // init() directly followed by finish(): recognitionStart only
         rc = launch_search(d, std::vector<int2>(1, make_int2(s, 0)), d->d_ll[0], 0, 0, 0, d->s_search);
         if (rc) return rc;

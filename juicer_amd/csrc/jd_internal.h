@@ -11,6 +11,7 @@
 #include "juicer_amd.h"
 #include "jd_mlp.h"             // neural acoustic models: the network as plain data, its packing, the host twin
 #include "jd_mlp_bf16.h"        // ... and their bf16 form: the rounding, its packing, its twin
+#include "jd_splice.h"          // ... and their spliced form: the window, the row span, the push plan, the twin
 
 #define JD_MAXN 8          // max HMM states (incl. entry/exit) the search kernel handles
 
@@ -81,6 +82,10 @@ struct jd_am {
     // empty), mlp_bp the biases padded to its n tile pairs
     int32_t mlp_precision = JD_MLP_F32;
     std::vector<uint16_t> mlp_wq;
+    // spliced models (jd_am_mlp_splice, jd_splice.h): the same network on a window of mlp_left + 1 + mlp_right frames of
+    // D = in_dim / (mlp_left + mlp_right + 1) values each - D is then the FRAMES' size, mlp_desc.in_dim stays the network's
+    bool mlp_spliced = false;
+    int32_t mlp_left = 0, mlp_right = 0;
     // HMM names (HTKModels::getHMMName, for phone output): the MMF's ~h names / JMBI's JMHM names; empty when the models
     // were built from arrays
     std::vector<std::string> hmm_name;            // [n_hmm] or empty
@@ -110,4 +115,7 @@ int jd_res_poll(jd_dec *d, int s, int *idle, int *frame, int *error, int *stoppe
 int jd_res_stream_error(jd_dec *d, int s, int dev_error, int frame);   // a poll's device-side error as code + jd_last_error()
 int jd_res_collect(jd_dec *d, int s);
 int jd_res_finish(jd_dec *d, int s, jd_hyp *out);
+// the decoder's models are spliced ones (jd_am_mlp_splice): no broker serves them.  (Weak: jd_broker.cpp is also linked against decoders
+// that have no such models and do not define it - it asks only where the symbol is there)
+int jd_dec_spliced(const jd_dec *d) __attribute__((weak));
 #endif

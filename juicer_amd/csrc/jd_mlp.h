@@ -151,6 +151,7 @@ struct JdMlpDev {
     int32_t in_dim, n_layers, stride;             // stride: floats of an activation row in LDS
     int32_t width[JD_MLP_MAX_LAYERS], act[JD_MLP_MAX_LAYERS];
     uint32_t w_off[JD_MLP_MAX_LAYERS + 1], b_off[JD_MLP_MAX_LAYERS + 1];      // packed; [n_layers]: the sizes
+    int32_t base_dim, left, right;                // spliced models (jd_splice.h): the frames' size and the context; else in_dim, 0, 0
 };
 // (tied: jd_mlp_tied_kernel's - the last layer's outputs are not held in LDS and do not widen the stride)
 static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d, bool tied = false)
@@ -158,6 +159,7 @@ static inline JdMlpDev jd_mlp_dev(const JdMlpDesc &d, bool tied = false)
     JdMlpDev m;
     memset(&m, 0, sizeof m);
     m.in_dim = d.in_dim; m.n_layers = d.n_layers;
+    m.base_dim = d.in_dim;
     int widest = jd_mlp_pad16(d.in_dim);
     for (int l = 0; l < d.n_layers; ++l) {
         m.width[l] = d.width[l]; m.act[l] = d.act[l];

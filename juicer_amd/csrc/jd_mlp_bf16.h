@@ -84,6 +84,7 @@ static inline JdMlpDev jd_mlp_bf16_dev(const JdMlpDesc &d)
     JdMlpDev m;
     memset(&m, 0, sizeof m);
     m.in_dim = d.in_dim; m.n_layers = d.n_layers;
+    m.base_dim = d.in_dim;
     int widest = jd_mlp_pad32(d.in_dim);
     for (int l = 0; l < d.n_layers; ++l) {
         m.width[l] = d.width[l]; m.act[l] = d.act[l];

@@ -22,6 +22,10 @@
 // columns are outputs 32 w + (lane & 15) (+ 16) modulo 128, chains that belong to this lane alone and meet their elements in ascending
 // order; the partials of its 8 rows x 2 chains stay in registers, go to LDS [32][128], and lane r of the first wave chains them.
 // A row with row_src < 0 is written 0.0f; a tile without a used row does no arithmetic; rows at or behind n_rows are never touched.
+//
+// SPLICED models (jd_am_mlp_splice, jd_splice.h): the SPL = true instantiations, jd_mlp_bf16_spliced_kernel / jd_mlp_tied_bf16_spliced_kernel,
+// differ in the input stage alone, as jd_mlp_kernel.h's do: the tile keeps its rows' spans beside ssrc and gathers C pieces of D values a
+// row, rounded to bf16 as they land.  The SPL = false ones read neither `span` nor the context.
 #pragma once
 
 typedef __bf16 jd_mlp_bf8 __attribute__((ext_vector_type(8)));
@@ -62,11 +66,12 @@ __device__ __forceinline__ void jd_mlp_bf16_chain(const jd_mlp_bf8 *__restrict__
 
 // (one body, two kernels: jd_mlp_bf16_kernel and jd_mlp_tied_bf16_kernel are its instantiations, named at the end of this file.  m is
 // the kernel's own argument - read from the kernel-argument segment with scalar loads, not through a private copy)
-template <bool TIED>
+template <bool TIED, bool SPL>
 __global__ __launch_bounds__(256) void jd_mlp_bf16_kernel_t(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
                                                             const unsigned short *__restrict__ wp, const float *__restrict__ bp,
                                                             const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
-                                                            const JdMlpDev m, float *out, int out_mode, int layer)
+                                                            const JdMlpDev m, float *out, int out_mode, int layer,
+                                                            const JdSpan *__restrict__ span)
 {
     extern __shared__ __align__(16) char smem[];
     constexpr int R = JD_MLP_BF16_ROWS;
@@ -75,6 +80,7 @@ __global__ __launch_bounds__(256) void jd_mlp_bf16_kernel_t(const float *__restr
     int *ssrc = (int *)(buf1 + R * S);                                 // [32] the tile's row_src (-1 behind n_rows)
     float *slz = (float *)(ssrc + R);                                  // [32] logZ
     float *sp = slz + R;                                               // TIED: [32][JD_MLP_LZ_CHAINS] the partial chains
+    JdSpan *sspan = (JdSpan *)(TIED ? sp + R * JD_MLP_LZ_CHAINS : sp); // SPL: [32] the tile's spans
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, q = lane >> 4;
@@ -85,6 +91,7 @@ __global__ __launch_bounds__(256) void jd_mlp_bf16_kernel_t(const float *__restr
         const int rows = min(R, n_rows - r0);                          // the tile's rows inside the table: nothing behind them is touched
         __syncthreads();                                               // the previous tile's readers are done
         if (tid < R) ssrc[tid] = (tid < rows) ? row_src[r0 + tid] : -1;
+        if (SPL && tid < rows) sspan[tid] = span[r0 + tid];
         __syncthreads();
         bool any = false;
 #pragma unroll
@@ -95,7 +102,23 @@ __global__ __launch_bounds__(256) void jd_mlp_bf16_kernel_t(const float *__restr
                     for (int j = tid; j < P; j += 256) out[(size_t)(r0 + r) * P + j] = 0.0f;
             continue;
         }
-        {   // the input rows as bf16, padded with +0 to the k group; an unused row is +0 throughout
+        if (SPL) {   // pieces outside, d inside (jd_mlp_stage_spliced): a wave takes a piece, its lanes the piece's D contiguous values
+            const int D = m.base_dim, left = m.left, C = left + m.right + 1, K = m.in_dim, pad = ((K + 31) & ~31) - K;
+            for (int p = wid; p < R * C; p += 4) {                     // (wave-uniform)
+                const int r = p / C, c = p - r * C;
+                const int src = ssrc[r];
+                unsigned short *dst = buf0 + r * S + c * D;
+                if (src >= 0) {
+                    const float *f = feats + (size_t)jd_splice_frame(src, c, left, sspan[r]) * D;
+                    for (int d = lane; d < D; d += 64) dst[d] = jd_bf16_bits(f[d]);
+                } else
+                    for (int d = lane; d < D; d += 64) dst[d] = (unsigned short)0;
+            }
+            for (int e = tid; e < R * pad; e += 256) {
+                const int r = e / pad;
+                buf0[r * S + K + (e - r * pad)] = (unsigned short)0;
+            }
+        } else {   // the input rows as bf16, padded with +0 to the k group; an unused row is +0 throughout
             const int K = m.in_dim, Kp = (K + 31) & ~31;
             for (int e = tid; e < R * Kp; e += 256) {
                 const int r = e / Kp, k = e - r * Kp;
@@ -207,5 +230,7 @@ __global__ __launch_bounds__(256) void jd_mlp_bf16_kernel_t(const float *__restr
     }
 }
 
-static constexpr auto jd_mlp_bf16_kernel = jd_mlp_bf16_kernel_t<false>;
-static constexpr auto jd_mlp_tied_bf16_kernel = jd_mlp_bf16_kernel_t<true>;
+static constexpr auto jd_mlp_bf16_kernel = jd_mlp_bf16_kernel_t<false, false>;
+static constexpr auto jd_mlp_tied_bf16_kernel = jd_mlp_bf16_kernel_t<true, false>;
+static constexpr auto jd_mlp_bf16_spliced_kernel = jd_mlp_bf16_kernel_t<false, true>;
+static constexpr auto jd_mlp_tied_bf16_spliced_kernel = jd_mlp_bf16_kernel_t<true, true>;

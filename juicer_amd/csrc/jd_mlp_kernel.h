@@ -20,6 +20,12 @@
 //
 // jd_mlp_tied_kernel, at the end of this file, is the same pass for the models of jd_am_create_mlp_tied: an output layer of up to
 // 16384 tied states whose logits live in the tile's rows of the table, and logZ by 128 interleaved chains.
+//
+// SPLICED models (jd_am_mlp_splice, jd_splice.h).  Each kernel is a template over SPL; jd_mlp_kernel / jd_mlp_tied_kernel name the
+// SPL = false instantiations - the code of an unspliced model, which reads neither `span` nor the context - and jd_mlp_spliced_kernel /
+// jd_mlp_tied_spliced_kernel the SPL = true ones, which differ in the input stage alone (jd_mlp_stage_spliced): the tile keeps its
+// rows' spans beside ssrc and fills the first activation buffer with C = left + right + 1 pieces of D = base_dim values each, piece c
+// of a row from frame jd_splice_frame(row_src, c, left, span).  The layout in LDS is the one layer 0 expects.
 #pragma once
 
 typedef float jd_mlp_f4 __attribute__((ext_vector_type(4)));
@@ -104,16 +110,43 @@ __device__ __forceinline__ void jd_mlp_chain(const jd_mlp_f4 *__restrict__ ap, c
     }
 }
 
-__global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
-                                                     const float *__restrict__ wp, const float *__restrict__ bp,
-                                                     const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
-                                                     const JdMlpDev m, float *__restrict__ out, int out_mode, int layer)
+// The input stage of a spliced tile: pieces outside, d inside - a wave takes a piece (row r, frame c of its window: wave-uniform, one
+// division a piece and none an element), its lanes the piece's D contiguous values.  An unused row is 0.0f and reads nothing; the
+// padding behind in_dim is -0 as ever.  sspan: the tile's spans (LDS).  (D, left, right, K by value: the kernel's argument m stays in
+// the kernel-argument segment - a reference to it would make a private copy)
+__device__ __forceinline__ void jd_mlp_stage_spliced(const float *__restrict__ feats, const int *ssrc, const JdSpan *sspan, int D, int left, int right,
+                                                     int K, float *buf0, int S, int tid, int lane, int wid)
+{
+    const int C = left + right + 1, pad = ((K + 15) & ~15) - K;
+    for (int p = wid; p < JD_MLP_ROWS * C; p += 4) {                   // (wave-uniform)
+        const int r = p / C, c = p - r * C;
+        const int src = ssrc[r];
+        float *dst = buf0 + r * S;
+        if (src >= 0) {
+            const float *f = feats + (size_t)jd_splice_frame(src, c, left, sspan[r]) * D;
+            for (int d = lane; d < D; d += 64) dst[jd_mlp_act_pos(c * D + d)] = f[d];
+        } else
+            for (int d = lane; d < D; d += 64) dst[jd_mlp_act_pos(c * D + d)] = 0.0f;
+    }
+    for (int e = tid; e < JD_MLP_ROWS * pad; e += 256) {
+        const int r = e / pad, k = K + (e - r * pad);
+        buf0[r * S + jd_mlp_act_pos(k)] = -0.0f;
+    }
+}
+
+template <bool SPL>
+__global__ __launch_bounds__(256) void jd_mlp_kernel_t(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
+                                                       const float *__restrict__ wp, const float *__restrict__ bp,
+                                                       const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
+                                                       const JdMlpDev m, float *__restrict__ out, int out_mode, int layer,
+                                                       const JdSpan *__restrict__ span)
 {
     extern __shared__ __align__(16) char smem[];
     const int S = m.stride;
     float *buf0 = (float *)smem, *buf1 = buf0 + JD_MLP_ROWS * S;      // [16][S] each
     int *ssrc = (int *)(buf1 + JD_MLP_ROWS * S);                       // [16] the tile's row_src (-1 behind n_rows)
     float *slz = (float *)(ssrc + JD_MLP_ROWS);                        // [16] logZ
+    JdSpan *sspan = (JdSpan *)(slz + JD_MLP_ROWS);                     // SPL: [16] the tile's spans
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int P = m.width[m.n_layers - 1];
@@ -122,6 +155,7 @@ __global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ f
         const int r0 = rt * JD_MLP_ROWS;
         __syncthreads();                                               // the previous tile's readers are done
         if (tid < JD_MLP_ROWS) ssrc[tid] = (r0 + tid < n_rows) ? row_src[r0 + tid] : -1;
+        if (SPL && tid < JD_MLP_ROWS && r0 + tid < n_rows) sspan[tid] = span[r0 + tid];
         __syncthreads();
         bool any = false;
 #pragma unroll
@@ -134,7 +168,8 @@ __global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ f
                 }
             continue;
         }
-        {   // the input rows, padded with -0 to the k group
+        if (SPL) jd_mlp_stage_spliced(feats, ssrc, sspan, m.base_dim, m.left, m.right, m.in_dim, buf0, S, tid, lane, wid);
+        else {   // the input rows, padded with -0 to the k group
             const int K = m.in_dim, Kp = (K + 15) & ~15;
             for (int e = tid; e < JD_MLP_ROWS * Kp; e += 256) {
                 const int r = e / Kp, k = e - r * Kp;
@@ -204,10 +239,15 @@ __global__ __launch_bounds__(256) void jd_mlp_kernel(const float *__restrict__ f
 // beyond P are not added and a chain c >= P stays empty.  The partials go to LDS [16][128], lane r of the first wave runs row r's chain
 // over them (128 steps: serial by definition), and all threads read the tile's logits back and write (z - logZ) - log_prior.
 // The logits are kept in memory whatever the width: the result does not depend on where they were held.
-__global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
-                                                          const float *__restrict__ wp, const float *__restrict__ bp,
-                                                          const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
-                                                          const JdMlpDev m, float *out, int out_mode, int layer)
+static constexpr auto jd_mlp_kernel = jd_mlp_kernel_t<false>;
+static constexpr auto jd_mlp_spliced_kernel = jd_mlp_kernel_t<true>;
+
+template <bool SPL>
+__global__ __launch_bounds__(256) void jd_mlp_tied_kernel_t(const float *__restrict__ feats, const int *__restrict__ row_src, int n_rows,
+                                                            const float *__restrict__ wp, const float *__restrict__ bp,
+                                                            const float *__restrict__ log_prior, const JdLogTab *__restrict__ logtab,
+                                                            const JdMlpDev m, float *out, int out_mode, int layer,
+                                                            const JdSpan *__restrict__ span)
 {
     extern __shared__ __align__(16) char smem[];
     const int S = m.stride;
@@ -215,6 +255,7 @@ __global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restric
     int *ssrc = (int *)(buf1 + JD_MLP_ROWS * S);                       // [16] the tile's row_src (-1 behind n_rows)
     float *slz = (float *)(ssrc + JD_MLP_ROWS);                        // [16] logZ
     float *sp = slz + JD_MLP_ROWS;                                     // [16][JD_MLP_LZ_CHAINS] the partial chains
+    JdSpan *sspan = (JdSpan *)(sp + JD_MLP_ROWS * JD_MLP_LZ_CHAINS);   // SPL: [16] the tile's spans
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = m.n_layers, P = m.width[L - 1];
@@ -224,6 +265,7 @@ __global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restric
         const int rows = min(JD_MLP_ROWS, n_rows - r0);                // the tile's rows inside the table: nothing behind them is touched
         __syncthreads();                                               // the previous tile's readers are done
         if (tid < JD_MLP_ROWS) ssrc[tid] = (tid < rows) ? row_src[r0 + tid] : -1;
+        if (SPL && tid < rows) sspan[tid] = span[r0 + tid];
         __syncthreads();
         bool any = false;
 #pragma unroll
@@ -234,7 +276,8 @@ __global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restric
                     for (int j = tid; j < P; j += 256) out[(size_t)(r0 + r) * P + j] = 0.0f;
             continue;
         }
-        {   // the input rows, padded with -0 to the k group
+        if (SPL) jd_mlp_stage_spliced(feats, ssrc, sspan, m.base_dim, m.left, m.right, m.in_dim, buf0, S, tid, lane, wid);
+        else {   // the input rows, padded with -0 to the k group
             const int K = m.in_dim, Kp = (K + 15) & ~15;
             for (int e = tid; e < JD_MLP_ROWS * Kp; e += 256) {
                 const int r = e / Kp, k = e - r * Kp;
@@ -333,3 +376,6 @@ __global__ __launch_bounds__(256) void jd_mlp_tied_kernel(const float *__restric
         }
     }
 }
+
+static constexpr auto jd_mlp_tied_kernel = jd_mlp_tied_kernel_t<false>;
+static constexpr auto jd_mlp_tied_spliced_kernel = jd_mlp_tied_kernel_t<true>;

@@ -21,7 +21,11 @@ enum { PATH_COLLECT_EVERY = 100 };
 // ---- one stream of the streaming interface, as the host knows it (lazy_in and stream_dirty are the device run's, jd_dec)
 struct PushModels { std::vector<int32_t> model, label, time; std::vector<float> score, ac, lm; };
 struct PushStream {
-    int T = 0;                                         // frames pushed so far
+    int T = 0;                                         // frames pushed - and searched - so far
+    // a spliced model's stream (jd_splice.h): the frames pushed, of which T are searched, and the last ones of them, which a later
+    // window still reads (splice_push_plan: at most left + right while the stream is open); 0 / empty for every other model
+    int pushed = 0;
+    std::vector<float> held;
     int started = 0;
     int open = 0;                                      // frames pushed since the stream's init, not finished yet (jd_dec_set_output_level)
     int resident = 0;                                  // the utterance was begun on the resident kernel (jd_res_init: a broker's stream)
@@ -36,14 +40,15 @@ struct PushStream {
     void init()                                        // jd_stream_init (WFSTDecoderLite.cpp:179-181, 202-206)
     {
         T = 0; started = 1; open = 0; resident = 0;
+        pushed = 0; held.clear();
         last_collect = -1; last_trace = -1; n_collect = 0;
         partial_label.clear(); partial_time.clear();
         partial_m = PushModels();
         best = PushModels();
         fin = PushModels(); fin_tot[0] = fin_tot[1] = fin_tot[2] = 0.0f;
     }
-    void begin() { T = 0; started = 1; open = 0; resident = 1; }     // jd_res_init: the broker's stream begins an utterance (it runs no PARTIAL_DECODING)
-    void taken_over() { started = 0; T = 0; open = 0; resident = 0; }   // a batch takes every stream over (jd_decode_batch_device)
+    void begin() { T = 0; started = 1; open = 0; resident = 1; pushed = 0; held.clear(); }     // jd_res_init: the broker's stream begins an utterance (it runs no PARTIAL_DECODING)
+    void taken_over() { started = 0; T = 0; open = 0; resident = 0; pushed = 0; held.clear(); }   // a batch takes every stream over (jd_decode_batch_device)
     // jd_stream_finish: under PARTIAL_DECODING one more trace, from the best token (:245-251) - the hypothesis (n < 0: none) comes
     // newest first, partialPaths are oldest first
     void finish(bool partial, int n, const int32_t *label, const int32_t *time)

@@ -12,6 +12,7 @@
 #include "../../include/juicer_amd.h"   // JD_KERNEL_* (by its place: jd_pipe.h's includers search csrc alone)
 #include "jd_mlp.h"            // JD_MLP_ROWS: the rows of jd_mlp_kernel's tile
 #include "jd_mlp_bf16.h"       // JD_MLP_BF16_ROWS: the rows of jd_mlp_bf16_kernel's tile, and its LDS
+#include "jd_splice.h"         // jd_splice_lds_bytes: what a spliced kernel's tile keeps beside it
 
 #define GMM_ROWS 64             // stream-frames per tile of jd_gmm_kernel<0> (one per lane)
 #define GMM_GT 64               // tied states per GMM workgroup (16 per wave)
@@ -43,17 +44,25 @@ struct ScoreKernels {
 };
 // (tied: jd_am_create_mlp_tied's models among those with a network - jd_mlp_tied_kernel; bf16: jd_am_mlp_to_bf16's among those -
 // jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel, tiles of JD_MLP_BF16_ROWS rows; lds_bytes is then the bound the kernel is told,
-// JD_MLP_BF16_LDS_MAX / JD_MLP_TIED_BF16_LDS_MAX, and the launch takes the network's own, jd_mlp_bf16.h)
-static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast, bool tied = false, bool bf16 = false)
+// JD_MLP_BF16_LDS_MAX / JD_MLP_TIED_BF16_LDS_MAX, and the launch takes the network's own, jd_mlp_bf16.h;
+// spliced: jd_am_mlp_splice's among those with a network - the spliced flavour of the same kernel, the same tile, and the tile's spans
+// behind the bf16 bound)
+static inline ScoreKernels score_kernels(int D, bool hybrid, bool mlp, bool fast, bool tied = false, bool bf16 = false, bool spliced = false)
 {
     ScoreKernels k;
     if (mlp && bf16) {
-        k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED_BF16 : JD_KERNEL_MLP_BF16;
+        if (spliced) k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED_BF16_SPLICED : JD_KERNEL_MLP_BF16_SPLICED;
+        else k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED_BF16 : JD_KERNEL_MLP_BF16;
         k.tile_rows = JD_MLP_BF16_ROWS;
-        k.lds_bytes = tied ? JD_MLP_TIED_BF16_LDS_MAX : JD_MLP_BF16_LDS_MAX;
+        k.lds_bytes = (tied ? JD_MLP_TIED_BF16_LDS_MAX : JD_MLP_BF16_LDS_MAX) + (spliced ? jd_splice_lds_bytes(JD_MLP_BF16_ROWS) : 0);
         return k;
     }
-    if (mlp) { k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED : JD_KERNEL_MLP; k.tile_rows = JD_MLP_ROWS; return k; }
+    if (mlp) {
+        if (spliced) k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED_SPLICED : JD_KERNEL_MLP_SPLICED;
+        else k.kernel = k.kernel_small = tied ? JD_KERNEL_MLP_TIED : JD_KERNEL_MLP;
+        k.tile_rows = JD_MLP_ROWS;
+        return k;
+    }
     if (hybrid) { k.kernel = k.kernel_small = JD_KERNEL_HYBRID; return k; }
     k.state_tiles = true;
     k.tiles128 = D == 39 || fast;
@@ -91,6 +100,7 @@ struct ScorePlanIn {
     bool has_list; int n_rt_list;         // score the listed row tiles only (the kernels of 128-row tiles)
     bool tied = false;                    // mlp, and the network's outputs are tied states (jd_am_create_mlp_tied): jd_mlp_tied_kernel
     bool bf16 = false;                    // mlp, and the model is a bf16 one (jd_am_mlp_to_bf16): jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel
+    bool spliced = false;                 // mlp, and the model is a spliced one (jd_am_mlp_splice): the spliced flavour of its kernel
 };
 
 enum ScorePlanVerdict {
@@ -102,7 +112,7 @@ enum ScorePlanVerdict {
 struct ScorePlan {                        // (what follows the point a verdict other than ok was reached stays 0)
     ScorePlanVerdict verdict = SCORE_PLAN_OK;
     int kernel = JD_KERNEL_NONE;
-    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel, jd_mlp_tied_kernel; 32: their bf16 kernels; 64 or 128
+    int tile_rows = 0;                    // 0: jd_hybrid_kernel; 16: jd_mlp_kernel, jd_mlp_tied_kernel; 32: their bf16 kernels (spliced or not); 64 or 128
     int tile_states = 0;                  // 16 or 64; 0: no state tiles
     long long row_tiles = 0, tiles = 0;   // jd_hybrid_kernel: no row tiles, and its tiles are blocks of 256 cells
     unsigned grid = 0;
@@ -114,7 +124,7 @@ static inline ScorePlan score_plan(const ScorePlanIn &in)
 {
     ScorePlan p;
     if (in.n_rows <= 0) { p.verdict = SCORE_PLAN_NOTHING; return p; }
-    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast, in.tied, in.bf16);
+    const ScoreKernels k = score_kernels(in.D, in.hybrid, in.mlp, in.fast, in.tied, in.bf16, in.spliced);
     const int max_blocks = in.max_blocks;
     // (hybrid models: all of rows [0, n_rows), whatever the other arguments say - but for max_blocks, which bounds the grid of
     // jd_mlp_kernel and jd_mlp_tied_kernel and of their bf16 kernels)

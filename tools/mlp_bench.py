@@ -7,7 +7,12 @@ networks 351 -> 1024 -> 1024 -> 3000 and 351 -> 1024 -> 1024 -> 8192, sigmoid (j
 FLOP = 2 x rows x weights (the products' multiply-adds; activations and the log-softmax are not counted).
 --bf16: beside them the bf16 model of the same network (jd_am_mlp_to_bf16: jd_mlp_bf16_kernel / jd_mlp_tied_bf16_kernel) and torch in
 bf16 - the f32 and the bf16 kernel alternate, R runs each (at least 3); the median over the runs' medians, and their spread
-(least .. greatest), are reported."""
+(least .. greatest), are reported.
+--splice [--runs R] [--lib PATH]: the 39 x 9 network as it is on caller-spliced vectors of 351 values, and its model spliced (4, 4)
+(jd_am_mlp_splice: the window is gathered in the kernel's input stage) on the same frames as raw vectors of 39 values - one utterance -
+alternating, R runs each; the median of the runs' medians, the spread, and the bytes each variant copies to the device for the rows.
+--lib: another build of libjuicer_amd.so, the parent commit's for instance - one that knows no splicing reports the unspliced figures
+alone, which is what this commit's unspliced figures are held against."""
 import argparse
 import json
 import os
@@ -81,6 +86,41 @@ def torch_ms(layers, log_prior, x, warmup, iters, dtype=torch.float32):
     return float(np.median(ms)), out.cpu().numpy()
 
 
+def splice_bench(args):
+    """the unspliced kernel on caller-spliced vectors against the spliced kernel on raw frames, alternating"""
+    left = right = 4
+    D = IN_DIM // (left + right + 1)
+    layers, pr = make()
+    parent = capi.Models.from_mlp(pr, 3, layers)
+    spl = parent.splice(left, right) if hasattr(capi.lib(), "jd_am_mlp_splice") else None
+    res = []
+    for rows in (8192, 64):
+        f = np.random.default_rng(rows).standard_normal((rows, D)).astype(np.float32)
+        idx = np.clip(np.arange(rows)[:, None] + np.arange(left + right + 1)[None, :] - left, 0, rows - 1)
+        x = np.ascontiguousarray(f[idx].reshape(rows, IN_DIM))
+        a, b = [], []
+        for r in range(args.runs):
+            a.append(float(np.median(parent.mlp_time(x, warmup=args.warmup, iters=args.iters))))
+            if spl is not None:
+                b.append(float(np.median(spl.mlp_time(f, warmup=args.warmup, iters=args.iters))))
+        out = dict(net="-".join(str(v) for v in (IN_DIM,) + WIDTHS), rows=rows, iters=args.iters, runs=args.runs, lib=capi.LIB_PATH,
+                   caller_spliced_ms=float(np.median(a)), caller_spliced_spread=[min(a), max(a)], caller_spliced_bytes=int(x.nbytes))
+        if spl is not None:
+            out.update(spliced_ms=float(np.median(b)), spliced_spread=[min(b), max(b)], spliced_bytes=int(f.nbytes) + 8 * rows,
+                       equal=bool(np.array_equal(spl.score_frames(f).view(np.uint32), parent.score_frames(x).view(np.uint32))))
+        res.append(out)
+    if args.json:
+        print(json.dumps(res))
+        return
+    for r in res:
+        line = "%s, %5d rows: caller-spliced %.4f ms [%.4f .. %.4f], %d bytes to the device" % (r["net"], r["rows"], r["caller_spliced_ms"],
+                                                                                                *r["caller_spliced_spread"], r["caller_spliced_bytes"])
+        if "spliced_ms" in r:
+            line += "   spliced (4, 4) %.4f ms [%.4f .. %.4f], %d bytes   spliced / caller-spliced %.3f   equal %s" % (
+                r["spliced_ms"], *r["spliced_spread"], r["spliced_bytes"], r["spliced_ms"] / r["caller_spliced_ms"], r["equal"])
+        print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
@@ -88,13 +128,19 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--tied", action="store_true", help="the tied-state networks (jd_mlp_tied_kernel)")
     ap.add_argument("--bf16", action="store_true", help="also the bf16 model of the same network and torch in bf16")
-    ap.add_argument("--runs", type=int, default=3, help="--bf16: runs of each kernel, alternating")
+    ap.add_argument("--runs", type=int, default=3, help="--bf16 / --splice: runs of each kernel, alternating")
+    ap.add_argument("--splice", action="store_true", help="the network on caller-spliced vectors and its spliced model on raw frames")
+    ap.add_argument("--lib", help="--splice: the libjuicer_amd.so to load instead of this tree's")
     args = ap.parse_args()
+    if args.lib:
+        capi.LIB_PATH = os.path.abspath(args.lib)
     assert args.runs >= 3, "at least three runs each"
     assert args.iters >= 20, "the median of at least 20 warm launches"
     if not torch.cuda.is_available():
         sys.exit("mlp_bench: no GPU (a time is a measurement on the device)")
     torch.backends.cuda.matmul.allow_tf32 = False
+    if args.splice:
+        return splice_bench(args)
     res = []
     for widths in (TIED_WIDTHS if args.tied else (WIDTHS,)):
         layers, pr = make(widths=widths)
